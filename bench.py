@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the driver's measurement contract for the EFTS-CNN hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one synthetic batch.  Default workload = BASELINE.json configs[1]: the EFTS-CNN
@@ -13,21 +13,25 @@ before the timed region.
 `--gpus N` with N > 1: one process per GPU.  Under a launcher (WORLD_SIZE set: torch.distributed.run) the ranks are the
 launcher's and must number N; WITHOUT one this script launches the N ranks itself (re-executing under torch.distributed.run on
 127.0.0.1) and fails unless N ranks come up -- it never silently measures one GPU.  The forward has no exchange step, so its
-N-GPU value is N replicas (weak scaling, frames of all ranks / max-over-ranks time).  The same line then carries `train32`:
+N-GPU value is N replicas (weak scaling, frames of all ranks / max-over-ranks time).  With --full the line then carries `train32`:
 BASELINE configs 3 / 4, the data-parallel training step at batch 32 per GPU with the bucketed RCCL gradient all-reduce overlapped
 with the backward (efficient_tts_amd/bench_train.py), with its `dp` record (backend, ranks, bytes and time per bucket, exposed wait,
 RCCL's own topology lines, bit-exact replica check).  `--workload train32` times only that step.  At N > 1 the forward result is
 protected from that record: an exception in it costs the record (`train32.error`), a hang is cut after EFTS_BENCH_DP_TIMEOUT
 (240) seconds by a watchdog that prints the line with what there is and ends every rank.
 
-The default line (N = 1, fwd64) carries every BASELINE config under the one invocation the driver times (round 6): `parity_mode` (bf16x3, the 1e-3 grade,
+A plain run of the forward workloads does only what its headline needs: it sets up, warms up, times exactly K steps, writes the last step's outputs with
+--dump-outputs DIR (float32 .npy files, fixed seeded inputs and weights: two builds run with the same arguments can be compared output
+for output) and prints the line: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step, in milliseconds).
+
+With --full the line (N = 1, fwd64) carries every BASELINE config under the one invocation: `parity_mode` (bf16x3, the 1e-3 grade,
 same K / W), `long16` (config 5: B=16 x (128, 1200), both precisions), `infer64` (config 2-ii: batched free-running inference), `infer_lj` (config 1: ten
 LJSpeech utterances one by one, + end-to-end with the vocoder), `train32` (config 3, + its parity mode), each with ms_per_step, roofline, the oracle as
 checker (hip_vs_oracle_mel_max_abs) and a bounded CPU leg; and `stock_gpu_baseline`: the oracle's plain torch ops on THIS GPU (MIOpen / hipBLASLt, fp32 and
 bf16 autocast; forward B=64 and training step B=32) -- a second baseline leg beside `cpu_baseline`, never the product.
 
-Prints ONE JSON line on rank 0, with `roofline` for the dominant kernel (the k5 Conv1d contraction at mel length, measured with HIP
-events on the launch stream inside the timed region; `traffic` from two rocprofv3 PMC child passes) and `cpu_baseline` (the
+Prints ONE JSON line on rank 0; with --full it holds `roofline` for the dominant kernel (the k5 Conv1d contraction at mel length, measured with HIP
+events on the launch stream over eager steps after the timed region; `traffic` from two rocprofv3 PMC child passes) and `cpu_baseline` (the
 oracle's CPU restatement timed on this box's host cores on a bounded sample).
 """
 import argparse
@@ -51,7 +55,7 @@ PEAK_HBM_GBS = 8000.0
 FWD_FLOP_PER_ITEM = 21.43e9           # SURVEY.md 8d, (T1, T2) = (128, 800)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # defaults: long enough for the clock governor to settle (the chip runs this workload at its 1 400 W cap and ramps for tens of
@@ -71,18 +75,28 @@ def parse():
     ap.add_argument("--resconv-min-rows", type=int, default=-1, help="A/B: row-space size from which the stacks run on efts_resconv5")
     ap.add_argument("--graph", type=int, default=0, help="forward workloads. 0 (default): the timed step is a plain model(...) call, as a drop-in caller issues it (the model replays a per-shape hipGraph internally); 1: a bench-level hipGraph of the eager launches")
     ap.add_argument("--model-graphs", type=int, default=1, help="0 with --graph 0: the model's internal graph cache off = every kernel launched eagerly")
-    ap.add_argument("--parity-mode", type=int, default=1, help="forward workloads in bf16: also time the bf16x3 parity-grade mode (same K / W) -> `parity_mode` in the JSON line")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline as well: the CPU and stock-GPU baselines, the parity-grade mode, call modes, "
+                    "the other BASELINE configs, the training record, roofline and PMC traffic (each switch below defaults to 1 with --full, 0 without; "
+                    "an explicit value wins). Without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="forward workloads: after the timed steps, write what the last timed step returned "
+                    "(loss, mel_loss, duration_loss, imv, reconst_alpha, mel_pred) as DIR/<name>.npy, float32, at most 64 MB in all")
+    ap.add_argument("--parity-mode", type=int, default=None, help="forward workloads in bf16: also time the bf16x3 parity-grade mode (same K / W) -> `parity_mode` in the JSON line")
     ap.add_argument("--train-graph", type=int, default=1, help="train32, one process: the step as one hipGraph replay (0: eager launches)")
-    ap.add_argument("--call-modes", type=int, default=1, help="forward workloads, N=1: 10 extra steps per call mode (plain call / bench graph / eager) -> `call_modes`")
-    ap.add_argument("--train-record", type=int, default=1, help="fwd64, N=1: also time BASELINE config 3 (training step B=32, 40 steps) under the same invocation -> `train32` in the JSON line")
-    ap.add_argument("--sub-records", type=int, default=1, help="fwd64, N=1: also time BASELINE configs 5, 2-ii and 1 under the same invocation -> `long16`, `infer64`, `infer_lj` in the JSON line")
-    ap.add_argument("--stock-gpu", type=int, default=1, help="fwd64, N=1: also time the oracle's plain torch ops on this GPU (MIOpen / hipBLASLt, fp32 and bf16 autocast) -> `stock_gpu_baseline`")
+    ap.add_argument("--call-modes", type=int, default=None, help="forward workloads, N=1: 10 extra steps per call mode (plain call / bench graph / eager) -> `call_modes`")
+    ap.add_argument("--train-record", type=int, default=None, help="fwd64: also time BASELINE config 3 (training step B=32, 40 steps) under the same invocation -> `train32` in the JSON line")
+    ap.add_argument("--sub-records", type=int, default=None, help="fwd64, N=1: also time BASELINE configs 5, 2-ii and 1 under the same invocation -> `long16`, `infer64`, `infer_lj` in the JSON line")
+    ap.add_argument("--stock-gpu", type=int, default=None, help="fwd64, N=1: also time the oracle's plain torch ops on this GPU (MIOpen / hipBLASLt, fp32 and bf16 autocast) -> `stock_gpu_baseline`")
     ap.add_argument("--stock-find", type=int, default=0, help="stock_gpu_baseline: 1 = torch.backends.cudnn.benchmark = True (MIOpen's exhaustive solver search, as nntts/bin/train.py:60 sets it; tens of seconds per new shape)")
-    ap.add_argument("--measure-traffic", type=int, default=1, help="forward workloads, N=1: roofline.traffic from two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) over a 2-step child run, when rocprofv3 is on the box; 0: the committed profiles/traffic.json")
+    ap.add_argument("--measure-traffic", type=int, default=None, help="forward workloads, N=1, with --full: roofline.traffic from two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) over a 2-step child run, when rocprofv3 is installed; 0: the committed profiles/traffic.json")
     ap.add_argument("--test-shape", default="", metavar="B,T1,T2", help="PLUMBING TESTS ONLY (tests/test_dist_gpu.py: eight ranks sharing one GPU over gloo): fwd64 / train32 at this shape "
                     "instead of BASELINE's, the training record at --steps / --warmup; the line says so in config.workload")
     ap.add_argument("--rc-kernel", type=int, default=0, help="A/B: efts_resconv5_args.kernel of every launch: 0 the 8-wave ping-pong kernel (default), 2 the one-wave-per-SIMD kernel where it applies")
-    return ap.parse_args()
+    a = ap.parse_args(argv)
+    for k in ("parity_mode", "call_modes", "train_record", "sub_records", "stock_gpu", "measure_traffic"):
+        if getattr(a, k) is None:
+            setattr(a, k, int(a.full))
+    a.no_cpu_baseline = a.no_cpu_baseline or not a.full
+    return a
 
 
 WORKLOADS = {
@@ -99,6 +113,31 @@ def synth(B, T1, T2, seed, dev):
     tl = torch.full((B,), T1, dtype=torch.int64, device=dev)
     sl = torch.full((B,), T2, dtype=torch.int64, device=dev)
     return text, tl, mel, sl
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: write each tensor of `arrays` (name -> tensor) as path/<name>.npy in float32.  When the whole exceeds `budget`, every
+    array is cut to its share of it by a fixed sample (seed 0, sorted flat indices, the same for the same shape): two builds run with the same
+    arguments write the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in host.values())
+    for name, v in host.items():
+        if total > budget and v.size > 1:
+            keep = max(1, int(v.size * budget // total))
+            v = v.reshape(-1)[np.unique(np.random.default_rng(0).integers(0, v.size, keep))]
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float32))
+
+
+def forward_outputs(out):
+    """what a caller of model(text, tl, mel, sl) receives, by name (the last element, the input mel handed back, is left out)"""
+    loss, stats, imv, ralpha, mel_pred, _ = out
+    return dict(loss=loss, mel_loss=torch.as_tensor(stats["mel_loss"]), duration_loss=torch.as_tensor(stats["duration_loss"]), imv=imv,
+                reconst_alpha=ralpha, mel_pred=mel_pred)
 
 
 def cpu_baseline(T1, T2, hip_check=None, Bc=64, threads=None, passes=3):
@@ -314,7 +353,7 @@ def measure_traffic(a, precision, workload=None):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, ctr)
             cmd = [exe, "--kernel-trace", "--pmc", ctr, "-d", out, "-o", "b", "--", sys.executable, os.path.abspath(__file__),
-                   "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--parity-mode", "0", "--call-modes", "0", "--train-record", "0",
+                   "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--parity-mode", "0", "--call-modes", "0", "--train-record", "0",
                    "--measure-traffic", "0", "--train-graph", "0", "--rc-kernel", str(a.rc_kernel), "--precision", precision, "--workload", workload or a.workload]
             subprocess.run(cmd, cwd="/tmp", env=env, timeout=150, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
             dbs = glob.glob(os.path.join(out, "**", "*.db"), recursive=True)
@@ -840,6 +879,8 @@ def main():
         tb, t1, t2 = (int(v) for v in a.test_shape.split(","))
         for k in ("fwd64", "train32"):
             WORKLOADS[k].update(B=tb, T1=t1, T2=t2, desc=WORKLOADS[k]["desc"] + f" [TEST SHAPE {tb} x ({t1}, {t2}): a plumbing run, not a measurement]")
+    if a.dump_outputs and a.workload not in ("fwd64", "fwd16_long"):
+        raise SystemExit(f"--dump-outputs: written by the forward workloads (fwd64, fwd16_long), not by --workload {a.workload}")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         raise SystemExit(_self_launch(a))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1037,12 +1078,15 @@ def run_forward(a, world, rank, dev, wl, sub=None):
             dt = float(t.item())
         loss = float(out[0])
         assert loss == loss, "NaN loss"
-        return dt, loss, step
+        return dt, loss, step, out
 
     model = build(a.precision)
     mode = "graph" if a.graph == 1 else ("call" if a.model_graphs else "eager")
-    dt, loss, step = timed(model, a.steps, a.warmup, mode)               # ---- THE timed region: exactly K steps
-    roof = conv_roofline(P, model, step, B, T2, a.precision, wname, a, traffic_ok=sub is None)
+    dt, loss, step, out = timed(model, a.steps, a.warmup, mode)          # ---- THE timed region: exactly K steps
+    if a.dump_outputs and rank == 0 and sub is None:
+        dump_outputs(a.dump_outputs, forward_outputs(out))              # (before any further step: graph replays write into the same buffers)
+    del out
+    roof = conv_roofline(P, model, step, B, T2, a.precision, wname, a, traffic_ok=sub is None) if a.full else None
 
     def line(precision, dt, steps):
         frames = world * B * T2 * steps
@@ -1069,15 +1113,15 @@ def run_forward(a, world, rank, dev, wl, sub=None):
     parity_model = None
     if a.precision == "bf16" and a.parity_mode:
         parity_model = build("bf16x3", {k: v.detach() for k, v in model.state_dict().items()})
-        dt2, loss2, step2 = timed(parity_model, a.steps, a.warmup, mode)
-        roof2 = conv_roofline(P, parity_model, step2, B, T2, "bf16x3", wname, a, traffic_ok=sub is None)
+        dt2, loss2, step2, _ = timed(parity_model, a.steps, a.warmup, mode)
+        roof2 = conv_roofline(P, parity_model, step2, B, T2, "bf16x3", wname, a, traffic_ok=sub is None) if a.full else None
         if rank == 0:
             res["parity_mode"] = dict(precision="bf16x3", dtype="bf16x3 (split-bf16 MFMA operands: hi*hi + hi*lo + lo*hi, fp32 accumulate)",
                                       steps=a.steps, warmup=a.warmup, loss=loss2, roofline=roof2, **line("bf16x3", dt2, a.steps))
     if rank == 0 and world == 1 and a.call_modes and sub is None:
         cm = {}
         for md in ("call", "graph", "eager"):
-            d, _, _ = timed(model, 10, 2, md)
+            d, _, _, _ = timed(model, 10, 2, md)
             cm[md + "_ms"] = d / 10 * 1e3
         res["call_modes"] = dict(cm, note="10 steps each after the timed region: plain model() call (the model's own per-shape choice) / bench-level hipGraph / eager launches")
     if rank == 0 and world == 1 and not a.no_cpu_baseline:

@@ -46,14 +46,14 @@ done
 fi
 cd $R
 if [ -z "$SKIP_BENCH" ]; then
-python bench.py > $O/bench_fwd64_$TAGR.json 2> $O/bench_fwd64.err
-python bench.py --workload fwd16_long > $O/bench_fwd16_long_$TAGR.json 2> $O/bench_fwd16_long.err
-python bench.py --workload train32 > $O/bench_train32_bf16_$TAGR.json 2> $O/bench_train32.err
-python bench.py --workload train32 --precision bf16x3 --no-cpu-baseline > $O/bench_train32_bf16x3_$TAGR.json 2>> $O/bench_train32.err
-python bench.py --workload infer64 > $O/bench_infer64_bf16_$TAGR.json 2> $O/bench_infer.err
-python bench.py --workload infer_lj > $O/bench_infer_lj_bf16_$TAGR.json 2>> $O/bench_infer.err
+python bench.py --full > $O/bench_fwd64_$TAGR.json 2> $O/bench_fwd64.err
+python bench.py --full --workload fwd16_long > $O/bench_fwd16_long_$TAGR.json 2> $O/bench_fwd16_long.err
+python bench.py --full --workload train32 > $O/bench_train32_bf16_$TAGR.json 2> $O/bench_train32.err
+python bench.py --full --workload train32 --precision bf16x3 --no-cpu-baseline > $O/bench_train32_bf16x3_$TAGR.json 2>> $O/bench_train32.err
+python bench.py --full --workload infer64 > $O/bench_infer64_bf16_$TAGR.json 2> $O/bench_infer.err
+python bench.py --full --workload infer_lj > $O/bench_infer_lj_bf16_$TAGR.json 2>> $O/bench_infer.err
 # the forward on the one-wave-per-SIMD kernel (where it is eligible), interleaved with the default for an in-situ comparison
-for k in 0 2 0 2; do python bench.py --rc-kernel $k --no-cpu-baseline --parity-mode 0 --call-modes 0 --measure-traffic 0 --train-record 0 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readlines()[-1]); print('rc-kernel $k', 'ms_per_step', round(d['ms_per_step'], 4), 'roofline', d['roofline']['achieved'], d['roofline']['frac'])"; done > $O/bench_rc_kernel_ab_$TAGR.txt 2>&1
+for k in 0 2 0 2; do python bench.py --full --rc-kernel $k --no-cpu-baseline --parity-mode 0 --call-modes 0 --measure-traffic 0 --train-record 0 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readlines()[-1]); print('rc-kernel $k', 'ms_per_step', round(d['ms_per_step'], 4), 'roofline', d['roofline']['achieved'], d['roofline']['frac'])"; done > $O/bench_rc_kernel_ab_$TAGR.txt 2>&1
 for f in $O/bench_*_$TAGR.json; do test -s $f || { echo "BENCH FAILED: $f"; exit 1; }; done
 fi
 ls -la $O

@@ -17,7 +17,7 @@ def short(name):
     return name.replace("void ", "").replace("efts::", "")[:72]
 
 
-print(f"# rocprofv3 summary {tag}: python bench.py --steps {os.environ.get('STEPS', '5')} --warmup 2 --no-cpu-baseline --parity-mode 0 --call-modes 0 "
+print(f"# rocprofv3 summary {tag}: python bench.py --steps {os.environ.get('STEPS', '5')} --warmup 2 --full --no-cpu-baseline --parity-mode 0 --call-modes 0 "
       f"--precision {os.environ.get('PREC', 'bf16')} --workload {os.environ.get('WL', 'fwd64')} {os.environ.get('BARGS', '')}")
 con = db("trace")
 if con:
