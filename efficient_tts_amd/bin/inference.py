@@ -45,7 +45,8 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--vocoder_checkpoint", type=str, default=None, help='HiFi-GAN checkpoint with a "generator" state_dict')
     p.add_argument("--no_vocoder", action="store_true", help="write <id>_<step>.npy mel-spectrograms instead of wav files")
     p.add_argument("--batch_size", type=int, default=1, help="utterances per acoustic-model call (default 1, as the reference)")
-    p.add_argument("--precision", type=str, default="bf16x3", choices=["bf16x3", "bf16"])
+    p.add_argument("--precision", type=str, default="bf16x3", choices=["bf16x3", "bf16", "fp32"],
+                   help="MFMA operand mode of the acoustic model and the vocoder (fp32: exact fp32 operands, the reference-parity mode)")
     p.add_argument("--verbose", type=int, default=1)
     return p
 

@@ -170,7 +170,8 @@ extern "C" int efts_act_apply(const float* z, const float* resid, const float* r
                               void* stream) {
     if (!z || (!y_f32 && !plane)) return efts_fail(EFTS_EINVAL, "efts_act_apply: null pointer");
     if (act < 0 || act >= EFTS_ACTFN_COUNT) return efts_fail(EFTS_EINVAL, "efts_act_apply: unknown activation %d", act);
-    if (rows <= 0 || c <= 0 || c % 4 || (plane && !(split == 1 || split == 2))) return efts_fail(EFTS_ESHAPE, "efts_act_apply: c must be a positive multiple of 4");
+    if (rows <= 0 || c <= 0 || c % 4) return efts_fail(EFTS_ESHAPE, "efts_act_apply: c must be a positive multiple of 4");
+    if (plane && !(split >= EFTS_SPLIT_BF16 && split <= EFTS_SPLIT_FP32)) return efts_fail(EFTS_EINVAL, "efts_act_apply: split must be 1, 2 or 3");
     unsigned thresh, seed_h; float inv_keep;
     if (int rc = drop_params(drop_p, drop_seed, (long)rows * c, &thresh, &seed_h, &inv_keep, "efts_act_apply")) return rc;
     const long items = (long)rows * (c >> 2);
@@ -184,7 +185,8 @@ extern "C" int efts_act_grad(const float* g, const float* z, const float* rowmas
                              void* stream) {
     if (!g || !z || (!dz && !plane)) return efts_fail(EFTS_EINVAL, "efts_act_grad: null pointer");
     if (act < 0 || act >= EFTS_ACTFN_COUNT) return efts_fail(EFTS_EINVAL, "efts_act_grad: unknown activation %d", act);
-    if (rows <= 0 || c <= 0 || c % 4 || (plane && !(split == 1 || split == 2))) return efts_fail(EFTS_ESHAPE, "efts_act_grad: c must be a positive multiple of 4");
+    if (rows <= 0 || c <= 0 || c % 4) return efts_fail(EFTS_ESHAPE, "efts_act_grad: c must be a positive multiple of 4");
+    if (plane && !(split == EFTS_SPLIT_BF16 || split == EFTS_SPLIT_BF16X3)) return efts_fail(EFTS_EINVAL, "efts_act_grad: split must be 1 or 2 (training has no fp32 form)");
     unsigned thresh, seed_h; float inv_keep;
     if (int rc = drop_params(drop_p, drop_seed, (long)rows * c, &thresh, &seed_h, &inv_keep, "efts_act_grad")) return rc;
     hipLaunchKernelGGL(act_grad_kernel, dim3((rows + 63) / 64, (c + 127) / 128), dim3(256), 0, (hipStream_t)stream, g, z, rowmask, act, p0, p1, dz,

@@ -23,7 +23,8 @@
 //     applied on the per-lane SOURCE address and again on the ds_read_b128 address.
 //   * K is consumed in 128-byte chunks: 64 bf16 ("bf16"), or 32 hi + 32 lo bf16 ("bf16x3":
 //     x = hi + lo, product = hi*hi + hi*lo + lo*hi, fp32 accumulate -> fp32-class accuracy at
-//     3 MFMAs per product instead of the 16x slower f32 MFMA).
+//     3 MFMAs per product instead of the 16x slower f32 MFMA), or 32 fp32 ("fp32", split 3: the exact
+//     operands on v_mfma_f32_32x32x2_f32, generic tiling only -- the reference-parity mode).
 //   * epilogue fused: bias, LeakyReLU/ReLU, residual add, row mask (gap rows / padded
 //     positions), fp32 store and bf16 operand planes for the next contraction.  The residual and
 //     mask values are requested at the start of the LAST K step, so their HBM latency hides under
@@ -157,6 +158,32 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmKernelArgs p) {
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[kk & 1][i], bfr[kk & 1][j], acc[i][j], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else if constexpr (SPLIT == 3) {
+            // fp32 planes (efts_abi.h split 3): a chunk row is 8 slots of 4 floats.  Lane half h reads slot 2q + h of each 32-row
+            // fragment; MFMA (q, e) of v_mfma_f32_32x32x2_f32 takes element e of it, i.e. k = 8q + e (h = 0) and 8q + 4 + e (h = 1).
+            // A and B are permuted alike, so the 16 MFMAs sum over all 32 k's; the four accumulators are independent (64-cycle latency).
+            f32x4 af[2][2], bfr[2][2];
+            auto ld = [&](int q, int b) {
+                const int slot = q * 2 + lhalf;
+#pragma unroll
+                for (int i = 0; i < 2; ++i) af[b][i] = *(const f32x4*)(at + lds_off(arow + i * 32, slot));
+#pragma unroll
+                for (int j = 0; j < 2; ++j) bfr[b][j] = *(const f32x4*)(wt + lds_off(brow + j * 32, slot));
+            };
+            ld(0, 0);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (q + 1 < 4) ld(q + 1, (q + 1) & 1);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q & 1][i][e], bfr[q & 1][j][e], acc[i][j], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
         } else {
@@ -320,12 +347,14 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmKernelArgs p) {
         }
     }
     float part_sq = 0.f;
+    // plane format of out_bf16: known at compile time to be 3 in the split-3 kernel and 1 / 2 (never 3) in the others
+    const int osp = SPLIT == 3 ? EFTS_SPLIT_FP32 : (p.out_split == 2 ? 2 : 1);
     if (pre) {
         const __amdgpu_buffer_rsrc_t ro = make_rsrc(of ? of + (long)m0 * p.ldo : nullptr, of ? (long)rows_out * p.ldo * 4 : 0);
         const __amdgpu_buffer_rsrc_t rb = make_rsrc(ob ? ob + (long)m0 * p.ldob : nullptr, ob ? (long)rows_out * p.ldob : 0);
         const __amdgpu_buffer_rsrc_t rbl = make_rsrc(obl ? obl + (long)m0 * p.ldob : nullptr, obl ? (long)rows_out * p.ldob : 0);
         const unsigned vo = trow * (unsigned)p.ldo * 4 + col * 4, so = RPP * (unsigned)p.ldo * 4;
-        const unsigned vb = trow * (unsigned)p.ldob + (unsigned)plane_off_hi(col, p.out_split), sb = RPP * (unsigned)p.ldob;
+        const unsigned vb = trow * (unsigned)p.ldob + (unsigned)plane_off_hi(col, osp), sb = RPP * (unsigned)p.ldob;
         const bool has_mask = rowmask != nullptr;
         float sq = 0.f;                                      // p.sqerr: this thread's share of sum (out - target)^2, sweeps in ascending order
         const unsigned ld_sg = (unsigned)(p.n >> 3);
@@ -368,6 +397,11 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmKernelArgs p) {
                     v.x = v.x > 0.f ? v.x : v.x * p.plane_slope; v.y = v.y > 0.f ? v.y : v.y * p.plane_slope;
                     v.z = v.z > 0.f ? v.z : v.z * p.plane_slope; v.w = v.w > 0.f ? v.w : v.w * p.plane_slope;
                 }
+                if constexpr (SPLIT == 3) {                          // fp32 plane (out_split 3 comes with split 3 only): the exact value
+                    const u32x4 o = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+                    store_b128(o, rb, vb, ps * sb);
+                    continue;
+                }
                 float r0, r1, r2, r3;
                 const u32x2 hi = {pack_bf16x2(v.x, v.y, &r0, &r1), pack_bf16x2(v.z, v.w, &r2, &r3)};
                 __builtin_amdgcn_raw_buffer_store_b64(hi, rb, vb, ps * sb, EFTS_AUX_STP);
@@ -398,7 +432,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmKernelArgs p) {
                 }
                 v.x *= rm; v.y *= rm; v.z *= rm; v.w *= rm;
                 if (of) *(float4*)(of + (long)row * p.ldo + col) = v;
-                if (ob) plane_store4(ob + (long)row * p.ldob, col, v.x, v.y, v.z, v.w, p.out_split);
+                if (ob) plane_store4(ob + (long)row * p.ldob, col, v.x, v.y, v.z, v.w, osp);
                 if (obl) {
                     plane_store4(obl + (long)row * p.ldob, col, v.x - bf16_to_f32(f32_to_bf16(v.x)), v.y - bf16_to_f32(f32_to_bf16(v.y)),
                                  v.z - bf16_to_f32(f32_to_bf16(v.z)), v.w - bf16_to_f32(f32_to_bf16(v.w)), 1);
@@ -414,8 +448,9 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmKernelArgs p) {
                     if (of) of[(long)row * p.ldo + col + u] = t;
                     if (ob) {
                         if (p.plane_act) t = t > 0.f ? t : t * p.plane_slope;
+                        char* d = ob + (long)row * p.ldob + plane_off_hi(col + u, osp);
+                        if constexpr (SPLIT == 3) { *(float*)d = t; continue; }
                         const unsigned short hi = f32_to_bf16(t);
-                        char* d = ob + (long)row * p.ldob + plane_off_hi(col + u, p.out_split);
                         *(unsigned short*)d = hi;
                         if (p.out_split == 2) *(unsigned short*)(d + 64) = f32_to_bf16(t - bf16_to_f32(hi));
                         else if (obl) *(unsigned short*)(obl + (long)row * p.ldob + (col + u) * 2) = f32_to_bf16(t - bf16_to_f32(hi));
@@ -482,7 +517,7 @@ static void launch_debug(dim3 grid, hipStream_t st, GemmKernelArgs k, int prof) 
 
 extern "C" int efts_gemm(const efts_gemm_args* a, void* stream) {
     if (!a) return efts_fail(EFTS_EINVAL, "efts_gemm: null args");
-    if (!(a->split == 1 || a->split == 2)) return efts_fail(EFTS_EINVAL, "efts_gemm: split must be 1 or 2");
+    if (!(a->split >= EFTS_SPLIT_BF16 && a->split <= EFTS_SPLIT_FP32)) return efts_fail(EFTS_EINVAL, "efts_gemm: split must be 1, 2 or 3");
     if (!(a->taps == 1 || a->taps == 3 || a->taps == 5 || a->taps == 7 || a->taps == 9 || a->taps == 11)) return efts_fail(EFTS_EINVAL, "efts_gemm: taps must be 1, 3, 5, 7, 9 or 11");
     const int dil = a->dilation > 0 ? a->dilation : 1;
     if ((a->taps - 1) * dil > 64) return efts_fail(EFTS_ESHAPE, "efts_gemm: (taps - 1) * dilation must not exceed 64 rows");
@@ -494,7 +529,9 @@ extern "C" int efts_gemm(const efts_gemm_args* a, void* stream) {
     if (a->lda < (int64_t)a->nchunk * 128 || a->ldb < (int64_t)a->nchunk * 128)
         return efts_fail(EFTS_ESHAPE, "efts_gemm: row stride smaller than nchunk*128 bytes");
     if (a->lda > (1 << 23) || a->ldb > (1 << 23)) return efts_fail(EFTS_ESHAPE, "efts_gemm: row stride above 8 MiB");
-    if (a->out_bf16 && !(a->out_split == 1 || a->out_split == 2)) return efts_fail(EFTS_EINVAL, "efts_gemm: out_split must be 1 or 2");
+    if (a->out_bf16 && !(a->out_split >= EFTS_SPLIT_BF16 && a->out_split <= EFTS_SPLIT_FP32)) return efts_fail(EFTS_EINVAL, "efts_gemm: out_split must be 1, 2 or 3");
+    if (a->out_bf16 && ((a->out_split == EFTS_SPLIT_FP32) != (a->split == EFTS_SPLIT_FP32)))
+        return efts_fail(EFTS_EINVAL, "efts_gemm: out_split 3 (fp32 plane) goes with split 3 operands, and split 3 writes fp32 planes only");
     if (!a->out_f32 && !a->out_bf16 && !a->soft_index) return efts_fail(EFTS_EINVAL, "efts_gemm: no output");
 
     GemmKernelArgs k;
@@ -526,7 +563,8 @@ extern "C" int efts_gemm(const efts_gemm_args* a, void* stream) {
     k.alpha = a->alpha; k.slope = a->slope; k.act = a->act; k.out_split = a->out_split;
     k.vec_ok = (!a->out_f32 || ((a->ldo & 3) == 0 && ((uintptr_t)a->out_f32 & 15) == 0 && (a->out_batch_stride & 3) == 0)) &&
                (!a->resid || ((a->ldr & 3) == 0 && ((uintptr_t)a->resid & 15) == 0 && (a->resid_batch_stride & 3) == 0)) &&
-               (!a->out_bf16 || ((a->ldob & 7) == 0 && ((uintptr_t)a->out_bf16 & 7) == 0 && (a->outb_batch_stride & 7) == 0));
+               (!a->out_bf16 || ((a->ldob & 7) == 0 && ((uintptr_t)a->out_bf16 & 7) == 0 && (a->outb_batch_stride & 7) == 0)) &&
+               (!a->out_bf16 || a->out_split != EFTS_SPLIT_FP32 || ((a->ldob & 15) == 0 && ((uintptr_t)a->out_bf16 & 15) == 0 && (a->outb_batch_stride & 15) == 0));
     k.prof = nullptr; k.dbg = 0;
     if (a->soft_index && (!a->key_len || !a->query_len || a->n > BN || nb2 > 1 || a->resid || a->out_bf16 || a->taps != 1 || a->act != EFTS_ACT_NONE))
         return efts_fail(EFTS_EINVAL, "efts_gemm: soft_index needs key_len / query_len, n <= 128, one tap, no activation, residual, plane output or batch2");
@@ -547,6 +585,10 @@ extern "C" int efts_gemm(const efts_gemm_args* a, void* stream) {
     // for the bit-equality tests between the kernels (they all compute identical results).
     const int tiling = a->tiling;
     if (tiling < EFTS_TILING_AUTO || tiling > EFTS_TILING_SMALLM) return efts_fail(EFTS_EINVAL, "efts_gemm: unknown tiling %d", tiling);
+    // fp32 planes: the generic kernel only (AUTO goes there); the other tilings have no split-3 main loop and never run one as bf16
+    const bool fp32 = a->split == EFTS_SPLIT_FP32;
+    if (fp32 && tiling > EFTS_TILING_GENERIC)
+        return efts_fail(EFTS_EINVAL, "efts_gemm: split 3 (fp32) runs on the generic tiling only (tiling %d requested)", tiling);
     // (0) short row spaces on request (never AUTO: the K dimension is split across the waves, so the summation order -- not the
     //     operand rounding -- differs from the ring kernels): 64 x 32 tiles, fragments straight from global memory
     if (tiling == EFTS_TILING_SMALLM) {
@@ -568,7 +610,7 @@ extern "C" int efts_gemm(const efts_gemm_args* a, void* stream) {
     if (tiling == EFTS_TILING_RESIDENT && !resident_ok) return efts_fail(EFTS_ESHAPE, "efts_gemm: the resident tiling needs n <= 64, one K chunk, taps 3 / 7 / 11");
     if (no_narrow && !generic_only && (tiling == EFTS_TILING_NARROW || tiling == EFTS_TILING_RESIDENT))
         return efts_fail(EFTS_EINVAL, "efts_gemm: sign_mask needs the generic or wide tiling");
-    if (!no_narrow && resident_ok && (tiling == EFTS_TILING_RESIDENT || (tiling == EFTS_TILING_AUTO && a->m >= 8 * R32_WIN))) {
+    if (!fp32 && !no_narrow && resident_ok && (tiling == EFTS_TILING_RESIDENT || (tiling == EFTS_TILING_AUTO && a->m >= 8 * R32_WIN))) {
         GemmKernelArgs kr = k;
         kr.bm = R32_WIN - (a->taps - 1) * dil;
         kr.mtiles = (a->m + kr.bm - 1) / kr.bm;
@@ -580,7 +622,7 @@ extern "C" int efts_gemm(const efts_gemm_args* a, void* stream) {
     //     at one utterance: 110): such a launch is bound by the per-workgroup step latency, and 64-column tiles double the
     //     number of workgroups that overlap (one per CU is the measured threshold; two was slower for the text side)
     const bool few = (long)k.mtiles * k.ntiles * a->batch < (long)efts_num_cus() && a->n > 64;
-    if (!no_narrow && (tiling == EFTS_TILING_NARROW || (tiling == EFTS_TILING_AUTO && (a->n <= 64 || few)))) {
+    if (!fp32 && !no_narrow && (tiling == EFTS_TILING_NARROW || (tiling == EFTS_TILING_AUTO && (a->n <= 64 || few)))) {
         GemmKernelArgs kn = k;
         kn.ntiles = a->n <= 32 ? 1 : (a->n + 63) / 64;
         if (launch_narrow_any(a->split, a->n <= 32 ? 32 : 64, a->taps, dim3(k.mtiles * kn.ntiles, a->batch, 1), st, kn)) return efts_check_launch("efts_gemm");
@@ -593,7 +635,7 @@ extern "C" int efts_gemm(const efts_gemm_args* a, void* stream) {
     const int mt5 = (a->m + C5_BM - 1) / C5_BM;
     const bool wide_fits = (long)mt5 * C5_BM + 2 - a->m <= 144;
     if (tiling == EFTS_TILING_WIDE && !(wide_ok && wide_fits)) return efts_fail(EFTS_ESHAPE, "efts_gemm: the wide tiling is for dense k5 launches whose last 256-row window stays inside the guard rows");
-    if (!generic_only && wide_ok && wide_fits &&
+    if (!fp32 && !generic_only && wide_ok && wide_fits &&
         (tiling == EFTS_TILING_WIDE || (tiling == EFTS_TILING_AUTO && a->split == 1 && (long)mt5 * k.ntiles * a->batch >= C5_DEFAULT_MIN_TILES))) {
         GemmKernelArgs k5 = k;
         k5.mtiles = mt5;
@@ -613,14 +655,23 @@ extern "C" int efts_gemm(const efts_gemm_args* a, void* stream) {
         const char* ed = getenv("EFTS_GEMM_DBG");
         const char* ep = getenv("EFTS_GEMM_PROF");
         const int dbg = ed ? atoi(ed) : 0, prof = ep ? atoi(ep) : 0;
-        if ((dbg || prof) && a->taps == 5) {
+        if ((dbg || prof) && a->taps == 5 && !fp32) {
             k.dbg = dbg;
             if (a->split == 1) launch_debug<1>(grid, st, k, prof); else launch_debug<2>(grid, st, k, prof);
             return efts_check_launch("efts_gemm");
         }
     }
 #endif
-    if (a->split == 1) {
+    if (fp32) {
+        switch (a->taps) {
+            case 11: launch_one<11, 3, 0>(grid, st, k); break;
+            case 9: launch_one<9, 3, 0>(grid, st, k); break;
+            case 7: launch_one<7, 3, 0>(grid, st, k); break;
+            case 5: launch_one<5, 3, 0>(grid, st, k); break;
+            case 3: launch_one<3, 3, 0>(grid, st, k); break;
+            default: launch_one<1, 3, 0>(grid, st, k);
+        }
+    } else if (a->split == 1) {
         switch (a->taps) {
             case 11: launch_one<11, 1, 0>(grid, st, k); break;
             case 9: launch_one<9, 1, 0>(grid, st, k); break;
@@ -653,6 +704,7 @@ __attribute__((visibility("hidden"))) void efts_gemm_init(void) {
         conv5_set_lds_attr();
         set_lds_attr<5, 1>(); set_lds_attr<3, 1>(); set_lds_attr<1, 1>(); set_lds_attr<5, 2>(); set_lds_attr<3, 2>(); set_lds_attr<1, 2>();
         set_lds_attr<7, 1>(); set_lds_attr<11, 1>(); set_lds_attr<7, 2>(); set_lds_attr<11, 2>(); set_lds_attr<9, 1>(); set_lds_attr<9, 2>();
+        set_lds_attr<1, 3>(); set_lds_attr<3, 3>(); set_lds_attr<5, 3>(); set_lds_attr<7, 3>(); set_lds_attr<9, 3>(); set_lds_attr<11, 3>();
         once = true;
     }
 }

@@ -55,13 +55,17 @@ __device__ __forceinline__ unsigned short f32_to_bf16(float f) {
 }
 __device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
 
-// Byte offset of element k of an operand-plane row (see efts_abi.h "MFMA operand planes").
+// Byte offset of element k of an operand-plane row (see efts_abi.h "MFMA operand planes"); split 2: of its hi half.
 __device__ __forceinline__ long plane_off_hi(int k, int split) {
-    return split == 1 ? (long)k * 2 : (long)(k >> 5) * 128 + (k & 31) * 2;
+    return split == 1 ? (long)k * 2 : (long)(k >> 5) * 128 + (k & 31) * (split == EFTS_SPLIT_FP32 ? 4 : 2);
 }
 
-// Store 4 consecutive k's (k % 4 == 0) of one row into an operand plane.
+// Store 4 consecutive k's (k % 4 == 0) of one row into an operand plane (split 3: one 16-byte store of the unrounded floats).
 __device__ __forceinline__ void plane_store4(char* row, int k, float v0, float v1, float v2, float v3, int split) {
+    if (split == EFTS_SPLIT_FP32) {
+        *(float4*)(row + plane_off_hi(k, split)) = make_float4(v0, v1, v2, v3);
+        return;
+    }
     const unsigned p0 = cvt_pk_bf16(v0, v1), p1 = cvt_pk_bf16(v2, v3);
     char* d = row + plane_off_hi(k, split);
     *(uint2*)d = make_uint2(p0, p1);

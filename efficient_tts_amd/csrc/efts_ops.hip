@@ -308,7 +308,7 @@ __global__ void dur_target_kernel(const float* __restrict__ e, const int* __rest
 __global__ __launch_bounds__(256) void reconst_alpha_kernel(const float* __restrict__ e, const int* __restrict__ tlen,
                                                             const int* __restrict__ mlen, float sigma,
                                                             float* __restrict__ alpha, char* __restrict__ plane,
-                                                            long ldp, int T1, int T2, int T2p) {
+                                                            long ldp, int T1, int T2, int T2p, int split) {
     extern __shared__ float es[];   // e[b, :]
     __shared__ float red[4][64];
     __shared__ float tile[64][33];
@@ -358,17 +358,17 @@ __global__ __launch_bounds__(256) void reconst_alpha_kernel(const float* __restr
             if (pj < T2) {
                 char* prow = plane + ((long)b * T2p + pj) * ldp;
                 const float* t = &tile[prow_l][pq * 8];
-                plane_store4(prow, i0 + pq * 8, t[0], t[1], t[2], t[3], 2);
-                plane_store4(prow, i0 + pq * 8 + 4, t[4], t[5], t[6], t[7], 2);
+                plane_store4(prow, i0 + pq * 8, t[0], t[1], t[2], t[3], split);
+                plane_store4(prow, i0 + pq * 8 + 4, t[4], t[5], t[6], t[7], split);
             }
             __syncthreads();
         }
     }
 }
 
-// V [B*T1p][c] fp32 -> V^T split-2 planes [B][c][K = i]; one block = 32 i x 32 c
+// V [B*T1p][c] fp32 -> V^T split-2 (or split-3: fp32) planes [B][c][K = i]; one block = 32 i x 32 c
 __global__ __launch_bounds__(256) void pack_vt_kernel(const float* __restrict__ v, long ldv, char* __restrict__ plane,
-                                                      long ldp, int T1, int T1p, int c) {
+                                                      long ldp, int T1, int T1p, int c, int split) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z, c0 = blockIdx.y * 32, i0 = blockIdx.x * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
@@ -380,6 +380,10 @@ __global__ __launch_bounds__(256) void pack_vt_kernel(const float* __restrict__ 
     for (int r = ty; r < 32; r += 8) {
         if (c0 + r >= c) continue;
         const float x = tile[tx][r];
+        if (split == EFTS_SPLIT_FP32) {
+            *(float*)(plane + ((long)b * c + c0 + r) * ldp + (long)blockIdx.x * 128 + tx * 4) = x;
+            continue;
+        }
         const unsigned short hi = f32_to_bf16(x);
         const unsigned short lo = f32_to_bf16(x - bf16_to_f32(hi));
         char* d = plane + ((long)b * c + c0 + r) * ldp + (long)blockIdx.x * 128 + tx * 2;
@@ -646,7 +650,7 @@ using namespace efts;
 extern "C" int efts_pack_weight(const float* w, const float* g, float* w_f32_out, void* plane, int64_t ldb,
                                 int32_t cout, int32_t cin, int32_t taps, int32_t split, void* stream) {
     if (!w || !plane) return efts_fail(EFTS_EINVAL, "efts_pack_weight: null pointer");
-    if (!(split == 1 || split == 2) || cout <= 0 || cin <= 0 || taps <= 0) return efts_fail(EFTS_ESHAPE, "efts_pack_weight: bad shape/split");
+    if (!(split >= EFTS_SPLIT_BF16 && split <= EFTS_SPLIT_FP32) || cout <= 0 || cin <= 0 || taps <= 0) return efts_fail(EFTS_ESHAPE, "efts_pack_weight: bad shape/split");
     const int kp = split == 1 ? (cin + 63) & ~63 : (cin + 31) & ~31;
     if (ldb < (split == 1 ? kp * 2 : kp * 4) || (ldb & 15)) return efts_fail(EFTS_EALIGN, "efts_pack_weight: ldb too small or not 16-byte aligned");
     hipLaunchKernelGGL(pack_weight_kernel, dim3(cout), dim3(256), 0, ST, w, g, w_f32_out, (char*)plane, (long)ldb, cout, cin, taps, kp, split);
@@ -673,6 +677,7 @@ extern "C" int efts_embed(const int64_t* ids, const float* table, float* f32_out
                           int32_t T, int32_t Tp, int32_t c, int32_t num_symbols, int32_t split, void* stream) {
     if (!ids || !table || (!f32_out && !plane)) return efts_fail(EFTS_EINVAL, "efts_embed: null pointer");
     if (c % 4 || c > 4096 || B <= 0 || T <= 0 || Tp < T) return efts_fail(EFTS_ESHAPE, "efts_embed: c must be a multiple of 4 (<= 4096)");
+    if (plane && !(split >= EFTS_SPLIT_BF16 && split <= EFTS_SPLIT_FP32)) return efts_fail(EFTS_EINVAL, "efts_embed: split must be 1, 2 or 3");
     hipLaunchKernelGGL(embed_kernel, dim3(B * Tp), dim3(((c / 4) + 63) & ~63), 0, ST, (const long*)ids, table, f32_out, (char*)plane,
                        (long)ld_plane, T, Tp, c, num_symbols, split);
     return efts_check_launch("efts_embed");
@@ -685,6 +690,8 @@ extern "C" int efts_embed_conv(const int64_t* ids, const int32_t* lengths, const
     if (c % 4 || c > 4096 || B <= 0 || T <= 0 || Tp < T || num_symbols <= 0 || !(taps == 1 || taps == 3 || taps == 5))
         return efts_fail(EFTS_ESHAPE, "efts_embed_conv: c must be a multiple of 4 (<= 4096), taps 1 / 3 / 5");
     if (((uintptr_t)tap_table | (uintptr_t)f32_out) & 15) return efts_fail(EFTS_EALIGN, "efts_embed_conv: 16-byte aligned tap table and output");
+    if (plane && !(split == EFTS_SPLIT_BF16 || split == EFTS_SPLIT_BF16X3))
+        return efts_fail(EFTS_EINVAL, "efts_embed_conv: split must be 1 or 2 (no fp32 form: efts_embed + efts_gemm)");
     hipLaunchKernelGGL(embed_conv_kernel, dim3(B * Tp), dim3(((c / 4) + 63) & ~63), 0, ST, (const long*)ids, lengths, table, tap_table, bias, slope, f32_out,
                        (char*)plane, (long)ld_plane, T, Tp, c, num_symbols, taps, split);
     return efts_check_launch("efts_embed_conv");
@@ -694,6 +701,7 @@ extern "C" int efts_pack_rows(const float* x, float* f32_out, void* plane, int64
                               int32_t c, int32_t kp, int32_t split, void* stream) {
     if (!x || (!f32_out && !plane)) return efts_fail(EFTS_EINVAL, "efts_pack_rows: null pointer");
     if (kp % 4 || kp < c || kp > 4096) return efts_fail(EFTS_ESHAPE, "efts_pack_rows: kp must be a multiple of 4, >= c");
+    if (plane && !(split >= EFTS_SPLIT_BF16 && split <= EFTS_SPLIT_FP32)) return efts_fail(EFTS_EINVAL, "efts_pack_rows: split must be 1, 2 or 3");
     hipLaunchKernelGGL(pack_rows_kernel, dim3(B * Tp), dim3(((kp / 4) + 63) & ~63), 0, ST, x, f32_out, (char*)plane, (long)ld_plane, T, Tp, c, kp, split);
     return efts_check_launch("efts_pack_rows");
 }
@@ -730,23 +738,26 @@ extern "C" int efts_duration_target(const float* e, const int32_t* text_len, con
 }
 
 extern "C" int efts_reconst_alpha(const float* e, const int32_t* text_len, const int32_t* mel_len, float sigma, float* alpha_out,
-                                  void* plane, int64_t ld_plane, int32_t B, int32_t T1, int32_t T2, int32_t T2p, void* stream) {
+                                  void* plane, int64_t ld_plane, int32_t B, int32_t T1, int32_t T2, int32_t T2p, int32_t split, void* stream) {
     if (!e || (!alpha_out && !plane)) return efts_fail(EFTS_EINVAL, "efts_reconst_alpha: null pointer");
+    if (plane && !(split == EFTS_SPLIT_BF16X3 || split == EFTS_SPLIT_FP32)) return efts_fail(EFTS_EINVAL, "efts_reconst_alpha: split must be 2 or 3");
     if (T1 <= 0 || T2 <= 0 || T2p < T2 || T1 > 8192) return efts_fail(EFTS_ESHAPE, "efts_reconst_alpha: bad shape");
     if (plane && ld_plane < (int64_t)((T1 + 31) / 32) * 128) return efts_fail(EFTS_ESHAPE, "efts_reconst_alpha: ld_plane too small");
     hipLaunchKernelGGL(reconst_alpha_kernel, dim3((T2 + 63) / 64, B), dim3(256), T1 * sizeof(float), ST, e, text_len, mel_len, sigma,
-                       alpha_out, (char*)plane, (long)ld_plane, T1, T2, T2p);
+                       alpha_out, (char*)plane, (long)ld_plane, T1, T2, T2p, split);
     return efts_check_launch("efts_reconst_alpha");
 }
 
-extern "C" int efts_pack_vt(const float* v, int64_t ldv, void* plane, int64_t ld_plane, int32_t B, int32_t T1, int32_t T1p, int32_t c, void* stream) {
+extern "C" int efts_pack_vt(const float* v, int64_t ldv, void* plane, int64_t ld_plane, int32_t B, int32_t T1, int32_t T1p, int32_t c, int32_t split,
+                            void* stream) {
     if (!v || !plane) return efts_fail(EFTS_EINVAL, "efts_pack_vt: null pointer");
+    if (!(split == EFTS_SPLIT_BF16X3 || split == EFTS_SPLIT_FP32)) return efts_fail(EFTS_EINVAL, "efts_pack_vt: split must be 2 or 3");
     if (ld_plane < (int64_t)((T1 + 31) / 32) * 128) return efts_fail(EFTS_ESHAPE, "efts_pack_vt: ld_plane too small");
-    if (c % 64 == 0 && (ldv & 3) == 0 && ((uintptr_t)v & 15) == 0 && (ld_plane & 15) == 0 && ((uintptr_t)plane & 15) == 0 && T1 >= 64) {
+    if (split == EFTS_SPLIT_BF16X3 && c % 64 == 0 && (ldv & 3) == 0 && ((uintptr_t)v & 15) == 0 && (ld_plane & 15) == 0 && ((uintptr_t)plane & 15) == 0 && T1 >= 64) {
         hipLaunchKernelGGL(pack_vt64_kernel, dim3((T1 + 63) / 64, c / 64, B), dim3(256), 0, ST, v, (long)ldv, (char*)plane, (long)ld_plane, T1, T1p, c, (T1 + 31) / 32);
         return efts_check_launch("efts_pack_vt");
     }
-    hipLaunchKernelGGL(pack_vt_kernel, dim3((T1 + 31) / 32, (c + 31) / 32, B), dim3(256), 0, ST, v, (long)ldv, (char*)plane, (long)ld_plane, T1, T1p, c);
+    hipLaunchKernelGGL(pack_vt_kernel, dim3((T1 + 31) / 32, (c + 31) / 32, B), dim3(256), 0, ST, v, (long)ldv, (char*)plane, (long)ld_plane, T1, T1p, c, split);
     return efts_check_launch("efts_pack_vt");
 }
 
@@ -761,6 +772,7 @@ extern "C" int efts_layernorm_rows(const float* x, const float* gamma, const flo
                                    uint32_t drop_seed, const uint32_t* drop_seed_add, void* stream) {
     if (!x || !gamma || !beta || (!f32_out && !plane)) return efts_fail(EFTS_EINVAL, "efts_layernorm_rows: null pointer");
     if (c % 256 || c > 2048 || rows <= 0) return efts_fail(EFTS_ESHAPE, "efts_layernorm_rows: c must be a multiple of 256, <= 2048");
+    if (plane && !(split >= EFTS_SPLIT_BF16 && split <= EFTS_SPLIT_FP32)) return efts_fail(EFTS_EINVAL, "efts_layernorm_rows: split must be 1, 2 or 3");
     hipLaunchKernelGGL((layernorm_kernel<false>), dim3((rows + 3) / 4), dim3(256), 0, ST, x, gamma, beta, eps, rowmask, f32_out, (char*)plane,
                        (long)ld_plane, rows, c, split, (const float*)nullptr, (const float*)nullptr, 0, 0.f, (float*)nullptr, drop_p, drop_seed, drop_seed_add);
     return efts_check_launch("efts_layernorm_rows");

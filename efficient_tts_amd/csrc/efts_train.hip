@@ -750,7 +750,8 @@ extern "C" int efts_pack_weights_grouped(const efts_pack_item* items, int32_t n_
                                          int32_t cout, int32_t cin, int32_t taps, int32_t split, int32_t with_t, void* stream) {
     static_assert(sizeof(PackItem) == sizeof(efts_pack_item), "efts_pack_item layout");
     if (!items || n_items <= 0) return efts_fail(EFTS_EINVAL, "efts_pack_weights_grouped: no items");
-    if (!(split == 1 || split == 2) || cout <= 0 || cin <= 0 || taps <= 0) return efts_fail(EFTS_ESHAPE, "efts_pack_weights_grouped: bad shape/split");
+    if (!(split >= EFTS_SPLIT_BF16 && split <= EFTS_SPLIT_FP32) || cout <= 0 || cin <= 0 || taps <= 0) return efts_fail(EFTS_ESHAPE, "efts_pack_weights_grouped: bad shape/split");
+    if (with_t && split == EFTS_SPLIT_FP32) return efts_fail(EFTS_EINVAL, "efts_pack_weights_grouped: the dgrad plane (with_t) has no split 3 form (training is bf16 / bf16x3)");
     const int kp = split == 1 ? (cin + 63) & ~63 : (cin + 31) & ~31;
     const int kpt = split == 1 ? (cout + 63) & ~63 : (cout + 31) & ~31;
     if (ldb < (split == 1 ? kp * 2 : kp * 4) || (ldb & 15)) return efts_fail(EFTS_EALIGN, "efts_pack_weights_grouped: ldb too small or not 16-byte aligned");
@@ -770,6 +771,7 @@ extern "C" int efts_pack_weights_grouped(const efts_pack_item* items, int32_t n_
 
 extern "C" int efts_pack_weight_t(const float* w, void* plane, int64_t ldb, int32_t cout, int32_t cin, int32_t taps, int32_t split, void* stream) {
     if (!w || !plane) return efts_fail(EFTS_EINVAL, "efts_pack_weight_t: null pointer");
+    if (!(split == EFTS_SPLIT_BF16 || split == EFTS_SPLIT_BF16X3)) return efts_fail(EFTS_EINVAL, "efts_pack_weight_t: split must be 1 or 2 (training has no fp32 form)");
     const int kp = split == 1 ? (cout + 63) & ~63 : (cout + 31) & ~31;
     if (ldb < (split == 1 ? kp * 2 : kp * 4) || (ldb & 15)) return efts_fail(EFTS_EALIGN, "efts_pack_weight_t: ldb too small or not 16-byte aligned");
     hipLaunchKernelGGL(pack_weight_t_kernel, dim3(cin), dim3(256), 0, ST, w, (char*)plane, (long)ldb, cout, cin, taps, kp, split);
@@ -781,6 +783,7 @@ extern "C" int efts_loss_bwd(const float* mel_pred, int64_t ldm, const float* sp
                              int64_t ld_plane, int32_t split, float* ddur, int32_t B, int32_t T1, int32_t T1p, int32_t T2, int32_t T2p,
                              int32_t odim, void* stream) {
     if (!mel_pred || !speech || !mel_len || !dur_pred || !log_delta_e || !text_len || !ddur) return efts_fail(EFTS_EINVAL, "efts_loss_bwd: null pointer");
+    if (dmel_plane && !(split == EFTS_SPLIT_BF16 || split == EFTS_SPLIT_BF16X3)) return efts_fail(EFTS_EINVAL, "efts_loss_bwd: split must be 1 or 2 (training has no fp32 form)");
     const int kp = split == 1 ? (odim + 63) & ~63 : (odim + 31) & ~31;
     const int th = ((kp / 4) + 63) & ~63;
     const int nb2 = (B * T1p + th - 1) / th;
@@ -819,6 +822,7 @@ extern "C" int efts_act_bwd(const float* g, const float* y, const float* x, cons
 extern "C" int efts_pack_t(const float* x, int64_t ldx, void* plane, int64_t ld_plane, int64_t plane_stride, int32_t split, int32_t rows,
                            int32_t c, int32_t shift0, int32_t nshift, int32_t kpad, void* stream) {
     if (!x || !plane) return efts_fail(EFTS_EINVAL, "efts_pack_t: null pointer");
+    if (!(split == EFTS_SPLIT_BF16 || split == EFTS_SPLIT_BF16X3)) return efts_fail(EFTS_EINVAL, "efts_pack_t: split must be 1 or 2 (training has no fp32 form)");
     if (kpad % 64 || ld_plane < (split == 1 ? kpad * 2 : kpad * 4)) return efts_fail(EFTS_ESHAPE, "efts_pack_t: kpad must be a multiple of 64 and fit ld_plane");
     if (nshift < 1 || nshift > 11) return efts_fail(EFTS_ESHAPE, "efts_pack_t: nshift must be in 1..11");
     hipLaunchKernelGGL(pack_t_kernel, dim3(kpad / 64, (c + 31) / 32), dim3(256), 0, ST, x, (long)ldx, (char*)plane, (long)ld_plane, (long)plane_stride,
@@ -942,6 +946,7 @@ extern "C" int efts_layernorm_bwd(const float* x, const float* gamma, const floa
                                   uint32_t drop_seed, const uint32_t* drop_seed_add, void* stream) {
     if (!x || !gamma || !beta || (!dy && !ddur) || (ddur && !w) || !dgamma || !dbeta) return efts_fail(EFTS_EINVAL, "efts_layernorm_bwd: null pointer");
     if (c % 256 || c > 2048) return efts_fail(EFTS_ESHAPE, "efts_layernorm_bwd: c must be a multiple of 256, <= 2048");
+    if (plane && !(split == EFTS_SPLIT_BF16 || split == EFTS_SPLIT_BF16X3)) return efts_fail(EFTS_EINVAL, "efts_layernorm_bwd: split must be 1 or 2 (training has no fp32 form)");
     int rpb = LNB_ROWS;                        // rows per block
     if (c > 768) (void)hipFuncSetAttribute((const void*)layernorm_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * c * (int)sizeof(float));
     hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((rows + rpb - 1) / rpb), dim3(256), (size_t)16 * c * sizeof(float), ST, x, gamma, beta, eps, dy, ddur, w,

@@ -37,7 +37,7 @@ extern "C" int efts_mean_act_rows(const float* a, const float* b, const float* c
                                   int64_t ldo, void* plane, int64_t ld_plane, int32_t split, int32_t rows, int32_t c, void* stream) {
     if (!a || (!out && !plane)) return efts_fail(EFTS_EINVAL, "efts_mean_act_rows: null pointer");
     if (rows <= 0 || c <= 0 || (c & 3) || (ld & 3) || (out && (ldo & 3))) return efts_fail(EFTS_ESHAPE, "efts_mean_act_rows: c, ld, ldo must be multiples of 4");
-    if (plane && !(split == 1 || split == 2)) return efts_fail(EFTS_EINVAL, "efts_mean_act_rows: split must be 1 or 2");
+    if (plane && !(split >= EFTS_SPLIT_BF16 && split <= EFTS_SPLIT_FP32)) return efts_fail(EFTS_EINVAL, "efts_mean_act_rows: split must be 1, 2 or 3");
     const long items = (long)rows * (c >> 2);
     const int blocks = (int)((items + 255) / 256 < 4096 ? (items + 255) / 256 : 4096);
     hipLaunchKernelGGL(mean_act_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, b, c3, (long)ld, scale, slope, out, (long)ldo,

@@ -12,12 +12,13 @@ from typing import Optional
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EFTS_LIB", os.path.join(HERE, "libefts_hip.so"))   # EFTS_LIB: kernel experiments only
 
-ABI_VERSION = 601         # EFTS_ABI_VERSION of the include/efts_abi.h this binding mirrors; load() refuses any other library
+ABI_VERSION = 602         # EFTS_ABI_VERSION of the include/efts_abi.h this binding mirrors; load() refuses any other library
 RC_PLAN_INTS = 42
 GAP = 2
 GUARD_LO = 8
 GUARD_HI = 144
 TILE_M = 128
+SPLIT_BF16, SPLIT_BF16X3, SPLIT_FP32 = 1, 2, 3     # EFTS_SPLIT_*: operand-plane formats (include/efts_abi.h "MFMA operand planes")
 ACT_NONE, ACT_LEAKY, ACT_RELU, ACT_TANH = 0, 1, 2, 3
 ACT_BWD_BIAS_PARTS = 16
 # EFTS_ACTFN_* (include/efts_abi.h): torch.nn module name -> (id, names of the module's scalar parameters in p0 / p1 order with torch's defaults)
@@ -125,8 +126,8 @@ _SIGS = {
     "efts_imv_scan": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "efts_aligned_positions": (i32, [vp, vp, vp, f32, f32, vp, vp, i32, i32, i32, vp]),
     "efts_duration_target": (i32, [vp, vp, vp, f32, i32, vp, i32, i32, vp]),
-    "efts_reconst_alpha": (i32, [vp, vp, vp, f32, vp, vp, i64, i32, i32, i32, i32, vp]),
-    "efts_pack_vt": (i32, [vp, i64, vp, i64, i32, i32, i32, i32, vp]),
+    "efts_reconst_alpha": (i32, [vp, vp, vp, f32, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
+    "efts_pack_vt": (i32, [vp, i64, vp, i64, i32, i32, i32, i32, i32, vp]),
     "efts_cumsum_rows": (i32, [vp, vp, i32, i32, vp]),
     "efts_imv_align": (i32, [vp, vp, vp, f32, f32, i32, vp, vp, vp, i32, i32, i32, vp]),
     "efts_expand": (i32, [C.POINTER(ExpandArgs), vp]),

@@ -141,7 +141,19 @@ class _Workspace:
         return self.bufs[key]
 
 
-PRECISIONS = {"bf16": 1, "bf16x3": 2}
+PRECISIONS = {"bf16": 1, "bf16x3": 2, "fp32": 3}
+TRAINABLE_PRECISIONS = ("bf16", "bf16x3")      # fp32 (operand format 3) is an eval-path mode: no backward, wgrad or optimiser form
+# launch options whose fused kernels have no fp32 form: an fp32 model runs their generic fallback (efts_gemm on format-3 planes)
+FP32_GENERIC_OPTIONS = ("resconv", "fuse_prenet", "fuse_expand", "embed_conv", "small_m")
+
+
+def require_trainable(model, what: str) -> None:
+    """NotImplementedError unless `model` (or the module a wrapper holds) runs in a precision the training path implements"""
+    m = getattr(model, "module", model)
+    prec = getattr(m, "precision", None)
+    if prec is not None and prec not in TRAINABLE_PRECISIONS:
+        raise NotImplementedError(f"{what}: training is implemented for precision {' / '.join(map(repr, TRAINABLE_PRECISIONS))}, "
+                                  f"not {prec!r} (an inference / validation mode)")
 
 
 @dataclasses.dataclass
@@ -172,8 +184,11 @@ class EfficientTTSCNN(torch.nn.Module):
     """EFTS-CNN acoustic model (drop-in for nntts.models.EfficientTTSCNN).
 
     Extra keyword (not in the reference): ``precision`` selects the MFMA operand mode of the
-    Conv1d/Linear stacks: "bf16x3" (split-bf16, fp32-class accuracy; default) or "bf16".
-    The alignment block (QK^T, expand) always runs in bf16x3 / fp32.
+    Conv1d/Linear stacks: "bf16x3" (split-bf16, fp32-class accuracy; default), "bf16", or "fp32"
+    (exact fp32 operands on the fp32-input MFMA, efts_gemm on format-3 planes: the reference-parity
+    mode, eval paths only -- training refuses it).  The alignment block (QK^T, expand) runs in bf16x3
+    in the bf16 / bf16x3 modes and in fp32 in the fp32 mode.  An fp32 model runs the generic fallback
+    of every fused launch that has no fp32 form (FP32_GENERIC_OPTIONS are off, and setting one raises).
     """
 
     def __init__(self, num_symbols: int, odim: int = 80, symbol_embedding_dim: int = 512, n_channels: int = 512,
@@ -209,6 +224,7 @@ class EfficientTTSCNN(torch.nn.Module):
             raise NotImplementedError("n_channels must be a multiple of 256 and odim <= 128")
         self.precision = precision
         self.split = PRECISIONS[precision]
+        self.align_split = L.SPLIT_FP32 if self.split == L.SPLIT_FP32 else L.SPLIT_BF16X3   # operand format of q, k, alpha'^T, V^T
         self.odim, self.n_channels, self.num_symbols = odim, n_channels, num_symbols
         self.duration_offset, self.sigma, self.sigma_e = duration_offset, sigma, sigma_e
         self.delta_e_method_1 = delta_e_method_1
@@ -236,6 +252,9 @@ class EfficientTTSCNN(torch.nn.Module):
         self.mel_output_layer = torch.nn.Linear(n_channels, odim)
         self.duration_predictor = _DurationPredictor(n_channels, n_duration_layer, n_channels, offset=duration_offset)
         self.opt = LaunchOptions()          # launch-affecting options (A/B and test hooks): also plain attributes of the model, see below
+        if self.split == L.SPLIT_FP32:
+            for name in FP32_GENERIC_OPTIONS:
+                setattr(self.opt, name, False)
         self._free_running = False          # set while inference() / inference_batch() enqueue their launches
         self.graphs = True                  # plain eval calls replay a per-shape hipGraph (False: every kernel launched eagerly)
         self._graph_cache = GraphCache()
@@ -600,7 +619,7 @@ class EfficientTTSCNN(torch.nn.Module):
     def _key_proj(self, ws, pk, rs1: Rows, h_p: Plane, gap1, len1) -> Plane:
         """text_encoder_key, zero at padded text (efficient_tts.py:149, :155-156): split-2 operand plane of q.k^T"""
         C = self.n_channels
-        key_p = ws.plane("key_p", rs1, C, 2)
+        key_p = ws.plane("key_p", rs1, C, self.align_split)
         wk = pk["key"]
         O.gemm(a=h_p, b_ptr=wk.ptr, ldb=wk.ld, m=rs1.rows, n=C, bias=self.text_encoder_key.bias,
                rowmask_ptr=(gap1 if len1 is None else len1).data_ptr(), out_plane=key_p, tiling=self._til(rs1.rows))
@@ -665,10 +684,10 @@ class EfficientTTSCNN(torch.nn.Module):
             # alpha' is the MFMA A operand, produced in registers; V is read as fp32: no alpha'^T plane, no V^T planes
             O.expand(e=e, tl=tl, ml=ml, sigma=float(self.sigma), v=val_f, rs1=rs1, rs2=rs2, alpha_out=ralpha, y_f32=h_f, y=h_p, y_lo=h_l)
         else:
-            ra_plane = ws.plane("ra_p", rs2, T1, 2)
+            ra_plane = ws.plane("ra_p", rs2, T1, self.align_split)
             O.reconst_alpha(e, tl, ml, float(self.sigma), ralpha, ra_plane, B, T1, rs2.T, rs2.Tp)
             if vt is None:
-                vt = ws.raw_plane("vt", B * C, T1, 2)
+                vt = ws.raw_plane("vt", B * C, T1, self.align_split)
                 O.pack_vt(val_f, vt, B, T1, rs1.Tp, C)
             O.gemm(a=ra_plane, b_ptr=vt.ptr, ldb=vt.ld, m=rs2.T, n=C, batch=B, a_batch_stride=rs2.Tp * ra_plane.ld,
                    b_batch_stride=C * vt.ld, rowmask_ptr=len2_ptr, rowmask_batch_stride=rs2.Tp,
@@ -708,6 +727,7 @@ class EfficientTTSCNN(torch.nn.Module):
         training_path = torch.is_grad_enabled() and (self.text_embedding_table.weight.requires_grad or any(p.requires_grad for p in self.parameters()))
         self._require(text)
         if training_path:
+            require_trainable(self, "EfficientTTSCNN.forward with gradients")
             from .autograd import training_forward
             return training_forward(self, text, text_lengths, speech, speech_lengths)
         if self.training:
@@ -783,7 +803,7 @@ class EfficientTTSCNN(torch.nn.Module):
         if not masks_done:
             O.row_masks(ml, rs2, gap2, len2)                                      # :139 (in FRONT of the fork: the prenet on the side stream reads gap2)
         side.wait_stream(main)
-        vt = None if self._fused_expand(T1) else ws.raw_plane("vt", B * C, T1, 2)
+        vt = None if self._fused_expand(T1) else ws.raw_plane("vt", B * C, T1, self.align_split)
         nt, nm = len(self.text_encoder.layers), len(self.mel_encoder.layers)
         merged = self._on_resconv(rs2) and nt >= 1 and nm >= 1
         v_ready = torch.cuda.Event()
@@ -812,10 +832,10 @@ class EfficientTTSCNN(torch.nn.Module):
 
         def mel_stack(pre_f, pre_p, pre_l, rider=None):                            # :162-164
             if self.mel_query_fc is None:
-                _, q_p = self._res_stack(ws, "me", "mel_encoder", pk, rs2, pre_f, pre_p, gap2.data_ptr(), 2, False, x_lo=pre_l, rider=rider)
+                _, q_p = self._res_stack(ws, "me", "mel_encoder", pk, rs2, pre_f, pre_p, gap2.data_ptr(), self.align_split, False, x_lo=pre_l, rider=rider)
                 return q_p
             _, mh_p = self._res_stack(ws, "me", "mel_encoder", pk, rs2, pre_f, pre_p, gap2.data_ptr(), self.split, False, x_lo=pre_l, rider=rider)
-            q_p = ws.plane("q_p", rs2, C, 2)
+            q_p = ws.plane("q_p", rs2, C, self.align_split)
             wq = pk["qfc"]
             O.gemm(a=mh_p, b_ptr=wq.ptr, ldb=wq.ld, m=rs2.rows, n=C, bias=self.mel_query_fc.bias, rowmask_ptr=gap2.data_ptr(), out_plane=q_p)
             return q_p
@@ -1107,7 +1127,12 @@ class EfficientTTSCNN(torch.nn.Module):
 
 
 def _opt_property(name: str):
-    return property(lambda self: getattr(self.opt, name), lambda self, v: setattr(self.opt, name, type(getattr(LaunchOptions(), name))(v)))
+    def set_opt(self, v):
+        v = type(getattr(LaunchOptions(), name))(v)
+        if v and name in FP32_GENERIC_OPTIONS and self.split == L.SPLIT_FP32:
+            raise ValueError(f"{name}=True: its fused kernel has no fp32 (operand format 3) form; a precision='fp32' model runs the generic path")
+        setattr(self.opt, name, v)
+    return property(lambda self: getattr(self.opt, name), set_opt)
 
 
 for _f in dataclasses.fields(LaunchOptions):

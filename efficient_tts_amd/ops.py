@@ -106,7 +106,7 @@ class F32Rows:
 
 
 class Plane:
-    """bf16 MFMA operand plane [rows, nchunk*128 B] (split 1: bf16; split 2: hi/lo interleaved)."""
+    """MFMA operand plane [rows, nchunk*128 B] (split 1: bf16; split 2: bf16 hi/lo interleaved; split 3: fp32)."""
 
     def __init__(self, nrows_alloc: int, k: int, split: int, device, guard_lo: int = 0):
         self.split, self.k = split, k
@@ -399,7 +399,7 @@ def duration_target(e, tl, ml, offset, method1: bool, lde, B, T1) -> None:
 def reconst_alpha(e, tl, ml, sigma, alpha_out, plane: Optional[Plane], B, T1, T2, T2p) -> None:
     L.check(L.load().efts_reconst_alpha(e.data_ptr(), _p(tl), _p(ml), sigma, _p(alpha_out),
                                         None if plane is None else plane.ptr, 0 if plane is None else plane.ld,
-                                        B, T1, T2, T2p, _stream()), "efts_reconst_alpha")
+                                        B, T1, T2, T2p, L.SPLIT_BF16X3 if plane is None else plane.split, _stream()), "efts_reconst_alpha")
 
 
 def imv_align_fits(T1: int, T2: int) -> bool:
@@ -431,7 +431,7 @@ def expand(*, e, tl, ml, sigma: float, v: F32Rows, rs1: Rows, rs2: Rows, alpha_o
 
 
 def pack_vt(v: F32Rows, plane: Plane, B, T1, T1p, c) -> None:
-    L.check(L.load().efts_pack_vt(v.ptr, v.c, plane.ptr, plane.ld, B, T1, T1p, c, _stream()), "efts_pack_vt")
+    L.check(L.load().efts_pack_vt(v.ptr, v.c, plane.ptr, plane.ld, B, T1, T1p, c, plane.split, _stream()), "efts_pack_vt")
 
 
 def cumsum_rows(x, y, B, T) -> None:

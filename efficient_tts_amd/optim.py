@@ -17,10 +17,12 @@ from torch.optim.lr_scheduler import _LRScheduler
 from . import lib as L
 from . import ops as O
 from .autograd import engine_of
+from .model import require_trainable
 
 
 class EftsAdam(torch.optim.Optimizer):
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.99), eps=1e-9, weight_decay=1e-5, amsgrad=True, grad_norm=1.0):
+        require_trainable(model, "EftsAdam")
         if not amsgrad:
             raise NotImplementedError("the fused kernel implements amsgrad=True (the reference YAML)")
         self.model = model

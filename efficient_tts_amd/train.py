@@ -16,6 +16,7 @@ import torch
 from . import lib as L
 from . import ops as O
 from .ops import F32Rows, PackedWeight, Plane, Rows
+from .model import require_trainable
 
 _lib = L.load
 
@@ -104,6 +105,7 @@ def grad_layout(model) -> List[Tuple[str, torch.nn.Parameter]]:
 
 class TrainEngine:
     def __init__(self, model):
+        require_trainable(model, "TrainEngine")
         self.m = model
         self.layout = grad_layout(model)
         self.named = list(model.named_parameters())     # model.parameters() order (what autograd's Function receives)
@@ -718,7 +720,7 @@ class TrainEngine:
         O.gemm(a=dS_p, b_ptr=kt.ptr, ldb=kt.ld, m=T2, n=C, batch=B, a_batch_stride=rs2.Tp * dS_p.ld, b_batch_stride=C * kt.ld, alpha=scale,
                out_f32_ptr=GQ.ptr, ldo=C, out_batch_stride=rs2.Tp * C)
         dSt = ws.raw_plane("BdSt", B * T1 + 264, T2, 2)             # dS^T: rows (b,i), K = j
-        L.check(_lib().efts_pack_vt(dS.data_ptr(), T1, dSt.ptr, dSt.ld, B, T2, T2, T1, O._stream()), "efts_pack_vt")
+        L.check(_lib().efts_pack_vt(dS.data_ptr(), T1, dSt.ptr, dSt.ld, B, T2, T2, T1, dSt.split, O._stream()), "efts_pack_vt")
         GK = ws.f32("BGK", rs1, C)
         GK_p = ws.plane("BGK_p", rs1, C, split)
         shared = m.share_text_encoder_key_value                     # value = key projection: its gradient joins dK here (residual)

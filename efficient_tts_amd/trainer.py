@@ -29,6 +29,8 @@ from typing import Dict
 
 import torch
 
+from .model import require_trainable
+
 try:
     from tensorboardX import SummaryWriter as _TBWriter
 except Exception:                                       # pragma: no cover - optional dependency
@@ -63,6 +65,7 @@ class _Meter:
 class EfficientTTSTrainer:
     def __init__(self, steps, epochs, data_loader, sampler, model, optimizer, scheduler, config,
                  device=torch.device("cpu")):
+        require_trainable(model, "EfficientTTSTrainer")
         self.steps = int(steps)
         self.epochs = int(epochs)
         self.data_loader = data_loader

@@ -77,9 +77,10 @@ class HiFiGANGenerator(nn.Module):
         super().__init__()
         if str(_cfg(h, "resblock", "1")) != "1":
             raise NotImplementedError("only ResBlock1 (the HiFiGAN_LJ_V1 configuration) is implemented")
-        if precision not in ("bf16x3", "bf16"):
-            raise ValueError("precision must be 'bf16x3' or 'bf16'")
-        self.precision, self.split = precision, 2 if precision == "bf16x3" else 1
+        splits = {"bf16": L.SPLIT_BF16, "bf16x3": L.SPLIT_BF16X3, "fp32": L.SPLIT_FP32}     # fp32: exact operands, generic efts_gemm tiling
+        if precision not in splits:
+            raise ValueError("precision must be 'bf16x3', 'bf16' or 'fp32'")
+        self.precision, self.split = precision, splits[precision]
         self.upsample_rates = tuple(_cfg(h, "upsample_rates"))
         self.upsample_kernel_sizes = tuple(_cfg(h, "upsample_kernel_sizes"))
         self.res_kernels = tuple(_cfg(h, "resblock_kernel_sizes"))

@@ -23,11 +23,18 @@
  * Buffers carry EFTS_GUARD_LO zero rows before row 0 and EFTS_GUARD_HI rows after the
  * last 128-row tile; pointers passed in point at row 0.
  *
- * MFMA operand planes.  Matrices consumed by the MFMA GEMM are bf16, row-major, K in
- * 128-byte chunks:
+ * MFMA operand planes.  Matrices consumed by the MFMA GEMM are row-major, K in 128-byte
+ * chunks; the format is named by a `split` value (EFTS_SPLIT_*):
  *   split 1 ("bf16")   : row = [Kp] bf16,            Kp = roundup(K, 64); chunk = 64 k's
  *   split 2 ("bf16x3") : row = [Kp/32][hi32 | lo32], Kp = roundup(K, 32); chunk = 32 k's,
  *                        x = hi + lo (two bf16), product = hi*hi + hi*lo + lo*hi in fp32.
+ *   split 3 ("fp32")   : row = [Kp] fp32,            Kp = roundup(K, 32); chunk = 32 k's,
+ *                        the exact value; efts_gemm contracts it on v_mfma_f32_32x32x2_f32
+ *                        (a k-ordered fmaf chain, no operand rounding).  Same chunk geometry as
+ *                        split 2, so nchunk, row strides and guard rows are unchanged.  Produced
+ *                        and consumed by the eval-path entry points; the fused kernels
+ *                        (efts_resconv5, efts_frame_linear, efts_expand, efts_embed_conv) and
+ *                        the training entry points have no fp32 form and refuse it (EFTS_EINVAL).
  */
 #ifndef EFTS_ABI_H
 #define EFTS_ABI_H
@@ -51,6 +58,10 @@ extern "C" {
 #define EFTS_ELAUNCH (-4)
 #define EFTS_EDEVICE (-5)
 
+#define EFTS_SPLIT_BF16 1
+#define EFTS_SPLIT_BF16X3 2
+#define EFTS_SPLIT_FP32 3
+
 #define EFTS_ACT_NONE 0
 #define EFTS_ACT_LEAKY 1 /* LeakyReLU, slope in args */
 #define EFTS_ACT_RELU 2
@@ -63,9 +74,10 @@ extern "C" {
  *   500  round 5: efts_resconv5_args grew by act_bwd_sign / act_bwd_bias_part / act_bwd_bias_rows / act_bwd_slope / kernel;
  *        efts_wgrad_tn, efts_wgrad_reduce_bias, efts_resconv5_kernel removed (efts_wgrad_tn_grouped / efts_wgrad_reduce_grouped instead)
  *   600  round 6: + efts_frame_pack_dit, efts_logmel_dit; efts_pack_item.plane may be NULL (dgrad plane only)
- *   601  round 6 (this header): efts_gemm_args grew by sqerr_target / ld_target / target_batch_stride / sqerr_part;
- *        + efts_losses_from_parts, efts_logmel_fft, efts_logmel_fft_pcm16 */
-#define EFTS_ABI_VERSION 601
+ *   601  round 6: efts_gemm_args grew by sqerr_target / ld_target / target_batch_stride / sqerr_part;
+ *        + efts_losses_from_parts, efts_logmel_fft, efts_logmel_fft_pcm16
+ *   602  (this header): operand format 3 (EFTS_SPLIT_FP32); efts_reconst_alpha and efts_pack_vt take the format of their plane */
+#define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
 /* 0 when the current HIP device is gfx950. */
@@ -88,7 +100,7 @@ typedef struct efts_gemm_args {
     int64_t ldb;
     int64_t b_tap_stride;
     int64_t b_batch_stride;
-    int32_t split;  /* 1 = bf16, 2 = bf16x3 (hi/lo interleaved) */
+    int32_t split;  /* 1 = bf16, 2 = bf16x3 (hi/lo interleaved), 3 = fp32 (generic tiling only) */
     int32_t taps;   /* 1, 3, 5, 7, 9 or 11 */
     int32_t m;      /* rows per batch item */
     int32_t n;      /* output columns */
@@ -109,7 +121,7 @@ typedef struct efts_gemm_args {
     void* out_bf16;    /* operand plane for the next contraction, or NULL */
     int64_t ldob;      /* bytes */
     int64_t outb_batch_stride;
-    int32_t out_split; /* 1 or 2: format of out_bf16 */
+    int32_t out_split; /* 1, 2 or 3: format of out_bf16 */
     int32_t batch2;    /* optional outer batch (grid.z), 0/1 = none; e.g. the taps of a wgrad */
     int64_t a_batch2_stride, b_batch2_stride, out_batch2_stride; /* bytes, bytes, elements */
     /* dilated convolutions (HiFi-GAN residual blocks, nntts/vocoders/hifigan_model.py:30-58): rows between taps,
@@ -334,8 +346,8 @@ int efts_embed_conv(const int64_t* ids, const int32_t* lengths, const float* tab
  * efts_reconst_alpha: alpha'[b][i][j] = softmax_i(-sigma (q_j - e_i)^2), zero outside the
  *   text x mel mask (reconstruct_align_from_aligned_position :347-375 + :186).  Lengths NULL
  *   = inference (no masks, :270-274).  Writes the fp32 API tensor [B][T1][T2] (optional) and
- *   the split-2 A operand plane of alpha'^T: row (b*T2p + j), K = i  (for the expand bmm :190).
- * efts_pack_vt: V fp32 [B*T1p][c] -> per-item split-2 B operand plane V^T [B][c][K = i].
+ *   the A operand plane of alpha'^T, format `split` (2 or 3): row (b*T2p + j), K = i  (for the expand bmm :190).
+ * efts_pack_vt: V fp32 [B*T1p][c] -> per-item B operand plane V^T [B][c][K = i], format `split` (2 or 3).
  * efts_cumsum_rows: e = cumsum(delta) over T1 (inference :260); x [B][T] contiguous.
  * ---------------------------------------------------------------------------------- */
 int efts_attn_soft_index(const float* scores, int64_t ld, const int32_t* text_len, const int32_t* mel_len,
@@ -351,9 +363,9 @@ int efts_duration_target(const float* e, const int32_t* text_len, const int32_t*
                          float* log_delta_e, int32_t B, int32_t T1, void* stream);
 int efts_reconst_alpha(const float* e, const int32_t* text_len, const int32_t* mel_len, float sigma,
                        float* alpha_out, void* plane, int64_t ld_plane, int32_t B, int32_t T1, int32_t T2,
-                       int32_t T2p, void* stream);
+                       int32_t T2p, int32_t split, void* stream);
 int efts_pack_vt(const float* v, int64_t ldv, void* plane, int64_t ld_plane, int32_t B, int32_t T1,
-                 int32_t T1p, int32_t c, void* stream);
+                 int32_t T1p, int32_t c, int32_t split, void* stream);
 int efts_cumsum_rows(const float* x, float* y, int32_t B, int32_t T, void* stream);
 
 /* The middle of the alignment block in ONE launch (one workgroup per item, operands in LDS after the first load):
