@@ -12,7 +12,9 @@ HiFi-GAN V1 generator (efficient_tts_amd.vocoder).  Differences from the referen
     (useful for smoke tests and timing only), `--no_vocoder` writes the mel-spectrograms as .npy instead;
   * `--batch_size N` synthesises N utterances per call with `inference_batch` (each item equals its B = 1 result);
   * every line of the list is processed (the reference stops after 10), alignment plots are not drawn;
-  * RTF is reported as the reference does (wall time of model + vocoder over audio duration), synchronised per call.
+  * RTF is reported as the reference does (wall time of model + vocoder over audio duration), synchronised per call;
+  * `--length_scale S` multiplies every predicted duration (> 1: slower speech), `--write_durations` writes the frames per
+    phoneme next to each output (<id>_<step>.durations.txt: index, phoneme, start frame, frames, start time in seconds).
 """
 from __future__ import annotations
 
@@ -47,6 +49,9 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--batch_size", type=int, default=1, help="utterances per acoustic-model call (default 1, as the reference)")
     p.add_argument("--precision", type=str, default="bf16x3", choices=["bf16x3", "bf16", "fp32"],
                    help="MFMA operand mode of the acoustic model and the vocoder (fp32: exact fp32 operands, the reference-parity mode)")
+    p.add_argument("--length_scale", type=float, default=1.0, help="multiplies every predicted duration (default 1.0; > 1: slower speech)")
+    p.add_argument("--write_durations", action="store_true",
+                   help="also write <id>_<step>.durations.txt: token index, phoneme, start frame, frame count, start time in seconds")
     p.add_argument("--verbose", type=int, default=1)
     return p
 
@@ -70,6 +75,14 @@ def _write_wav(path: str, samples: torch.Tensor) -> None:
     write(path, SAMPLING_RATE, pcm)
 
 
+def _write_durations(path: str, phonemes: List[str], frames, hop: int, sampling_rate: int) -> None:
+    start = 0
+    with open(path, "w") as handle:
+        for i, (p, n) in enumerate(zip(phonemes, frames)):
+            handle.write(f"{i}\t{p}\t{start}\t{int(n)}\t{start * hop / sampling_rate:.6f}\n")
+            start += int(n)
+
+
 def run_tts(args) -> float:
     level = {0: logging.WARNING, 1: logging.INFO}.get(args.verbose, logging.DEBUG)
     logging.basicConfig(level=level, stream=sys.stdout, force=True, format="%(asctime)s %(levelname)s %(name)s:%(lineno)d  %(message)s")
@@ -85,6 +98,12 @@ def run_tts(args) -> float:
         raise NotImplementedError("only phoneme-sequence recipes (dataset_params.use_phnseq: true) are supported")
     with open(data_params["phnset_path"]) as handle:
         phn2idx = {p.strip(): i for i, p in enumerate(handle)}
+    idx2phn = {i: p for p, i in phn2idx.items()}
+    hop = int(config.get("hop_size", 256))
+    sampling_rate = int(config.get("sampling_rate", SAMPLING_RATE))
+    if not args.length_scale > 0:
+        raise ValueError("--length_scale must be > 0")
+    ctl = dict(length_scale=args.length_scale, return_durations=args.write_durations)
     items = _read_list(args.test_fid_scp, phn2idx)
     logging.info(f"{len(items)} utterances to synthesise")
     step = os.path.basename(args.checkpoint).split("-")[-1][:-4]
@@ -113,15 +132,18 @@ def run_tts(args) -> float:
         start = time.perf_counter()
         with torch.no_grad():
             if len(chunk) == 1:
-                mel, _ = model.inference(chunk[0][1][None].to(device))
-                mels = [mel[0]]
+                out = model.inference(chunk[0][1][None].to(device), **ctl)
+                mels = [out[0][0]]
+                frames = [out[2][0]] if args.write_durations else None
             else:
                 lens = torch.tensor([len(t) for _, t in chunk])
                 ids = torch.zeros(len(chunk), int(lens.max()), dtype=torch.long)
                 for n, (_, t) in enumerate(chunk):
                     ids[n, :len(t)] = t
-                mel, mel_lens, _ = model.inference_batch(ids.to(device), lens.to(device))
+                out = model.inference_batch(ids.to(device), lens.to(device), **ctl)
+                mel, mel_lens = out[0], out[1]
                 mels = [mel[n, :int(mel_lens[n])] for n in range(len(chunk))]
+                frames = [out[3][n, :int(lens[n])] for n in range(len(chunk))] if args.write_durations else None
             if vocoder is None:
                 outs = mels
             elif len(chunk) == 1:
@@ -139,6 +161,10 @@ def run_tts(args) -> float:
                 np.save(os.path.join(args.outdir, f"{utt}_{step}.npy"), out.cpu().numpy())
             else:
                 _write_wav(os.path.join(args.outdir, f"{utt}_{step}.wav"), out)
+        if frames is not None:
+            for (utt, ids1), fr in zip(chunk, frames):
+                _write_durations(os.path.join(args.outdir, f"{utt}_{step}.durations.txt"), [idx2phn[int(i)] for i in ids1],
+                                 fr.cpu().tolist(), hop, sampling_rate)
         logging.debug(f"{[u for u, _ in chunk]}: {elapsed * 1e3:.2f} ms for {seconds:.2f} s of audio")
     rtf = total_rtf / max(done, 1)
     logging.info(f"Finished generation of {done} utterances (RTF = {rtf:.05f}).")

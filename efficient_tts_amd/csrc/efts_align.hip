@@ -351,6 +351,109 @@ extern "C" int efts_duration_positions(const float* dur, int64_t ld, const int32
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// efts_duration_control: efts_duration_positions with the controls of free-running synthesis in the same launch -- a per-item
+// length scale, per-token frame counts that replace the prediction, a per-item target length -- and the integer frames per token.
+// Same scan (same chunks, same summation order): with every control off, e and mel_len are those of efts_duration_positions
+// bit for bit.  Passes: (1) chunk sums + block scan, (2) running sums -> e, E_{len-1}, (3) only with a target or a frames output:
+// the chunk's running sums once more (the same float operations, so the same values), rescaled to the target, rounded.  Pass 3
+// starts each chunk from the running sum the PREVIOUS thread ended pass 2 with (published in LDS), not from the scan's value of
+// the same boundary: the two can differ by an ulp, and at a boundary on x.5 they round apart -- the frames would then no longer
+// add up to mel_len.  Every boundary is rounded from one value, so the frames telescope exactly.
+// A rejected item (bad scale, target < 1, zero / non-finite total under a target, a total beyond int32, a negative override
+// without a prediction) gets mel_len = -1 and frames 0; its e is left as computed.
+// ---------------------------------------------------------------------------------------------------------------
+namespace efts {
+__global__ __launch_bounds__(256) void dur_control_kernel(const float* __restrict__ dur, long ld, const int* __restrict__ tlen,
+                                                          const float* __restrict__ scale, const float* __restrict__ ovr, long ldo,
+                                                          const int* __restrict__ target, int method1, float* __restrict__ e,
+                                                          int* __restrict__ mlen, int* __restrict__ frames, int T) {
+    __shared__ float sh[4];
+    __shared__ float last;
+    __shared__ int bad;
+    __shared__ float endrun[256];                        // each thread's running sum at the end of its chunk (pass 2)
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tl = min(tlen[b], T);
+    const float* xr = dur ? dur + (long)b * ld : nullptr;
+    const float* orow = ovr ? ovr + (long)b * ldo : nullptr;
+    float* yr = e + (long)b * T;
+    const float s = scale ? scale[b] : 1.f;
+    // one value per token: the override where it is >= 0 (valid tokens only), else the prediction; scaled (a scale of 1 is skipped,
+    // so the default path adds the very same floats as dur_positions_kernel)
+    auto x = [&](int j) {
+        float v;
+        if (orow && j < tl && orow[j] >= 0.f) v = orow[j];
+        else v = xr ? xr[j] : 0.f;
+        return scale ? v * s : v;
+    };
+    if (tid == 0) {
+        last = 0.f;
+        bad = !(s > 0.f) || isinf(s) || (target && target[b] < 1);
+    }
+    const int chunk = (T + 255) / 256;
+    const int j0 = tid * chunk, j1 = min(j0 + chunk, T);
+    float loc = 0.f;
+    for (int j = j0; j < j1; ++j) loc += x(j);
+    const float incl = wave_scan_incl(loc);
+    if (lane == 63) sh[w] = incl;
+    __syncthreads();
+    if (!xr && orow)                                   // no prediction: every valid token needs an override
+        for (int j = j0; j < min(j1, tl); ++j)
+            if (!(orow[j] >= 0.f)) bad = 1;
+    float base = 0.f;
+    for (int i = 0; i < w; ++i) base += sh[i];
+    const float start = base + incl - loc;
+    float run = start;
+    for (int j = j0; j < j1; ++j) {
+        const float d = x(j);
+        run += d;
+        yr[j] = method1 ? run : run - d;
+        if (j == tl - 1) last = run;
+    }
+    endrun[tid] = run;
+    __syncthreads();
+    const int tgt = target ? target[b] : 0;
+    // (read by thread 0 only after the barrier below) a total whose rounding does not fit an int32 is rejected, not converted
+    if (!(fabsf(last) < 2147483520.f) || (target && !(last > 0.f))) bad = 1;
+    if (target || frames) {
+        const float f = target ? (float)tgt / last : 1.f;
+        // E_{j0-1} exactly as the previous thread computed it (its last e / frame boundary); thread 0: E_{-1} = 0.  A thread with
+        // a non-empty chunk always follows one with a full chunk, so endrun[tid - 1] is that thread's sequential sum.
+        const float pe = tid ? endrun[tid - 1] : 0.f;
+        float prev = pe, rprev = rintf(target ? pe * f : pe);
+        run = start;
+        for (int j = j0; j < j1; ++j) {
+            run += x(j);
+            float E = run;
+            if (target) {
+                E = j == tl - 1 ? (float)tgt : run * f;     // the last boundary lands on the target exactly
+                yr[j] = method1 ? E : prev * f;
+            }
+            const float r = rintf(E);
+            if (j < tl && !(fabsf(r) < 2147483520.f)) bad = 1;
+            if (frames) frames[(long)b * T + j] = j < tl && !(fabsf(r) >= 2147483520.f) ? (int)(r - rprev) : 0;
+            prev = run;
+            rprev = r;
+        }
+    }
+    __syncthreads();
+    if (bad && frames)
+        for (int j = j0; j < j1; ++j) frames[(long)b * T + j] = 0;
+    if (tid == 0) mlen[b] = bad ? -1 : target ? tgt : (int)rintf(last);
+}
+}  // namespace efts
+
+extern "C" int efts_duration_control(const float* dur, int64_t ld, const int32_t* text_len, const float* length_scale, const float* override_frames,
+                                     int64_t ldo, const int32_t* target_frames, int32_t method1, float* e, int32_t* mel_len, int32_t* frames,
+                                     int32_t B, int32_t T1, void* stream) {
+    if (!text_len || !e || !mel_len || B <= 0 || T1 <= 0) return efts_fail(EFTS_EINVAL, "efts_duration_control: bad arguments");
+    if (!dur && !override_frames) return efts_fail(EFTS_EINVAL, "efts_duration_control: neither durations nor overrides");
+    if ((dur && ld < T1) || (override_frames && ldo < T1)) return efts_fail(EFTS_ESHAPE, "efts_duration_control: ld / ldo < T1");
+    hipLaunchKernelGGL(dur_control_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, dur, (long)ld, text_len, length_scale, override_frames,
+                       (long)ldo, target_frames, method1 ? 1 : 0, e, mel_len, frames, T1);
+    return efts_check_launch("efts_duration_control");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // efts_bf16_round: the fp32 -> bf16 rounding every operand-plane producer of this library applies (mode 0; gfx950's
 // v_cvt_pk_bf16_f32) next to its integer reference form (mode 1), so that a test can sweep bit patterns through both.
 // ---------------------------------------------------------------------------------------------------------------

@@ -47,6 +47,7 @@ class GraphCache:
     def __init__(self, capacity: int = 8):
         self.capacity = capacity
         self.entries: "OrderedDict[tuple, _Entry]" = OrderedDict()
+        self.captures = 0                # graphs captured so far (a replay does not count): tests read it to check which calls re-capture
 
     def clear(self) -> None:
         self.entries.clear()
@@ -115,6 +116,7 @@ class GraphCache:
                 torch.cuda.synchronize()
                 return plain()
             ent.graph, ent.tag, ent.keepalive = g, tag, (keepalive, tuple(refs))
+            self.captures += 1
         else:
             for s, t in zip(ent.static_in, inputs):
                 if isinstance(t, PadTo):

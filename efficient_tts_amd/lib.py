@@ -132,6 +132,7 @@ _SIGS = {
     "efts_imv_align": (i32, [vp, vp, vp, f32, f32, i32, vp, vp, vp, i32, i32, i32, vp]),
     "efts_expand": (i32, [C.POINTER(ExpandArgs), vp]),
     "efts_duration_positions": (i32, [vp, i64, vp, f32, i32, vp, vp, i32, i32, vp]),
+    "efts_duration_control": (i32, [vp, i64, vp, vp, vp, i64, vp, i32, vp, vp, vp, i32, i32, vp]),
     "efts_bf16_round": (i32, [vp, vp, i64, i32, vp]),
     "efts_layernorm_rows": (i32, [vp, vp, vp, f32, vp, vp, vp, i64, i32, i32, i32, f32, C.c_uint32, vp, vp]),
     "efts_layernorm_dot": (i32, [vp, vp, vp, f32, vp, vp, vp, i32, f32, vp, i32, i32, f32, C.c_uint32, vp, vp]),

@@ -778,7 +778,9 @@ class EfficientTTSCNN(torch.nn.Module):
         finally:
             object.__setattr__(self, "_drop_now", prev)
 
-    def _forward_body(self, text, text_lengths, speech, speech_lengths, keep: bool = False):
+    def _forward_body(self, text, text_lengths, speech, speech_lengths, keep: bool = False, upto_align: bool = False):
+        """upto_align (align()): stop after the IMV block -- no value projection of the merged path, no duration predictor, decoder,
+        mel head or losses -- and return (imv, e, tl, ml) (e: this workspace's buffer)"""
         dev = text.device
         B, T1 = text.shape
         T2 = speech.shape[1]
@@ -884,10 +886,11 @@ class EfficientTTSCNN(torch.nn.Module):
             te_done.record(main)
             key_p = self._key_proj(ws, pk, rs1, tstate["x_p"], gap1, len1)          # :149, :155-156 (q.k^T is next on this stream)
             side.wait_event(te_done)
-            with O.on_stream(side):                                               # the value projection beside the key projection, then the
-                val_f, val_p = self._value_proj(ws, pk, rs1, tstate["x_p"], gap1, len1, vt)   # :150-157   duration predictor (:219;
-                v_ready.record(side)                                              # needed by the loss only).  (Its k3 convolutions as riders of
-                dur = self._duration(ws, pk, rs1, val_p, gap1, len1.data_ptr(), 0)    # decoder launches: measured slower, 1.665 vs 1.633 ms, r3.)
+            if not upto_align:
+                with O.on_stream(side):                                           # the value projection beside the key projection, then the
+                    val_f, val_p = self._value_proj(ws, pk, rs1, tstate["x_p"], gap1, len1, vt)   # :150-157   duration predictor (:219;
+                    v_ready.record(side)                                          # needed by the loss only).  (Its k3 convolutions as riders of
+                    dur = self._duration(ws, pk, rs1, val_p, gap1, len1.data_ptr(), 0)    # decoder launches: measured slower, 1.665 vs 1.633 ms, r3.)
         else:
             # second HIP stream: the text-side launches fill the tail rounds of the mel-length kernels
             k_ready = torch.cuda.Event()
@@ -896,7 +899,8 @@ class EfficientTTSCNN(torch.nn.Module):
                     O.row_masks(tl, rs1, gap1, len1)                              # :137
                 key_p, val_f, val_p = self._text_side(ws, pk, text, rs1, gap1, len1, on_key=lambda: k_ready.record(side), vt=vt)  # :144-157
                 v_ready.record(side)
-                dur = self._duration(ws, pk, rs1, val_p, gap1, len1.data_ptr(), 0)    # :219
+                if not upto_align:
+                    dur = self._duration(ws, pk, rs1, val_p, gap1, len1.data_ptr(), 0)    # :219
             q_p = mel_stack(*prenet())
             main.wait_event(k_ready)
 
@@ -923,6 +927,9 @@ class EfficientTTSCNN(torch.nn.Module):
                                 B, T1, T2)                                        # :178-180, :203-216
             if not self.delta_e_method_1:
                 O.duration_target(e, tl, ml, float(self.duration_offset), False, lde, B, T1)   # :205-213
+        if upto_align:
+            main.wait_stream(side)
+            return imv, e, tl, ml
         ralpha = torch.empty(B, T1, T2, dtype=torch.float32, device=dev)
 
         main.wait_event(v_ready)
@@ -948,20 +955,32 @@ class EfficientTTSCNN(torch.nn.Module):
 
     # ------------------------------------------------------------------ inference (efficient_tts.py:230-285)
     @torch.no_grad()
-    def inference(self, text: torch.Tensor, text_lengths: torch.Tensor = None):
-        """Free-running synthesis of ONE utterance: returns (mel_pred[1,T2,odim], reconst_alpha[1,T1,T2])."""
+    def inference(self, text: torch.Tensor, text_lengths: torch.Tensor = None, *, length_scale: float = 1.0,
+                  durations: Optional[torch.Tensor] = None, target_frames=None, return_durations: bool = False):
+        """Free-running synthesis of ONE utterance: returns (mel_pred[1,T2,odim], reconst_alpha[1,T1,T2]).
+
+        Duration control (keyword-only; the defaults are the reference's call): `length_scale` multiplies every duration (> 1:
+        slower speech), `durations` [1, T1] (or [T1]) gives frames per phoneme -- entries >= 0 replace the prediction, negative
+        ones keep it, the scale applies to both -- and `target_frames` rescales the utterance to exactly that many frames.
+        return_durations=True appends the integer frames per phoneme [1, T1] int64 (they add up to T2).
+        A call with any of these (return_durations=True alone included) runs as a ragged batch of one even with `graphs` off: that
+        arithmetic masks every layer by the length and differs from the unmasked B = 1 pass of a plain graphs-off call by up to ~1e-4
+        (with `graphs` on, the default, plain calls take that batched path too and the two agree bit for bit).  A total that does not
+        fit an int32 frame count (a huge length_scale) is rejected with ValueError."""
+        ctl = self._duration_controls(1, text.shape[-1], length_scale, durations, target_frames, return_durations)
         prev, self._free_running = self._free_running, True
         try:
-            return self._inference_impl(text, text_lengths)
+            out = self._inference_impl(text, text_lengths, ctl)
         finally:
             self._free_running = prev
+        return out if return_durations else out[:2]
 
-    def _inference_impl(self, text: torch.Tensor, text_lengths: torch.Tensor = None):
+    def _inference_impl(self, text: torch.Tensor, text_lengths: torch.Tensor = None, ctl=None):
         self._require(text)
         if text.shape[0] != 1:
             raise ValueError("inference() takes one utterance, like the reference (efficient_tts.py:361); "
                              "use inference_batch() for B > 1")
-        if self.graphs and not torch.cuda.is_current_stream_capturing():
+        if ctl is not None or (self.graphs and not torch.cuda.is_current_stream_capturing()):
             # same arithmetic as a ragged batch of one (every layer masked by the length; equal to the unmasked B = 1 pass
             # below to ~1e-4), on bucketed shapes whose launches replay as two hipGraphs around the one host sync
             # (text_lengths is accepted and ignored, like the reference's inference(): efficient_tts.py:233, :243 -- every position
@@ -972,6 +991,9 @@ class EfficientTTSCNN(torch.nn.Module):
                 if len(self._len1) > 4096:
                     self._len1.clear()
                 tl1 = self._len1[key] = torch.full((1,), text.shape[1], dtype=torch.int32, device=text.device)
+            if ctl is not None:                              # (with graphs off too: the controls live in the batched phase 1)
+                mel, _, ralpha, frames = self._inference_batch_impl(text, None, None, tl_i32=tl1, want_lengths=False, ctl=ctl)
+                return mel, ralpha, frames
             mel, _, ralpha = self._inference_batch_impl(text, None, None, tl_i32=tl1, want_lengths=False)
             return mel, ralpha
         dev = text.device
@@ -1002,9 +1024,48 @@ class EfficientTTSCNN(torch.nn.Module):
     # ------------------------------------------------------------------ batched ragged inference (extension)
     T1_BUCKET, T2_BUCKET = 16, 64       # free-running inference runs on shapes rounded up to these multiples (graph / workspace reuse)
 
-    def _infer_text(self, ws, text, tl, force_delta):
+    @staticmethod
+    def _duration_controls(B: int, T1: int, length_scale, durations, target_frames, return_durations: bool):
+        """Host-side checks of the duration controls of inference() / inference_batch(), before any device call.  None when no
+        control is asked for (the calls of today, on their own graphs); else (scale [B] fp32, override [B, T1] fp32,
+        target [B] int32), each None when absent and not yet on the device.  A length_scale of exactly 1.0 is no control."""
+        scale = over = target = None
+        if length_scale is not None:
+            if isinstance(length_scale, torch.Tensor):
+                if length_scale.dim() > 1 or length_scale.numel() not in (1, B):
+                    raise ValueError(f"length_scale: a float or a [B] = [{B}] tensor, got shape {tuple(length_scale.shape)}")
+                scale = length_scale.detach().reshape(-1).to(torch.float32).expand(B).contiguous()
+                if not scale.is_cuda and not bool(((scale > 0) & torch.isfinite(scale)).all()):
+                    raise ValueError("length_scale must be > 0 and finite")
+            else:
+                v = float(length_scale)
+                if not (v > 0.0 and v != float("inf")):
+                    raise ValueError(f"length_scale must be > 0 and finite, got {length_scale}")
+                if v != 1.0:
+                    scale = torch.full((B,), v, dtype=torch.float32)
+        if durations is not None:
+            d = torch.as_tensor(durations).detach()
+            if B == 1 and d.dim() == 1:
+                d = d[None]
+            if tuple(d.shape) != (B, T1):
+                raise ValueError(f"durations: [B, T1] = [{B}, {T1}] frames per phoneme (negative: predicted), got shape {tuple(d.shape)}")
+            over = d.to(torch.float32).contiguous()
+        if target_frames is not None:
+            t = torch.as_tensor(target_frames).detach().reshape(-1)
+            if t.numel() != B or t.is_floating_point() and not bool((t == t.round()).all()):
+                raise ValueError(f"target_frames: {B} whole numbers of frames, got {tuple(torch.as_tensor(target_frames).shape)}")
+            if not t.is_cuda and bool((t < 1).any()):
+                raise ValueError("target_frames must be >= 1")
+            target = t.to(torch.int32).contiguous()
+        if scale is None and over is None and target is None and not return_durations:
+            return None
+        return scale, over, target
+
+    def _infer_text(self, ws, text, tl, force_delta, ctl=None):
         """phase 1 (no host sync): embed -> text encoder -> value -> duration predictor -> aligned positions e = cumsum(durations)
-        and the mel length of every item (efficient_tts.py:246-260).  text [B, T1] int64 (positions >= tl are ignored), tl int32 [B]."""
+        and the mel length of every item (efficient_tts.py:246-260).  text [B, T1] int64 (positions >= tl are ignored), tl int32 [B].
+        ctl: device (scale, override, target) of the duration controls (any of them None): positions, lengths and the frames per
+        phoneme from efts_duration_control, returned as a third output (mel length -1: a rejected item)."""
         dev = text.device
         B, T1 = text.shape
         C = self.n_channels
@@ -1036,8 +1097,12 @@ class EfficientTTSCNN(torch.nn.Module):
         # durations -> positions e = cumsum, mel lengths round(e[len - 1]) (:260, :270), positions from 0 for method 2 (:261-265)
         e = torch.empty(B, T1, dtype=torch.float32, device=dev)
         ml = torch.empty(B, dtype=torch.int32, device=dev)
-        O.duration_positions(delta, rs1.Tp, tl, force_delta, self.delta_e_method_1, e, ml, B, T1)
-        return e, ml
+        if ctl is None:
+            O.duration_positions(delta, rs1.Tp, tl, force_delta, self.delta_e_method_1, e, ml, B, T1)
+            return e, ml
+        frames = torch.empty(B, T1, dtype=torch.int32, device=dev)
+        O.duration_control(delta, rs1.Tp, tl, *ctl, self.delta_e_method_1, e, ml, frames, B, T1)
+        return e, ml, frames
 
     def _infer_mel(self, ws, ws2, e, tl, ml, T2: int):
         """phase 2: Gaussian re-alignment from e, expand, decoder, mel head on a [B, T2] row space (efficient_tts.py:270-284);
@@ -1056,7 +1121,9 @@ class EfficientTTSCNN(torch.nn.Module):
         return mel, ralpha
 
     @torch.no_grad()
-    def inference_batch(self, text: torch.Tensor, text_lengths: torch.Tensor, force_delta: Optional[float] = None):
+    def inference_batch(self, text: torch.Tensor, text_lengths: torch.Tensor, force_delta: Optional[float] = None, *,
+                        length_scale=None, durations: Optional[torch.Tensor] = None, target_frames: Optional[torch.Tensor] = None,
+                        return_durations: bool = False):
         """Free-running synthesis of B utterances at once -- an extension the reference cannot do
         (its inference() is B == 1 only: efficient_tts.py:361).  Every item is computed exactly as if it
         were alone: positions beyond an item's own length are kept at zero after EVERY layer (true
@@ -1070,16 +1137,27 @@ class EfficientTTSCNN(torch.nn.Module):
         like any other ragged tail) and replay per-shape hipGraphs from the second call of a shape on.
 
         force_delta (benchmark hook): the duration predictor still runs, but every
-        valid phoneme then gets this many frames, so a synthetic batch yields a known, equal T2."""
+        valid phoneme then gets this many frames, so a synthetic batch yields a known, equal T2.
+
+        Duration control (keyword-only, as inference(); not together with force_delta): `length_scale` a float or a [B] tensor,
+        `durations` [B, T1] frames per phoneme (negative: predicted), `target_frames` [B] exact mel lengths.  The controls are
+        inputs of the phase-1 graph: a new pace replays it.  return_durations=True appends the frames per phoneme [B, T1] int64
+        (0 beyond each text length; item b's add up to mel_lengths[b])."""
+        ctl = self._duration_controls(text.shape[0], text.shape[1], length_scale, durations, target_frames, return_durations)
+        if ctl is not None and force_delta is not None:
+            raise ValueError("force_delta (benchmark hook) does not combine with length_scale / durations / target_frames / return_durations")
         prev, self._free_running = self._free_running, True
         try:
-            return self._inference_batch_impl(text, text_lengths, force_delta)
+            out = self._inference_batch_impl(text, text_lengths, force_delta, ctl=ctl)
         finally:
             self._free_running = prev
+        return out if return_durations else out[:3]
 
-    def _inference_batch_impl(self, text, text_lengths, force_delta, tl_i32: Optional[torch.Tensor] = None, want_lengths: bool = True):
+    def _inference_batch_impl(self, text, text_lengths, force_delta, tl_i32: Optional[torch.Tensor] = None, want_lengths: bool = True,
+                              ctl=None):
         """tl_i32: the lengths already as an int32 device tensor (inference() keeps one per length); want_lengths=False: the caller
-        drops the mel lengths (inference()), so they are not converted"""
+        drops the mel lengths (inference()), so they are not converted.  ctl: host-checked duration controls (_duration_controls):
+        the frames per phoneme are returned as a fourth output"""
         self._require(text)
         with O.stream_scope():
             dev = text.device
@@ -1091,7 +1169,20 @@ class EfficientTTSCNN(torch.nn.Module):
             self._te0_table(pk)                               # (built outside the graphs, like the packed planes)
             wsig = (self._ptr_sig, tuple(w.ptr for w in pk.values()), self.opt.tag(), self._te0_ptr())
             ws = self._workspace(("infb", B, T1b), dev)
-            if graphs:
+            if ctl is not None:
+                ctl = tuple(None if c is None else c.to(dev) for c in ctl)
+                have = tuple(c is not None for c in ctl)       # graph keys name the controls present, not their values
+            frames = None
+            if graphs and ctl is not None:
+                def phase1c(t, l, *given):
+                    it = iter(given)
+                    with O.stream_scope():
+                        return self._infer_text(ws, t, l, None, tuple(next(it) if h else None for h in have)) + (l,)
+                ids = PadTo(text, (B, T1b)) if T1b != T1 else text.contiguous()
+                given = [c if i != 1 or T1b == T1 else PadTo(c, (B, T1b)) for i, c in enumerate(ctl) if c is not None]
+                e, ml, frames, tl = self._infer_cache.run(("text", B, T1b, "ctl", have), (ws.serial, wsig), (ids, tl, *given), phase1c,
+                                                          keepalive=ws, clone=False)
+            elif graphs:
                 def phase1(t, l):
                     with O.stream_scope():              # resolved INSIDE the capture: the launches must go to the capturing stream
                         return self._infer_text(ws, t, l, force_delta) + (l,)
@@ -1100,9 +1191,19 @@ class EfficientTTSCNN(torch.nn.Module):
                 # The ids go straight into the zero-filled bucket-wide static input (positions beyond an item's length are ignored).
                 ids = PadTo(text, (B, T1b)) if T1b != T1 else text.contiguous()
                 e, ml, tl = self._infer_cache.run(("text", B, T1b, force_delta), (ws.serial, wsig), (ids, tl), phase1, keepalive=ws, clone=False)
+            elif ctl is not None:
+                e, ml, frames = self._infer_text(ws, text, tl, None, ctl)
             else:
                 e, ml = self._infer_text(ws, text, tl, force_delta)
-            t2 = int((ml if B == 1 else ml.max()).item())                                  # the one host sync
+            if ctl is None:
+                t2 = int((ml if B == 1 else ml.max()).item())                              # the one host sync
+            else:
+                mlh = ml.cpu()                                                             # the one host sync
+                bad = (mlh < 0).nonzero().flatten().tolist()
+                if bad:
+                    raise ValueError(f"duration control rejected item(s) {bad}: length_scale must be > 0 and finite, target_frames >= 1 "
+                                     "with a non-zero total duration, a total that fits an int32 frame count")
+                t2 = int(mlh.max())
             if t2 <= 0:
                 raise ValueError("predicted total durations round to 0 frames")
             T2b = roundup(t2, self.T2_BUCKET) if graphs else t2
@@ -1112,7 +1213,8 @@ class EfficientTTSCNN(torch.nn.Module):
                     with O.stream_scope():
                         return self._infer_mel(ws, ws2, e_, l, m, T2b)
                 trim = T2b != t2 or T1b != T1
-                mel, ralpha = self._infer_cache.run(("mel", B, T1b, T2b), (ws.serial, ws2.serial, wsig), (), phase2, keepalive=(ws, ws2),
+                mkey = ("mel", B, T1b, T2b) if ctl is None else ("mel", B, T1b, T2b, "ctl", have)   # (one phase 2 per phase-1 entry)
+                mel, ralpha = self._infer_cache.run(mkey, (ws.serial, ws2.serial, wsig), (), phase2, keepalive=(ws, ws2),
                                                     refs=(e, tl, ml), clone=not trim)
                 if trim:                                       # (the trimmed copies are the fresh tensors the caller gets)
                     # .clone(), not .contiguous(): at B == 1 (or t2 == T2b) the slice of the graph's static output is already
@@ -1123,7 +1225,43 @@ class EfficientTTSCNN(torch.nn.Module):
             else:
                 mel, ralpha = self._infer_mel(ws, ws2, e, tl, ml, T2b)
                 ml = ml.to(torch.int64) if want_lengths else ml
+            if ctl is not None:
+                return mel, ml, ralpha, frames[:, :T1].to(torch.int64)       # (a new tensor: `frames` may be a graph's static output)
             return mel, ml, ralpha
+
+    # ------------------------------------------------------------------ alignment of a recording (extension)
+    @torch.no_grad()
+    def align(self, text: torch.Tensor, text_lengths: torch.Tensor, speech: torch.Tensor, speech_lengths: torch.Tensor) -> dict:
+        """Phoneme timings of recordings through the model's own teacher-forced alignment (efficient_tts.py:137-180, :203-213):
+        the text side, the prenet, the mel encoder, the attention and the IMV -- the launches of forward() up to there, and
+        nothing after them (no duration predictor, decoder, mel head or losses).  Dropout is never applied.  Returns a dict:
+          e         [B, T1] fp32  the aligned positions forward() computes (:178-180);
+          durations [B, T1] fp32  the reference's delta_e for this model's delta_e_method_1 (:203-213), 0 beyond each text length;
+          frames    [B, T1] int64 the durations as whole frames (efts_duration_control: round(E_i) - round(E_{i-1}) of their
+                                  cumulative sum E, so item b's add up to round(sum of its durations));
+          imv       [B, T2] fp32  the index mapping vector (:174).
+        `inference(text, durations=align(...)["durations"])` re-synthesises with the recorded timing."""
+        self._require(text)
+        B, T1 = text.shape
+        prev = getattr(self, "_drop_now", None)
+        object.__setattr__(self, "_drop_now", None)
+        try:
+            with O.stream_scope():
+                imv, e, tl, ml = self._forward_body(text, text_lengths, speech, speech_lengths, upto_align=True)
+                e = e.clone()                                  # (the workspace's buffer: the next forward() overwrites it)
+                valid = torch.arange(T1, device=e.device)[None, :] < tl.to(torch.int64)[:, None]
+                if self.delta_e_method_1:                      # :204  delta_e_i = e_i - e_{i-1}, e_{-1} = 0
+                    dur = torch.diff(e, dim=1, prepend=torch.zeros(B, 1, device=e.device))
+                else:                                          # :205-213  delta_e_i = e_{i+1} - e_i with e_{len} = mel length
+                    ee = torch.cat([e, torch.zeros(B, 1, device=e.device)], dim=1)
+                    ee.scatter_(1, tl.to(torch.int64)[:, None], ml.to(torch.float32)[:, None])
+                    dur = ee[:, 1:] - ee[:, :-1]
+                dur = torch.where(valid, dur, torch.zeros((), device=e.device))
+                frames = torch.empty(B, T1, dtype=torch.int32, device=e.device)
+                O.duration_control(dur, T1, tl, None, None, None, True, torch.empty_like(e), torch.empty_like(tl), frames, B, T1)
+        finally:
+            object.__setattr__(self, "_drop_now", prev)
+        return dict(e=e, durations=dur, frames=frames.to(torch.int64), imv=imv)
 
 
 def _opt_property(name: str):

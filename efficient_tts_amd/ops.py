@@ -444,6 +444,15 @@ def duration_positions(dur: torch.Tensor, ld: int, tl, force_delta, method1: boo
                                              e.data_ptr(), ml.data_ptr(), B, T1, _stream()), "efts_duration_positions")
 
 
+def duration_control(dur: Optional[torch.Tensor], ld: int, tl, scale: Optional[torch.Tensor], override: Optional[torch.Tensor],
+                     target: Optional[torch.Tensor], method1: bool, e, ml, frames: Optional[torch.Tensor], B, T1) -> None:
+    """duration_positions with a per-item scale [B], per-token frame overrides [B][>= T1] (negative: keep dur) and per-item target
+    lengths [B] int32, plus the integer frames per token (efts_duration_control; ml = -1 marks a rejected item)"""
+    L.check(L.load().efts_duration_control(_p(dur), ld, tl.data_ptr(), _p(scale), _p(override), 0 if override is None else override.stride(0),
+                                           _p(target), int(method1), e.data_ptr(), ml.data_ptr(), _p(frames), B, T1, _stream()),
+            "efts_duration_control")
+
+
 def layernorm_rows(x_ptr, gamma, beta, eps, rowmask_ptr, out_f32_ptr, plane: Optional[Plane], rows, c, drop_p: float = 0.0,
                    drop_seed: int = 0, seed_add_ptr: Optional[int] = None) -> None:
     L.check(L.load().efts_layernorm_rows(x_ptr, gamma.data_ptr(), beta.data_ptr(), eps, rowmask_ptr, out_f32_ptr,

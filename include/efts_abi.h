@@ -410,6 +410,22 @@ int efts_expand(const efts_expand_args* a, void* stream);
 int efts_duration_positions(const float* dur, int64_t ld, const int32_t* text_len, float force_delta, int32_t method1, float* e,
                             int32_t* mel_len, int32_t B, int32_t T1, void* stream);
 
+/* efts_duration_positions with duration control, one launch per batch (same scan; with every control NULL the results are
+ * efts_duration_positions' bit for bit).  Every control may be NULL:
+ *   length_scale [B]      multiplies every duration of item b (> 0 and finite);
+ *   override_frames [B][ldo]  frames per token: entries >= 0 replace dur (valid tokens only), negative ones keep it; the scale
+ *                         applies to replaced entries too.  dur may be NULL when the overrides cover every valid token;
+ *   target_frames [B]     after the scan, item b is rescaled so that its last inclusive position E_{len-1} is target_frames[b]
+ *                         exactly (>= 1; a zero total duration cannot be rescaled), and mel_len[b] = target_frames[b].
+ * e [B][T1] and mel_len [B] as efts_duration_positions (method1 == 0: positions from 0).  frames [B][T1] (optional):
+ * frames[b][i] = round(E_i) - round(E_{i-1}) with E the inclusive cumulative (scaled) duration, E_{-1} = 0, round half-even;
+ * 0 past text_len, so sum_i frames[b][i] == mel_len[b] (each boundary is rounded from one fp32 value, also across the scan's
+ * chunks).  A rejected item (bad scale or target, a total that does not fit an int32, a negative override without dur) gets
+ * mel_len[b] = -1 (and frames 0). */
+int efts_duration_control(const float* dur, int64_t ld, const int32_t* text_len, const float* length_scale, const float* override_frames,
+                          int64_t ldo, const int32_t* target_frames, int32_t method1, float* e, int32_t* mel_len, int32_t* frames,
+                          int32_t B, int32_t T1, void* stream);
+
 /* The fp32 -> bf16 rounding of every operand-plane producer in this library (round to nearest even; torch's
  * .to(torch.bfloat16)): mode 0 = as the kernels do it (gfx950's packed conversion instruction), mode 1 = the integer
  * reference form.  y[i] = bf16 bits of x[i].  Exists so that a test can sweep bit patterns through both. */
