@@ -241,7 +241,7 @@ def measure_train(a, world, rank, dev, wl, steps, warmup, precision=None):
             model.dropout_calls = snap[6]
             for g_, old in zip(opt.param_groups, snap[7]):
                 g_.update(old)
-            model._packed_sig = None
+            model.planes.invalidate()
         torch.cuda.synchronize()
         same_again, every_again = fingerprints()
         assert same_again, "replicas differ after the no-exchange loop was undone: " + str([e.tolist() for e in every_again])

@@ -20,7 +20,8 @@ import torch
 from . import lib as L
 from . import ops as O
 from .graphs import GraphCache, PadTo
-from .ops import F32Rows, PackedWeight, Plane, Rows, roundup
+from .ops import F32Rows, Plane, Rows, roundup
+from .weights import WeightPlanes
 
 
 # --------------------------------------------------------------------------------------
@@ -265,11 +266,7 @@ class EfficientTTSCNN(torch.nn.Module):
         self.dropout_seed = 0x5EED          # base seed of the train-mode dropout masks (mixed with the data-parallel rank and the step counter)
         self._drop_now = None               # set while a train()-mode gradient-free forward enqueues its launches: (conv p, k -> seed, duration p, (seed0, seed1))
         self.dropout_calls = 0              # training steps taken so far: the position in the mask sequence (the trainer restores it from the step count on --resume)
-        self._packed: Dict[str, PackedWeight] = {}
-        self._packed_sig = None
-        self._ptr_sig = 0
-        self._packed_gen = 0                # bumped by every repack: what derived caches (TrainEngine) compare
-        self._folded_gen = -1               # the repack that last wrote the training engine's folded fp32 copies
+        self.planes = WeightPlanes()        # the packed operand planes of the Conv1d / Linear weights
         self._ws: Dict[Tuple, _Workspace] = {}
         self._ws_infer: Dict[Tuple, _Workspace] = {}
         self._ws_train: Dict[Tuple, _Workspace] = {}
@@ -280,153 +277,20 @@ class EfficientTTSCNN(torch.nn.Module):
             if isinstance(m, torch.nn.Conv1d) and hasattr(m, "weight_g"):
                 torch.nn.utils.remove_weight_norm(m)
                 logging.debug(f"Weight norm is removed from {m}.")
-        self._packed_sig = None
+        self.planes.invalidate()
 
     def apply_weight_norm(self):
         for m in self.modules():
             if isinstance(m, torch.nn.Conv1d) and not hasattr(m, "weight_g"):
                 torch.nn.utils.weight_norm(m)
-        self._packed_sig = None
+        self.planes.invalidate()
 
-    # ------------------------------------------------------------------ packed weights
-    def _conv_modules(self):
-        out = []
-        for blk in ("text_encoder", "mel_encoder", "decoder"):
-            for i, layer in enumerate(getattr(self, blk).layers):
-                out.append((f"{blk}.{i}", layer.conv[0]))
-        for i, seq in enumerate(self.duration_predictor.conv):
-            out.append((f"dur.{i}", seq[0]))
-        return out
-
-
-    def _weights(self, folded: Optional[Dict[str, torch.Tensor]] = None,
-                 wt: Optional[Dict[str, PackedWeight]] = None, params=None, phase_of=None) -> Dict[str, PackedWeight]:
-        """B operand planes of every Conv1d/Linear; repacked (weight-norm fold fused) whenever
-        a parameter changed (optimizer step, load_state_dict, .to()).  Training engine extras, produced by the same
-        launches: `folded[name]` (fp32 [cout][cin][taps]) receives the folded weight g * v / ||v|| of a weight-normed
-        conv, `wt[name]` the transposed + tap-flipped dgrad plane.  Equally shaped weights go through ONE grouped
-        call (`efts_pack_weights_grouped`, a device-side item table) instead of a launch each.
-        `_packed_sig` cannot see in-place updates made by the fused optimizer kernel (no version bump), which is
-        why EftsAdam resets it and why consumers of derived data compare `_packed_gen`, never the signature.
-        `phase_of(name, has_dgrad_plane) -> [(phase, with_dgrad_plane, with_forward_plane), ...]` (round 6, the training pass): the repack in PHASES.  Nothing is
-        launched here then; `_issue_packs(phase)` enqueues a phase's grouped launches on the CURRENT stream, and the caller places the phases
-        where their first consumer needs them (the training pass: the text side's planes on the text stream, the rest on the main one; a phase
-        entry with with_forward_plane = False writes the dgrad plane only).  Every phase of a repack must be issued before the next one is scheduled."""
-        sig = tuple((p.data_ptr(), p._version) for p in (params if params is not None else self.parameters()))
-        if sig == self._packed_sig:
-            return self._packed
-        self._ptr_sig = hash(tuple(a for a, _ in sig))       # parameter storage identity (captured graphs hold these pointers)
-        dev = self.text_embedding_table.weight.device
-        pk = self._packed
-        folded = folded or {}
-        wt = wt or {}
-        mods = [(name, conv, conv.kernel_size[0]) for name, conv in self._conv_modules()]
-        lins = [("key", self.text_encoder_key), ("prenet", self.mel_prenet[0]), ("head", self.mel_output_layer)]
-        if not self.share_text_encoder_key_value:
-            lins.append(("value", self.text_encoder_value))
-        if self.mel_query_fc is not None:
-            lins.append(("qfc", self.mel_query_fc))
-        mods += [(name, lin, 1) for name, lin in lins]
-        groups: Dict[Tuple, list] = {}
-        for name, mod, taps in mods:
-            cout, cin = mod.weight_v.shape[:2] if hasattr(mod, "weight_g") else mod.weight.shape[:2]
-            if name not in pk or pk[name].buf.device != dev:
-                pk[name] = PackedWeight(cout, cin, taps, self.split, dev)
-            for phase, with_t, with_f in ([(None, name in wt, True)] if phase_of is None else phase_of(name, name in wt)):
-                groups.setdefault((cout, cin, taps, bool(with_t), phase, bool(with_f)), []).append((name, mod))
-        lib = L.load()
-        table_rows, launches = [], []
-        for (cout, cin, taps, with_t, phase, with_f), members in groups.items():
-            first = len(table_rows)
-            tiled = cout % 64 == 0 and cin % 64 == 0 and taps <= 5     # the library's one-pass path: no folded copy needed
-            for name, mod in members:
-                if hasattr(mod, "weight_g"):
-                    w, g = mod.weight_v.detach(), mod.weight_g.detach()
-                    fo = None if tiled else folded.get(name)
-                    if with_t and not tiled and fo is None:
-                        raise L.EftsError(f"{name}: the row pack kernels need a folded fp32 copy for the dgrad plane")
-                else:
-                    w, g, fo = mod.weight.detach(), None, None
-                assert w.is_contiguous()
-                # (a NULL forward plane: the item only writes its dgrad plane -- the forward plane was packed by an earlier phase)
-                table_rows.append((w.data_ptr(), 0 if g is None else g.data_ptr(), 0 if fo is None else fo.data_ptr(),
-                                   pk[name].ptr if with_f else 0, wt[name].ptr if with_t else 0))
-            ref = pk[members[0][0]]
-            launches.append((first, len(members), ref.ld, wt[members[0][0]].ld if with_t else 0, cout, cin, taps, int(with_t), phase))
-        key = tuple(table_rows)
-        tables = getattr(self, "_pack_tables", None)
-        if tables is None:
-            tables = {}
-            object.__setattr__(self, "_pack_tables", tables)
-        if key not in tables:
-            # Pointers are stable across steps: built once per item list.  Tables are KEPT (the eval forward and the training engine
-            # alternate between two lists -- with and without the dgrad planes -- and a training step captured as a hipGraph keeps
-            # launching with the table it was captured with: a replaced table would be freed memory under that graph).  Least
-            # recently used ones go beyond 8: those belong to parameter storages that no longer exist (re-homed / re-created
-            # parameters), which a captured step can no longer be replayed with either (its tag holds the storage signature)
-            while len(tables) >= 8:
-                tables.pop(next(iter(tables)))
-            # (scale workspace: one region per phase -- the launches of a phase run in order on one stream, different phases may overlap)
-            phases = sorted({t[8] for t in launches}, key=str)
-            region = max(n * co for _, n, _, _, co, _, _, _, _ in launches)
-            tables[key] = (torch.tensor(table_rows, dtype=torch.int64, device=dev), torch.empty(len(phases) * region, device=dev),
-                           {ph: i * region * 4 for i, ph in enumerate(phases)})
-        else:
-            tables[key] = tables.pop(key)                                # most recently used last
-        table, scale, region_of = tables[key]
-        base = table.data_ptr()
-        pending: Dict = {}
-        for first, n, ld, ld_t, cout, cin, taps, with_t, phase in launches:
-            pending.setdefault(phase, []).append((base + first * 40, n, scale.data_ptr() + region_of[phase], ld, ld_t, cout, cin, taps, self.split, with_t))
-        object.__setattr__(self, "_pack_pending", pending)
-        if phase_of is None:
-            self._issue_packs(None)
-        self._packed_sig = sig
-        self._packed_gen += 1
-        if wt:
-            self._folded_gen = self._packed_gen      # this repack also wrote the training engine's derived copies
-        return pk
-
-    def _issue_packs(self, phase) -> None:
-        """enqueue the grouped repack launches of `phase` (scheduled by the last `_weights` call) on the current stream"""
-        lib = L.load()
-        for args in self._pack_pending.pop(phase, []):
-            L.check(lib.efts_pack_weights_grouped(*args, O._stream()), "efts_pack_weights_grouped")
-
-    def _te0_table(self, pk) -> Optional[torch.Tensor]:
-        """tap_table [k_size][num_symbols][C] of text-encoder layer 0: tap k's weights applied to every symbol's embedding, in the
-        operand format the model runs in (k_size one-tap efts_gemm launches over the embedding rows); rebuilt when the weights were
-        re-packed.  None when the look-up form does not apply."""
+    # ------------------------------------------------------------------ packed weights (weights.py)
+    def _te0_table(self) -> Optional[torch.Tensor]:
+        """tap table of text-encoder layer 0 (WeightPlanes.te0_table) where the look-up form applies, else None"""
         if not self.embed_conv or len(self.text_encoder.layers) == 0 or self.n_channels % 32 or self._drop(0)[0] > 0.0 or self.k_size > 5 or self.act_general:
             return None                      # (a Dropout mask sits between layer 0's activation and its residual add: no look-up form)
-        if getattr(self, "_te0_gen", None) == self._packed_gen and getattr(self, "_te0_tab", None) is not None:
-            return self._te0_tab
-        table = self.text_embedding_table.weight.detach()
-        V, C, K = table.shape[0], self.n_channels, self.k_size
-        dev = table.device
-        rsv = Rows(1, V)
-        # ONE table (and one staging plane) per (device, geometry), rebuilt IN PLACE like the packed planes: captured graphs bake the
-        # table's address into their efts_embed_conv launch, so a fresh allocation per repack would leave them reading a freed or
-        # stale table after any weight update (ADVICE r3); the stream orders the rebuild in front of the next replay
-        geo = (dev, K, V, C, self.split)
-        if getattr(self, "_te0_geo", None) != geo:
-            object.__setattr__(self, "_te0_geo", geo)
-            object.__setattr__(self, "_te0_tab", torch.empty(K, V, C, dtype=torch.float32, device=dev))
-            object.__setattr__(self, "_te0_plane", Plane.for_rows(rsv, C, self.split, dev))
-            object.__setattr__(self, "_te0_ids", torch.arange(V, device=dev)[None])
-        tab, plane = self._te0_tab, self._te0_plane
-        with O.stream_scope():
-            O.embed(self._te0_ids, table, None, plane, rsv)
-            w = pk["text_encoder.0"]
-            for k in range(K):
-                O.gemm(a=plane, b_ptr=w.ptr + k * w.tap_stride, ldb=w.ld, m=V, n=C, out_f32_ptr=tab[k].data_ptr(), ldo=C, tiling=L.TILING_GENERIC)
-        object.__setattr__(self, "_te0_gen", self._packed_gen)
-        return tab
-
-    def _te0_ptr(self) -> int:
-        """address of the tap table (part of every graph tag: a new table means a new capture)"""
-        tab = getattr(self, "_te0_tab", None)
-        return 0 if (tab is None or not self.embed_conv) else tab.data_ptr()
+        return self.planes.te0_table(self)
 
     def _embed_te0(self, ws, pk, text, rs1: Rows, lens_i32: Optional[torch.Tensor], tab: torch.Tensor):
         """embedding + text-encoder layer 0 in one gather launch -> (fp32 stream, operand plane) of layer 0's output"""
@@ -597,7 +461,7 @@ class EfficientTTSCNN(torch.nn.Module):
         (efficient_tts.py:144-157 / :246-255).  `on_key()` is called as soon as the key projection is enqueued (the q.k^T launch
         of the other stream waits for that, not for the value); `vt`: also pack V^T for the alpha'.V launch here."""
         C = self.n_channels
-        tab = self._te0_table(pk)
+        tab = self._te0_table()
         if tab is not None:                                    # embedding + layer 0 as table look-ups; padded ids are real symbols here
             x_f, x_p = self._embed_te0(ws, pk, text, rs1, None, tab)
             start = 1
@@ -739,13 +603,13 @@ class EfficientTTSCNN(torch.nn.Module):
         if not self.graphs or torch.cuda.is_current_stream_capturing():
             return self._forward_impl(text, text_lengths, speech, speech_lengths)[0]
         # per-shape hipGraph: the launches of this shape are replayed as one graph (efficient_tts_amd/graphs.py)
-        pk = self._weights()                                  # (re)packing stays outside the graph
-        self._te0_table(pk)                                   # ... and so does the tap table of text-encoder layer 0
+        self.planes.get(self)                                 # (re)packing stays outside the graph
+        self._te0_table()                                     # ... and so does the tap table of text-encoder layer 0
         dev = text.device
         key = ("fwd", tuple(text.shape), tuple(speech.shape), text.dtype, speech.dtype, text_lengths.dtype, speech_lengths.dtype)
         ws = self._workspace(("fwd", text.shape[0], text.shape[1], speech.shape[1]), dev)
         # the graph is valid while the buffers its launches point at live: this workspace, the packed planes, the parameters
-        tag = (ws.serial, self._ptr_sig, tuple(w.ptr for w in pk.values()), self.opt.tag(), self._te0_ptr())
+        tag = (ws.serial, self.planes.tag(), self.opt.tag())
 
         def body(t, tl, sp, sl):
             (_, stats, imv, ralpha, mel_pred, _), _ = self._forward_impl(t, tl, sp, sl)
@@ -787,7 +651,7 @@ class EfficientTTSCNN(torch.nn.Module):
         C = self.n_channels
         text = text.contiguous()
         speech = speech.contiguous().float()
-        pk = self._weights()
+        pk = self.planes.get(self)
         ws = self._workspace(("fwd", B, T1, T2), dev)
         rs1, rs2 = Rows(B, T1, self.row_gap), Rows(B, T2, self.row_gap)
         gap1, len1 = ws.tensor("gap1", (rs1.rows,)), ws.tensor("len1", (rs1.rows,))
@@ -848,21 +712,21 @@ class EfficientTTSCNN(torch.nn.Module):
             # A persistent launch owns every CU's LDS, so a text-length launch of its own beside it would get the 4 spare CUs:
             # only the first nt - nm text layers run by themselves (efts_resconv5 on the short row space), beside the HBM-bound
             # prenet on the second stream.
-            nr = min(nt - (1 if self._te0_table(pk) is not None else 0), nm)       # (layer 0 may be table look-ups: it never rides)
+            nr = min(nt - (1 if self._te0_table() is not None else 0), nm)       # (layer 0 may be table look-ups: it never rides)
             ns = nt - nr                                                           # text layers that run by themselves first
             pre_ready, te_done = torch.cuda.Event(), torch.cuda.Event()
             # The first text layers and the prenet share the chip by halves: both kinds of workgroup take a whole CU (LDS), the
             # prenet is bound by HBM -- which half the CUs saturate -- and a text-length layer by streaming its weights, so the
             # prenet's grid is capped at half the CUs and the text layers are scheduled onto the other half.
             cus = torch.cuda.get_device_properties(dev).multi_processor_count
-            share = ns > (1 if self._te0_table(pk) is not None else 0) and cus >= 64
+            share = ns > (1 if self._te0_table() is not None else 0) and cus >= 64
             with O.on_stream(side):
                 pre = prenet(cus // 2 if share else 0)                             # (r6: 128 / 144 / 160 / 176 CUs for the prenet measured: no difference)
                 pre_ready.record(side)
             te_plan = O.resconv5_plan_buf(rs1.rows, C, cus // 2 - 2) if share else None
             if not masks_done:
                 O.row_masks(tl, rs1, gap1, len1)                                  # :137
-            tab = self._te0_table(pk)
+            tab = self._te0_table()
             if tab is not None:                                                   # :144 + layer 0 of :148 as table look-ups
                 x_f, x_p = self._embed_te0(ws, pk, text, rs1, None, tab)
                 first = 1
@@ -998,7 +862,7 @@ class EfficientTTSCNN(torch.nn.Module):
             return mel, ralpha
         dev = text.device
         T1, C = text.shape[1], self.n_channels
-        pk = self._weights()
+        pk = self.planes.get(self)
         ws = self._workspace(("inf", 1, T1), dev)
         rs1 = Rows(1, T1, self.row_gap)
         full = torch.full((1,), T1, dtype=torch.int32, device=dev)
@@ -1069,12 +933,12 @@ class EfficientTTSCNN(torch.nn.Module):
         dev = text.device
         B, T1 = text.shape
         C = self.n_channels
-        pk = self._weights()
+        pk = self.planes.get(self)
         rs1 = Rows(B, T1, self.row_gap)
         gap1, len1 = ws.tensor("gap1", (rs1.rows,)), ws.tensor("len1", (rs1.rows,))
         O.row_masks(tl, rs1, gap1, len1)
         # embedding with padded positions zeroed, then every layer masked by the item length
-        tab = self._te0_table(pk)
+        tab = self._te0_table()
         if tab is not None:                                    # embedding + layer 0 as table look-ups, zero beyond each item's length
             x_f, x_p = self._embed_te0(ws, pk, text.contiguous(), rs1, tl, tab)
             start = 1
@@ -1111,7 +975,7 @@ class EfficientTTSCNN(torch.nn.Module):
         dev = e.device
         B, T1 = e.shape
         C = self.n_channels
-        pk = self._weights()
+        pk = self.planes.get(self)
         rs1, rs2 = Rows(B, T1, self.row_gap), Rows(B, T2, self.row_gap)
         val_f = ws.f32("val_f", rs1, C)
         gap2, len2 = ws2.tensor("gap2", (rs2.rows,)), ws2.tensor("len2", (rs2.rows,))
@@ -1165,9 +1029,9 @@ class EfficientTTSCNN(torch.nn.Module):
             tl = tl_i32 if tl_i32 is not None else text_lengths.to(device=dev, dtype=torch.int32)
             graphs = self.graphs and not torch.cuda.is_current_stream_capturing()
             T1b = roundup(T1, self.T1_BUCKET) if graphs else T1
-            pk = self._weights()
-            self._te0_table(pk)                               # (built outside the graphs, like the packed planes)
-            wsig = (self._ptr_sig, tuple(w.ptr for w in pk.values()), self.opt.tag(), self._te0_ptr())
+            self.planes.get(self)
+            self._te0_table()                                 # (built outside the graphs, like the packed planes)
+            wsig = (self.planes.tag(), self.opt.tag())
             ws = self._workspace(("infb", B, T1b), dev)
             if ctl is not None:
                 ctl = tuple(None if c is None else c.to(dev) for c in ctl)

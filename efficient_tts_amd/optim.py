@@ -51,8 +51,7 @@ class EftsAdam(torch.optim.Optimizer):
         """clip (global norm of grad_scale * flat grads) + Adam-amsgrad, all on the device."""
         self.t += 1
         self.launch(grad_scale)
-        # parameters changed in place through the flat view: invalidate packed-weight caches
-        self.model._packed_sig = None
+        self.model.planes.invalidate()          # parameters changed in place through the flat view
 
     def hyper_words(self, step: int):
         """{lr, 1 - beta1^step, sqrt(1 - beta2^step)} as the kernel derives them from its by-value arguments, as 32-bit words"""

@@ -47,7 +47,7 @@ class GraphedStep:
     def _eligible(self) -> bool:
         m = self.model
         conv_dropout = m.training and float(getattr(m, "dropout_rate", 0.0)) >= 1e-5
-        return isinstance(self.opt, EftsAdam) and hasattr(m, "_weights") and not conv_dropout and not torch.cuda.is_current_stream_capturing()
+        return isinstance(self.opt, EftsAdam) and hasattr(m, "planes") and not conv_dropout and not torch.cuda.is_current_stream_capturing()
 
     def inputs(self, text, text_lengths, speech, speech_lengths):
         """The device tensors a captured step of this shape reads (text, text_lengths int32, speech, speech_lengths int32), or None before
@@ -68,7 +68,7 @@ class GraphedStep:
         """what a captured step is valid for: the buffers its launches point at and every argument they carry by value"""
         m, g = self.model, self.opt.param_groups[0]
         red = self.ddp.reducer if self.ddp is not None else None
-        return (ws.serial, id(eng), getattr(m, "_ptr_sig", None), float(self.opt.grad_norm), self.grad_scale, tuple(g["betas"]), float(g["eps"]),
+        return (ws.serial, id(eng), m.planes.tag(), float(self.opt.grad_norm), self.grad_scale, tuple(g["betas"]), float(g["eps"]),
                 float(g["weight_decay"]), bool(m.training), id(red), None if red is None else red.algo, eng.bucket_hook is not None,
                 m.opt.tag(), T.switch_tag())
 
@@ -108,7 +108,7 @@ class GraphedStep:
                 ent["static"] = [text.clone(), text_lengths.to(device=dev, dtype=torch.int32).clone(), speech.clone(),
                                  speech_lengths.to(device=dev, dtype=torch.int32).clone()]
                 calls0 = int(getattr(m, "dropout_calls", 0))
-                m._packed_sig = None                                  # the weight planes are (re)packed INSIDE the graph, every step
+                m.planes.invalidate()                                 # the weight planes are (re)packed INSIDE the graph, every step
                 g = torch.cuda.CUDAGraph()
                 torch.cuda.synchronize()
                 eng.step_words = self.words
@@ -133,6 +133,7 @@ class GraphedStep:
                         pass
                     eng.step_words = None
                     m.dropout_calls = calls0
+                    m.planes.invalidate()                         # (a repack enqueued into the failed capture never ran)
                     torch.cuda.synchronize()
                     return self._eager(text, text_lengths, speech, speech_lengths)
                 finally:
@@ -149,7 +150,7 @@ class GraphedStep:
         # what the eager loop's Python does around its launches
         m.dropout_calls = int(getattr(m, "dropout_calls", 0)) + 1
         self.opt.t += 1
-        m._packed_sig = None
+        m.planes.invalidate()
         for n, p in eng.named:
             p.grad = eng.g[n]
         if self.sch is not None:

@@ -130,7 +130,6 @@ class TrainEngine:
                             self.numel]
         self.folded: Dict[str, torch.Tensor] = {}
         self.wt: Dict[str, PackedWeight] = {}
-        self._sig = None
         self._ws_tag = ""                       # "s" while work is being enqueued on the side stream
         self.bucket_hook: Optional[Callable[[int], None]] = None
         self.join_reduce: Optional[Callable[[], None]] = None
@@ -145,39 +144,21 @@ class TrainEngine:
 
     # ------------------------------------------------------------------ weights for the backward
     @staticmethod
-    def _pack_phase(name: str, has_t: bool):
-        """where a weight's planes are repacked in the training step (model._weights(phase_of=...)): "te" = on the text stream (text encoder,
-        duration predictor, key / value), "me" = on the main stream (everything else); forward and dgrad plane in one pass.  Round 6 measured a finer
-        split -- only the planes the step's first launches read in front of them, the rest beside / behind the head of the step on the third stream:
-        3.23 -> 3.25-3.27 ms (bf16), 5.93-5.97 -> 6.02-6.05 (bf16x3) under bench.py's clock (profiles/train_ab_r06.txt): not kept."""
-        return [("te" if name.startswith(("text_encoder.", "dur.", "key", "value")) else "me", has_t, True)]
+    def _pack_phase(name: str) -> str:
+        """the phase of the training step's repack a weight's planes (forward and dgrad in one pass) belong to: "te" on the text stream (text
+        encoder, duration predictor, key / value), "me" on the main one.  A finer split measured slower in round 6: 3.23 -> 3.25-3.27 ms (bf16),
+        5.93-5.97 -> 6.02-6.05 (bf16x3) under bench.py's clock (profiles/train_ab_r06.txt)."""
+        return "te" if name.startswith(("text_encoder.", "dur.", "key", "value")) else "me"
 
     def _prepare_weights(self):
-        """forward planes, folded fp32 weights and transposed/flipped dgrad planes, all from `model._weights` (a handful
-        of grouped launches).  The derived copies follow `model._packed_gen` / `_folded_gen`, the repack counters: the
-        fused optimizer updates parameters in place without a version bump, so the signature of the parameters cannot
-        be used to detect a change, and an eval forward in between repacks without writing the copies kept here."""
+        """schedules the repack of the forward planes, folded fp32 weights and transposed / flipped dgrad planes (WeightPlanes.schedule)"""
         m = self.m
-        dev = self.dev
-        for name, conv in m._conv_modules():
-            if name not in self.wt:
-                taps = conv.kernel_size[0]
-                if hasattr(conv, "weight_g") and (conv.out_channels % 64 or conv.in_channels % 64 or taps > 5):
-                    self.folded[name] = torch.empty(conv.out_channels, conv.in_channels, taps, device=dev)   # row-kernel shapes only
-                self.wt[name] = PackedWeight(conv.in_channels, conv.out_channels, taps, m.split, dev)
-        lins = [("key", m.text_encoder_key), ("head", m.mel_output_layer)]
-        if not m.share_text_encoder_key_value:
-            lins.append(("value", m.text_encoder_value))
-        if m.mel_query_fc is not None:
-            lins.append(("qfc", m.mel_query_fc))
-        for name, lin in lins:
-            if name not in self.wt:
-                self.wt[name] = PackedWeight(lin.in_features, lin.out_features, 1, m.split, dev)
-        pk = m._weights(self.folded, self.wt, self.step_params, phase_of=self._pack_phase)
-        if m._folded_gen != m._packed_gen:
-            m._packed_sig = None                # the last repack (an eval forward) did not write the copies kept here
-            pk = m._weights(self.folded, self.wt, self.step_params, phase_of=self._pack_phase)
-        return pk
+        for name, mod, cout, cin, taps in m.planes.modules(m):
+            if name not in self.wt and name != "prenet":          # (the prenet's input is the frames: no dgrad plane)
+                if hasattr(mod, "weight_g") and (cout % 64 or cin % 64 or taps > 5):
+                    self.folded[name] = torch.empty(cout, cin, taps, device=self.dev)   # row-kernel shapes only
+                self.wt[name] = PackedWeight(cin, cout, taps, m.split, self.dev)
+        return m.planes.schedule(m, self.folded, self.wt, self.step_params, self._pack_phase)
 
     # ------------------------------------------------------------------ small wrappers
     def _act_bwd(self, g_ptr, y_ptr, x_ptr, mask_ptr, mode, dz: Optional[F32Rows], plane: Optional[Plane], dbias, rows, c,
@@ -446,9 +427,9 @@ class TrainEngine:
         side0 = m._side_stream(dev)
         side0.wait_stream(torch.cuda.current_stream(dev))
         pk = self._prepare_weights()
-        m._issue_packs("me")
+        m.planes.issue("me")
         with O.on_stream(side0):
-            m._issue_packs("te")
+            m.planes.issue("te")
         self.flat.zero_()
 
         # Two HIP streams.  The text-length work (embedding, text encoder, K/V, duration predictor and all of their

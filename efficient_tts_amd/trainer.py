@@ -147,7 +147,7 @@ class EfficientTTSTrainer:
         payload = torch.load(checkpoint_path, map_location="cpu")
         net = self._net
         net.load_state_dict(payload["model"])
-        net._packed_sig = None                 # operand planes are re-packed from the new parameters
+        net.planes.invalidate()                # operand planes are re-packed from the new parameters
         if load_only_params:
             return
         self.steps, self.epochs = payload["steps"], payload["epochs"]

@@ -185,8 +185,8 @@ def test_embed_conv_equals_embedding_plus_first_text_layer(precision, masked):
     m = EfficientTTSCNN(num_symbols=76, dropout_rate=0.0, use_masking=True, sigma=0.01, precision=precision)
     m.load_state_dict(O.fill_params())
     m = m.to(dev).eval()
-    pk = m._weights()
-    tab = m._te0_table(pk)
+    pk = m.planes.get(m)
+    tab = m._te0_table()
     assert tab is not None and tab.shape == (5, 76, 512)
     B, T = 5, 61
     g = torch.Generator().manual_seed(9)

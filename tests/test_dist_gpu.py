@@ -77,7 +77,8 @@ def _worker(rank, port, out):
 
         def restore():
             opt.flat_p.copy_(state[0]); opt.m.copy_(state[1]); opt.v.copy_(state[2]); opt.vmax.copy_(state[3])
-            opt.t, m.dropout_calls, m._packed_sig = state[4], state[5], None
+            opt.t, m.dropout_calls = state[4], state[5]
+            m.planes.invalidate()
 
         l_dp = one_step(ddp)
         torch.cuda.synchronize()
@@ -111,7 +112,8 @@ def _worker(rank, port, out):
 
             def back():
                 opt.flat_p.copy_(st0[0]); opt.m.copy_(st0[1]); opt.v.copy_(st0[2]); opt.vmax.copy_(st0[3])
-                opt.t, m.dropout_calls, m._packed_sig = st0[4], st0[5], None
+                opt.t, m.dropout_calls = st0[4], st0[5]
+                m.planes.invalidate()
             le, _ = step._eager(*batch)
             ge, pe = eng.flat.clone(), opt.flat_p.clone()
             back()

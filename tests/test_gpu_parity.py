@@ -629,13 +629,13 @@ def test_graphs_follow_weight_updates():
             m(text, tl, mel, sl)
             m.inference(one)
         assert next(iter(m._graph_cache.entries.values())).graph is not None
-        tab0 = m._te0_ptr()
+        tab0 = m.planes.te0_tab.data_ptr()
         for rnd in range(2):                                   # two rounds of updates: the table must be rebuilt, not re-allocated
             for p in (m.text_embedding_table.weight, m.text_encoder.layers[0].conv[0].weight_v, m.decoder.layers[2].conv[0].bias):
                 p.add_(0.05 * torch.randn_like(p))
             got = m(text, tl, mel, sl)
             got_inf = m.inference(one)
-            assert m._te0_ptr() == tab0
+            assert m.planes.te0_tab.data_ptr() == tab0
             m.graphs = False
             ref = m(text, tl, mel, sl)
             ref_inf = m.inference(one)

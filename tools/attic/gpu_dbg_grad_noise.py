@@ -17,7 +17,7 @@ def eager():
 e = [eager() for _ in range(4)]
 words = torch.zeros(8, dtype=torch.int32, device=dev)
 eng.step_words = words
-m.dropout_calls = 5; m._packed_sig = None
+m.dropout_calls = 5; m.planes.invalidate()
 g = torch.cuda.CUDAGraph()
 with torch.cuda.graph(g, capture_error_mode="thread_local"):
     with O.stream_scope():

@@ -35,7 +35,7 @@ for _ in range(50): eager()
 torch.cuda.synchronize()
 print(f"eager {1e3*(time.perf_counter()-t0)/50:.3f} ms/step")
 gr = torch.cuda.CUDAGraph()
-model._packed_sig = None
+model.planes.invalidate()
 with torch.cuda.graph(gr, capture_error_mode="thread_local"):
     out3, _ = eng.forward_backward(text, tl, mel, sl)
     model.dropout_calls -= 1
