@@ -954,9 +954,14 @@ extern "C" int efts_layernorm_bwd(const float* x, const float* gamma, const floa
     return efts_check_launch("efts_layernorm_bwd");
 }
 
+// e_bwd_kernel keeps e, de, mx, 1/se of one item in dynamic LDS (4 * T1 floats) and has no static LDS; efts_e_bwd launches it without raising
+// hipFuncAttributeMaxDynamicSharedMemorySize, so the launch gets at most HIP's default of 64 KiB per workgroup
+constexpr size_t E_BWD_MAX_LDS = 64 * 1024;
+
 extern "C" int efts_alpha_bwd(const float* ralpha, const float* dalpha, const float* e, const int32_t* text_len, const int32_t* mel_len,
                               float sigma, float* r_ws, float* de, int32_t B, int32_t T1, int32_t T2, void* stream) {
     if (!ralpha || !dalpha || !e || !text_len || !mel_len || !r_ws || !de) return efts_fail(EFTS_EINVAL, "efts_alpha_bwd: null pointer");
+    if (B <= 0 || T1 <= 0 || T2 <= 0) return efts_fail(EFTS_ESHAPE, "efts_alpha_bwd: B, T1, T2 must be positive (got %d, %d, %d)", B, T1, T2);
     hipLaunchKernelGGL(alpha_bwd_r_kernel, dim3((T2 + 63) / 64, B), dim3(256), 0, ST, ralpha, dalpha, r_ws, T1, T2);
     hipLaunchKernelGGL(alpha_bwd_e_kernel, dim3((T1 + 3) / 4, B), dim3(256), 0, ST, ralpha, dalpha, (const float*)r_ws, e, text_len, mel_len, sigma, de, T1, T2);
     return efts_check_launch("efts_alpha_bwd");
@@ -965,6 +970,10 @@ extern "C" int efts_alpha_bwd(const float* ralpha, const float* dalpha, const fl
 extern "C" int efts_e_bwd(const float* imv, const float* e, const float* de, const int32_t* text_len, const int32_t* mel_len, float sigma_e,
                           float* stats_ws, float* dpi, int32_t B, int32_t T1, int32_t T2, void* stream) {
     if (!imv || !e || !de || !text_len || !mel_len || !stats_ws || !dpi) return efts_fail(EFTS_EINVAL, "efts_e_bwd: null pointer");
+    if (B <= 0 || T1 <= 0 || T2 <= 0) return efts_fail(EFTS_ESHAPE, "efts_e_bwd: B, T1, T2 must be positive (got %d, %d, %d)", B, T1, T2);
+    if ((size_t)4 * T1 * sizeof(float) > E_BWD_MAX_LDS)
+        return efts_fail(EFTS_ESHAPE, "efts_e_bwd: T1 = %d needs %zu bytes of LDS (4 * T1 floats), the launch has %zu: T1 <= %zu", T1,
+                         (size_t)4 * T1 * sizeof(float), E_BWD_MAX_LDS, E_BWD_MAX_LDS / (4 * sizeof(float)));
     float* mx = stats_ws; float* se = stats_ws + (long)B * T1;
     hipLaunchKernelGGL(beta_stats_kernel, dim3((T1 + 3) / 4, B), dim3(256), 0, ST, imv, text_len, mel_len, sigma_e, mx, se, T1, T2);
     hipLaunchKernelGGL(e_bwd_kernel, dim3((T2 + 127) / 128, B), dim3(128), (size_t)4 * T1 * sizeof(float), ST, imv, e, de, (const float*)mx, (const float*)se,
@@ -975,6 +984,7 @@ extern "C" int efts_e_bwd(const float* imv, const float* e, const float* de, con
 extern "C" int efts_imv_bwd(const float* soft_idx, const float* imv, const float* dpi, const int32_t* text_len, const int32_t* mel_len, float* ds,
                             int32_t B, int32_t T2, void* stream) {
     if (!soft_idx || !imv || !dpi || !text_len || !mel_len || !ds) return efts_fail(EFTS_EINVAL, "efts_imv_bwd: null pointer");
+    if (B <= 0 || T2 <= 0) return efts_fail(EFTS_ESHAPE, "efts_imv_bwd: B, T2 must be positive (got %d, %d)", B, T2);
     hipLaunchKernelGGL(imv_bwd_kernel, dim3(B), dim3(64), 0, ST, soft_idx, imv, dpi, text_len, mel_len, ds, T2);
     return efts_check_launch("efts_imv_bwd");
 }
@@ -983,6 +993,10 @@ extern "C" int efts_attn_bwd(const float* scores, int64_t ld, const float* soft_
                              const int32_t* mel_len, float* dscores, int64_t ldd, void* plane, int64_t ld_plane, int32_t B, int32_t T1,
                              int32_t T2, int32_t T2p, void* stream) {
     if (!scores || !soft_idx || !ds || !text_len || !mel_len || !dscores || !plane) return efts_fail(EFTS_EINVAL, "efts_attn_bwd: null pointer");
+    if (B <= 0 || T1 <= 0 || T2 <= 0) return efts_fail(EFTS_ESHAPE, "efts_attn_bwd: B, T1, T2 must be positive (got %d, %d, %d)", B, T1, T2);
+    if (ld < T1 || ldd < T1) return efts_fail(EFTS_ESHAPE, "efts_attn_bwd: ld (%lld) and ldd (%lld) must be >= T1 (%d)", (long long)ld, (long long)ldd, T1);
+    if (T2p < T2) return efts_fail(EFTS_ESHAPE, "efts_attn_bwd: T2p (%d) < T2 (%d)", T2p, T2);
+    if (ld_plane < (int64_t)((T1 + 31) / 32) * 128) return efts_fail(EFTS_ESHAPE, "efts_attn_bwd: ld_plane too small for ceil(T1 / 32) chunks of 128 bytes");
     const long rows = (long)B * T2;
     hipLaunchKernelGGL(attn_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ST, scores, (long)ld, soft_idx, ds, text_len, mel_len, dscores,
                        (long)ldd, (char*)plane, (long)ld_plane, B, T1, T2, T2p);
@@ -992,6 +1006,9 @@ extern "C" int efts_attn_bwd(const float* scores, int64_t ld, const float* soft_
 extern "C" int efts_embed_bwd(const int64_t* ids, const float* g, float* dtable, int32_t B, int32_t T, int32_t Tp, int32_t c, int32_t num_symbols,
                               void* stream) {
     if (!ids || !g || !dtable) return efts_fail(EFTS_EINVAL, "efts_embed_bwd: null pointer");
+    if (B <= 0 || T <= 0 || Tp < T || c <= 0 || num_symbols <= 0)
+        return efts_fail(EFTS_ESHAPE, "efts_embed_bwd: B, T, c, num_symbols must be positive and Tp >= T (got B %d, T %d, Tp %d, c %d, num_symbols %d)", B, T, Tp, c,
+                         num_symbols);
     hipLaunchKernelGGL(embed_bwd_kernel, dim3(B * Tp), dim3(256), 0, ST, (const long*)ids, g, dtable, T, Tp, c, num_symbols);
     return efts_check_launch("efts_embed_bwd");
 }

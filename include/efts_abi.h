@@ -595,18 +595,27 @@ int efts_layernorm_bwd(const float* x, const float* gamma, const float* beta, fl
                        const float* ddur, const float* w, const float* rowmask, float* dz, void* plane,
                        int64_t ld_plane, int32_t split, float* dgamma, float* dbeta, float* dbias, float* dw, float* db,
                        int32_t rows, int32_t c, float drop_p, uint32_t drop_seed, const uint32_t* drop_seed_add, void* stream);
-/* alignment block backward (efficient_tts.py:287-398 under autograd): */
+/* alignment block backward (efficient_tts.py:287-398 under autograd).  Every entry point refuses non-positive B, T1, T2 with
+ * EFTS_ESHAPE before any launch.
+ * efts_alpha_bwd: r_ws[b][j] = sum_i alpha'_ij dalpha_ij, de[b][i] (0 at i >= text_len).  ralpha is the masked alpha' of the forward
+ *   (0 outside text x mel); dalpha must be finite there (the caller's product with the masked dH leaves 0). */
 int efts_alpha_bwd(const float* ralpha, const float* dalpha, const float* e, const int32_t* text_len,
                    const int32_t* mel_len, float sigma, float* r_ws /* [B*T2] */, float* de, int32_t B, int32_t T1,
                    int32_t T2, void* stream);
+/* efts_e_bwd: dpi[b][j] (0 at j >= mel_len).  One item's e, de and softmax statistics live in 4 * T1 floats of LDS: EFTS_ESHAPE when they
+ *   exceed the 64 KiB of the launch (T1 > 4096). */
 int efts_e_bwd(const float* imv, const float* e, const float* de, const int32_t* text_len, const int32_t* mel_len,
                float sigma_e, float* stats_ws /* [2*B*T1] */, float* dpi, int32_t B, int32_t T1, int32_t T2,
                void* stream);
 int efts_imv_bwd(const float* soft_idx, const float* imv, const float* dpi, const int32_t* text_len,
                  const int32_t* mel_len, float* dsoft_idx, int32_t B, int32_t T2, void* stream);
+/* efts_attn_bwd: dscores [B*T2][ldd] (columns < T1) and its bf16x3 A plane, rows (b*T2p + j), K = i padded with zeros to a multiple of 32.
+ *   EFTS_ESHAPE for ld < T1, ldd < T1, T2p < T2 or ld_plane < ceil(T1 / 32) * 128. */
 int efts_attn_bwd(const float* scores, int64_t ld, const float* soft_idx, const float* dsoft_idx,
                   const int32_t* text_len, const int32_t* mel_len, float* dscores, int64_t ldd, void* plane,
                   int64_t ld_plane, int32_t B, int32_t T1, int32_t T2, int32_t T2p, void* stream);
+/* efts_embed_bwd: dtable[ids[b][t]] += g[b*Tp + t] for t < T (ids [B][T] contiguous, g in the padded row space; ids clamped to the table).
+ *   EFTS_ESHAPE for non-positive B, T, c, num_symbols or Tp < T. */
 int efts_embed_bwd(const int64_t* ids, const float* g, float* dtable, int32_t B, int32_t T, int32_t Tp, int32_t c,
                    int32_t num_symbols, void* stream);
 /* clip_grad_norm_ + torch.optim.Adam(amsgrad=True, coupled weight decay) on flat fp32 buffers
