@@ -10,6 +10,8 @@ HiFi-GAN V1 generator (efficient_tts_amd.vocoder).  Differences from the referen
   * the vocoder weights are named explicitly (`--vocoder_config`, `--vocoder_checkpoint`): the reference hard-codes
     a checkpoint that is not part of its repository; without one the generator runs with random weights and says so
     (useful for smoke tests and timing only), `--no_vocoder` writes the mel-spectrograms as .npy instead;
+  * `--vocoder griffinlim [--gl_iters N]` replaces the generator by Griffin-Lim phase reconstruction on the device
+    (efficient_tts_amd.griffinlim): no vocoder checkpoint is read, the audio is intelligible but not HiFi-GAN quality;
   * `--batch_size N` synthesises N utterances per call with `inference_batch` (each item equals its B = 1 result);
   * every line of the list is processed (the reference stops after 10), alignment plots are not drawn;
   * RTF is reported as the reference does (wall time of model + vocoder over audio duration), synchronised per call;
@@ -30,6 +32,7 @@ import torch
 import yaml
 
 from efficient_tts_amd import models
+from efficient_tts_amd.griffinlim import GriffinLimVocoder
 from efficient_tts_amd.vocoder import HiFiGANGenerator, load_hifigan_generator
 
 _V1 = dict(resblock="1", upsample_rates=[8, 8, 2, 2], upsample_kernel_sizes=[16, 16, 4, 4], upsample_initial_channel=512,
@@ -45,6 +48,9 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--config", type=str, default=None, help="training config.yml (default: next to the checkpoint)")
     p.add_argument("--vocoder_config", type=str, default=None, help="HiFi-GAN config.json (default: the V1 LJSpeech configuration)")
     p.add_argument("--vocoder_checkpoint", type=str, default=None, help='HiFi-GAN checkpoint with a "generator" state_dict')
+    p.add_argument("--vocoder", type=str, default="hifigan", choices=["hifigan", "griffinlim"],
+                   help="hifigan (default): the HiFi-GAN V1 generator; griffinlim: phase reconstruction on the device, needs no vocoder checkpoint")
+    p.add_argument("--gl_iters", type=int, default=32, help="Griffin-Lim iterations (--vocoder griffinlim; default 32)")
     p.add_argument("--no_vocoder", action="store_true", help="write <id>_<step>.npy mel-spectrograms instead of wav files")
     p.add_argument("--batch_size", type=int, default=1, help="utterances per acoustic-model call (default 1, as the reference)")
     p.add_argument("--precision", type=str, default="bf16x3", choices=["bf16x3", "bf16", "fp32"],
@@ -114,7 +120,9 @@ def run_tts(args) -> float:
     model = model.to(device).eval()
     model.remove_weight_norm()
     vocoder = None
-    if not args.no_vocoder:
+    if not args.no_vocoder and args.vocoder == "griffinlim":
+        vocoder = GriffinLimVocoder(device, n_iter=args.gl_iters, precision="fp32" if args.precision == "fp32" else "bf16x3")
+    elif not args.no_vocoder:
         if args.vocoder_checkpoint:
             if not args.vocoder_config:
                 raise ValueError("--vocoder_checkpoint needs --vocoder_config")

@@ -1,0 +1,109 @@
+// efts_fft.h -- the fp32 1024-point FFT building blocks shared by the log-mel front-end (efts_frontend.hip) and the Griffin-Lim
+// vocoder (efts_griffinlim.hip): complex arithmetic on register pairs, 4- and 16-point DFTs in registers, the DPP exchange inside
+// a quad, the twiddle tables, and the whole transform of one wave (16 complex values per lane, one transpose through LDS).
+// Not part of the ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace efts {
+namespace fft {
+
+// a complex value = one register pair: +, - and the two halves of a complex product are single packed instructions (v_pk_add_f32 /
+// v_pk_mul_f32 / v_pk_fma_f32 with op_sel picking the halves).  With a plain struct of two floats the vectoriser paired unrelated scalars
+// and spent a fifth of the loop on v_mov to assemble the pairs.
+typedef float cf __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ cf cmul(cf a, cf b) { const cf bp = {-b.y, b.x}; return a.xx * b + a.yy * bp; }
+__device__ __forceinline__ cf mul_mi(cf a) { const cf r = {a.y, -a.x}; return r; }                 // a * (-i)
+
+// forward 4-point DFT in place (W4 = -i)
+__device__ __forceinline__ void dft4(cf& a, cf& b, cf& c, cf& d) {
+    const cf t0 = a + c, t1 = a - c, t2 = b + d, t3 = mul_mi(b - d);
+    a = t0 + t2; b = t1 + t3; c = t0 - t2; d = t1 - t3;
+}
+
+// forward 16-point DFT in place, natural order in and out: n = 4 a + b, k = c + 4 d
+__device__ __forceinline__ void dft16(cf* v) {
+    constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f, H = 0.70710678118654752f;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) dft4(v[b], v[4 + b], v[8 + b], v[12 + b]);          // over a: v[4 c + b] = y_b[c]
+    // y_b[c] *= W16^(b c)
+    v[4 + 1] = cmul(v[4 + 1], cf{C1, -S1});  v[4 + 2] = cmul(v[4 + 2], cf{H, -H});     v[4 + 3] = cmul(v[4 + 3], cf{S1, -C1});
+    v[8 + 1] = cmul(v[8 + 1], cf{H, -H});    v[8 + 2] = mul_mi(v[8 + 2]);            v[8 + 3] = cmul(v[8 + 3], cf{-H, -H});
+    v[12 + 1] = cmul(v[12 + 1], cf{S1, -C1}); v[12 + 2] = cmul(v[12 + 2], cf{-H, -H}); v[12 + 3] = cmul(v[12 + 3], cf{-C1, S1});
+#pragma unroll
+    for (int c = 0; c < 4; ++c) dft4(v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]);   // over b: v[4 c + d] = X[c + 4 d]
+    // to natural order: X[k] sits at v[4 (k & 3) + (k >> 2)] -- a 4 x 4 transpose of the register names
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int d = c + 1; d < 4; ++d) { const cf t = v[4 * c + d]; v[4 * c + d] = v[4 * d + c]; v[4 * d + c] = t; }
+}
+
+template <int CTRL>
+__device__ __forceinline__ cf quad(cf a) {       // the value of the quad's lane selected by the DPP quad_perm control
+    cf r;
+    r.x = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a.x), CTRL, 0xf, 0xf, false));
+    r.y = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a.y), CTRL, 0xf, 0xf, false));
+    return r;
+}
+
+// The twiddle tables of the 1024 = 16 x (16 x 4) transform, filled by the whole block of NTHREADS threads (the caller puts a barrier behind it):
+// tw1s[k - 1][n2] = W1024^(n2 k), k = 1 .. 15; tw2s[q][s] = W64^(q s).  UNIT: every W1024 factor 1 (an ablation switch of the front-end).
+constexpr int PITCH = 68;                       // complex values per row of a wave's transpose buffer [16][PITCH]
+template <int NTHREADS, bool UNIT = false>
+__device__ __forceinline__ void fill_twiddles(cf (*tw1s)[64], cf (*tw2s)[16]) {
+    for (int i = threadIdx.x; i < 15 * 64; i += NTHREADS) {
+        const int k = i / 64 + 1, n2 = i & 63;
+        float sn, cs;
+        if (UNIT) { sn = 0.f; cs = 1.f; } else sincospif(-(float)((n2 * k) & 1023) / 512.f, &sn, &cs);
+        tw1s[k - 1][n2] = cf{cs, sn};
+    }
+    if (threadIdx.x < 64) {
+        const int qq = threadIdx.x >> 4, ss = threadIdx.x & 15;
+        float sn, cs;
+        sincospif(-(float)((qq * ss) & 63) / 32.f, &sn, &cs);
+        tw2s[qq][ss] = cf{cs, sn};
+    }
+}
+
+// where bin f of a finished transform lies in the wave's buffer (the four lanes of a quad hold the same k1: without the shift
+// their stores meet in the same banks)
+__device__ __forceinline__ int bin_slot(int f) { return f + 4 * (f >> 8); }
+
+// Forward 1024-point FFT of one wave.  In: v[n1] = z[64 n1 + lane], n1 = 0 .. 15.  Out: Z[f] at zw[bin_slot(f)], all LDS traffic of
+// the wave retired.  zw: the wave's own [16][PITCH] buffer (nobody else reads or writes it; v is clobbered).
+//   n = 64 n1 + n2, k = k1 + 16 k2:  X[k] = sum_n2 W1024^(n2 k1) W64^(n2 k2) [sum_n1 z[64 n1 + n2] W16^(n1 k1)]
+//   (1) 16-point DFT over n1 in registers, twiddles W1024^(n2 k1); (2) transpose through LDS; (3) lane (k1, q) holds n2 = 4 r + q:
+//   16-point DFT over r, twiddles W64^(q s), the last radix 4 across the four lanes of a quad; (4) natural order through LDS.
+__device__ __forceinline__ void fft1024(cf (&v)[16], cf* zw, const cf (*tw1s)[64], const cf (*tw2s)[16], int lane) {
+    const int k1 = lane >> 2, q = lane & 3;
+    const float s1 = (q & 2) ? -1.f : 1.f, s2 = (q & 1) ? -1.f : 1.f;     // signs of the quad radix-4: r = partner + s * own
+    dft16(v);
+#pragma unroll
+    for (int k = 1; k < 16; ++k) v[k] = cmul(v[k], tw1s[k - 1][lane]);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) zw[k * PITCH + lane] = v[k];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int r = 0; r < 16; ++r) v[r] = zw[k1 * PITCH + 4 * r + q];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    dft16(v);
+#pragma unroll
+    for (int s = 1; s < 16; ++s) v[s] = cmul(v[s], tw2s[q][s]);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        cf c = v[s];
+        const cf p = quad<0x4E>(c);                             // quad_perm [2, 3, 0, 1]
+        c = c * s1 + p;                                          // q0: x0 + x2, q1: x1 + x3, q2: x0 - x2, q3: x1 - x3
+        if (q == 3) c = mul_mi(c);
+        const cf p2 = quad<0xB1>(c);                            // quad_perm [1, 0, 3, 2]
+        v[s] = c * s2 + p2;                                      // q0: X0, q1: X2, q2: X1, q3: X3
+    }
+    const int u = ((q & 1) << 1) | (q >> 1);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) zw[k1 + 16 * s + 260 * u] = v[s];        // f = k1 + 16 s + 256 u at bin_slot(f)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+}  // namespace fft
+}  // namespace efts

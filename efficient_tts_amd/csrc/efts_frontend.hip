@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "efts_internal.h"
+#include "efts_fft.h"
 
 namespace efts {
 
@@ -306,48 +307,7 @@ __global__ __launch_bounds__(64 * LM_WAVES) void logmel_dit_fast_kernel(const fl
 //       filter m and m + 64 per lane), log, store.
 // fp32 throughout (the MFMA pipeline carried 16 mantissa bits).  meldataset.py:49-82, taco2_data.py:66-76, :122-139.
 // ----------------------------------------------------------------------------------------------------------------------------
-namespace fft {
-
-// a complex value = one register pair: +, - and the two halves of a complex product are single packed instructions (v_pk_add_f32 /
-// v_pk_mul_f32 / v_pk_fma_f32 with op_sel picking the halves).  With a plain struct of two floats the vectoriser paired unrelated scalars
-// and spent a fifth of the loop on v_mov to assemble the pairs.
-typedef float cf __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ cf cmul(cf a, cf b) { const cf bp = {-b.y, b.x}; return a.xx * b + a.yy * bp; }
-__device__ __forceinline__ cf mul_mi(cf a) { const cf r = {a.y, -a.x}; return r; }                 // a * (-i)
-
-// forward 4-point DFT in place (W4 = -i)
-__device__ __forceinline__ void dft4(cf& a, cf& b, cf& c, cf& d) {
-    const cf t0 = a + c, t1 = a - c, t2 = b + d, t3 = mul_mi(b - d);
-    a = t0 + t2; b = t1 + t3; c = t0 - t2; d = t1 - t3;
-}
-
-// forward 16-point DFT in place, natural order in and out: n = 4 a + b, k = c + 4 d
-__device__ __forceinline__ void dft16(cf* v) {
-    constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f, H = 0.70710678118654752f;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) dft4(v[b], v[4 + b], v[8 + b], v[12 + b]);          // over a: v[4 c + b] = y_b[c]
-    // y_b[c] *= W16^(b c)
-    v[4 + 1] = cmul(v[4 + 1], cf{C1, -S1});  v[4 + 2] = cmul(v[4 + 2], cf{H, -H});     v[4 + 3] = cmul(v[4 + 3], cf{S1, -C1});
-    v[8 + 1] = cmul(v[8 + 1], cf{H, -H});    v[8 + 2] = mul_mi(v[8 + 2]);            v[8 + 3] = cmul(v[8 + 3], cf{-H, -H});
-    v[12 + 1] = cmul(v[12 + 1], cf{S1, -C1}); v[12 + 2] = cmul(v[12 + 2], cf{-H, -H}); v[12 + 3] = cmul(v[12 + 3], cf{-C1, S1});
-#pragma unroll
-    for (int c = 0; c < 4; ++c) dft4(v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]);   // over b: v[4 c + d] = X[c + 4 d]
-    // to natural order: X[k] sits at v[4 (k & 3) + (k >> 2)] -- a 4 x 4 transpose of the register names
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int d = c + 1; d < 4; ++d) { const cf t = v[4 * c + d]; v[4 * c + d] = v[4 * d + c]; v[4 * d + c] = t; }
-}
-
-template <int CTRL>
-__device__ __forceinline__ cf quad(cf a) {       // the value of the quad's lane selected by the DPP quad_perm control
-    cf r;
-    r.x = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a.x), CTRL, 0xf, 0xf, false));
-    r.y = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a.y), CTRL, 0xf, 0xf, false));
-    return r;
-}
-
-}  // namespace fft
+// (cmul, dft4, dft16, the DPP quad exchange and the twiddle tables: efts_fft.h, shared with the Griffin-Lim vocoder)
 
 #ifndef FF_ABL
 #define FF_ABL 0
@@ -370,18 +330,7 @@ __global__ __launch_bounds__(64 * FF_WAVES, 3) void logmel_fft_kernel(const SAMP
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     cf* zw = zs[wave];
     // ---- per block (a block works through many frame pairs): twiddle tables, filterbank
-    for (int i = threadIdx.x; i < 15 * 64; i += 64 * FF_WAVES) {
-        const int k = i / 64 + 1, n2 = i & 63;
-        float sn, cs;
-        if (FF_ABL & 64) { sn = 0.f; cs = 1.f; } else sincospif(-(float)((n2 * k) & 1023) / 512.f, &sn, &cs);
-        tw1s[k - 1][n2] = cf{cs, sn};
-    }
-    if (threadIdx.x < 64) {
-        const int qq = threadIdx.x >> 4, ss = threadIdx.x & 15;
-        float sn, cs;
-        sincospif(-(float)((qq * ss) & 63) / 32.f, &sn, &cs);
-        tw2s[qq][ss] = cf{cs, sn};
-    }
+    fill_twiddles<64 * FF_WAVES, (FF_ABL & 64) != 0>(tw1s, tw2s);
     // span of a filter in cb: filters below FF_WIDE run on one lane, the others on four (a quarter each); all spans of a kind have the length of
     // the widest one (w0 / w1 4-tap steps, per lane), shorter ones are padded with zero weights -- so offsets are closed-form and a lane may run
     // its own number of steps or the common one

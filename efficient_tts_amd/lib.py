@@ -175,6 +175,11 @@ _SIGS = {
     "efts_logmel_fft_pcm16": (i32, [vp, i64, f32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     # vocoder
     "efts_mean_act_rows": (i32, [vp, vp, vp, i64, f32, f32, vp, i64, vp, i64, i32, i32, i32, vp]),
+    # Griffin-Lim vocoder
+    "efts_gl_init": (i32, [vp, vp, vp, i32, i32, i32, C.c_uint32, vp]),
+    "efts_gl_synthesis": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "efts_gl_analysis": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, f32, i32, i32, i32, i32, vp]),
+    "efts_gl_overlap_add": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -195,7 +200,10 @@ def load() -> C.CDLL:
             "Build it with `python -m efficient_tts_amd.build` (needs hipcc, gfx950).")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in _SIGS.items():
-        fn = getattr(lib, name)          # AttributeError if the symbol is not exported
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:           # an older build of the same revision (exports are added without a bump)
+            raise EftsError(f"{LIB_PATH} does not export {name}: rebuild with `python -m efficient_tts_amd.build --force`.") from None
         fn.restype, fn.argtypes = res, args
     have = lib.efts_version()
     if have != ABI_VERSION:

@@ -76,7 +76,10 @@ extern "C" {
  *   600  round 6: + efts_frame_pack_dit, efts_logmel_dit; efts_pack_item.plane may be NULL (dgrad plane only)
  *   601  round 6: efts_gemm_args grew by sqerr_target / ld_target / target_batch_stride / sqerr_part;
  *        + efts_losses_from_parts, efts_logmel_fft, efts_logmel_fft_pcm16
- *   602  (this header): operand format 3 (EFTS_SPLIT_FP32); efts_reconst_alpha and efts_pack_vt take the format of their plane */
+ *   602  (this header): operand format 3 (EFTS_SPLIT_FP32); efts_reconst_alpha and efts_pack_vt take the format of their plane
+ *        + efts_gl_init, efts_gl_synthesis, efts_gl_analysis, efts_gl_overlap_add (Griffin-Lim vocoder): exports added, nothing that existed
+ *        changed size or meaning, so by the rule above the revision stays (a binding that needs them and meets an older library fails on the
+ *        missing symbol) */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -702,6 +705,38 @@ int efts_logmel_fft_pcm16(const int16_t* audio, int64_t ld_audio, float pcm_scal
  * ---------------------------------------------------------------------------------- */
 int efts_mean_act_rows(const float* a, const float* b, const float* c3, int64_t ld, float scale, float slope, float* out,
                        int64_t ldo, void* plane, int64_t ld_plane, int32_t split, int32_t rows, int32_t c, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Griffin-Lim vocoder (Griffin & Lim 1984, momentum of Perraudin et al. 2013) for the analysis configuration of efts_logmel_fft:
+ * n_fft 1024, hop 256, periodic Hann `window` [1024], 384 samples of padding per side, frames not centred -- frame t starts at
+ * padded sample 256 t, and T frames describe a padded signal y_pad of 256 T + 768 samples.  fp32 throughout, the transforms as the
+ * front-end's register / LDS FFT (two real frames per complex transform).
+ *   spec, spec_prev, spec_out : [B][T][513] complex (re, im interleaved), 8-byte aligned (EFTS_EALIGN otherwise)
+ *   mag                       : [B][T][513] target magnitudes
+ *   wframes                   : [B][T][1024] windowed time frames
+ *   frames                    : [B] frame counts (clamped to 0 .. T); frames at or beyond an item's count are neither read nor
+ *                               written and add nothing to the overlap-add or to the window sum
+ * efts_gl_init        : spec = mag e^(i phi), spec_prev = 0.  mode 0: phi = 0; mode 1: phi = 2 pi u, u = (hash >> 8) / 2^24 with the
+ *                       counter-based hash of the Dropout masks over (seed, t * 513 + f) -- the same for every item of a batch.
+ * efts_gl_synthesis   : wframes[b][t] = window * irfft(spec[b][t]) (the imaginary parts of the DC and Nyquist bins are dropped).
+ * efts_gl_analysis    : y_pad[p] = (sum over the frames t' that cover p, oldest first, of wframes[b][t'][p - 256 t']) / max(sum of
+ *                       their window^2, 1e-8) -- a gather, never stored -- or, when `signal` is given instead of `wframes`,
+ *                       signal[b * ld_signal + p] (ld_signal >= 256 T + 768);  Y = rfft(window * y_pad[256 t ..]);
+ *                       C = Y + momentum (Y - spec_prev), spec_out = mag C / max(|C|, 1e-8), spec_prev = Y.
+ *                       mag = spec_prev = NULL: the plain analysis, spec_out = Y.  momentum in [0, 1).
+ * efts_gl_overlap_add : out[b * ld_out + s] = y_pad[start + s], s < n_out, zero at and beyond 256 frames[b] + 768 - 2 start samples
+ *                       (start 384, n_out 256 T: the audio the frames describe; start 0, n_out 256 T + 768: the padded signal).
+ * Two runs give the same bits (no atomics).  EFTS_EINVAL / EFTS_ESHAPE / EFTS_EALIGN before any launch; n_fft / hop other than 1024 / 256:
+ * EFTS_ESHAPE.
+ * ---------------------------------------------------------------------------------- */
+int efts_gl_init(const float* mag, float* spec, float* spec_prev, int32_t B, int32_t T, int32_t mode, uint32_t seed, void* stream);
+int efts_gl_synthesis(const float* spec, const int32_t* frames, const float* window, float* wframes, int32_t B, int32_t T,
+                      int32_t n_fft, int32_t hop, void* stream);
+int efts_gl_analysis(const float* wframes, const float* signal, int64_t ld_signal, const int32_t* frames, const float* window,
+                     const float* mag, float* spec_prev, float* spec_out, float momentum, int32_t B, int32_t T, int32_t n_fft,
+                     int32_t hop, void* stream);
+int efts_gl_overlap_add(const float* wframes, const int32_t* frames, const float* window, float* out, int64_t ld_out, int32_t start,
+                        int32_t n_out, int32_t B, int32_t T, int32_t n_fft, int32_t hop, void* stream);
 
 #ifdef __cplusplus
 }
