@@ -107,6 +107,16 @@ class WgradItem(C.Structure):
 
 WGRAD_MAX_ITEMS = 8
 
+OPTIM_ADAM, OPTIM_ADAMW, OPTIM_RADAM = 0, 1, 2      # EFTS_OPTIM_*
+
+
+class OptimArgs(C.Structure):
+    """mirror of `struct efts_optim_args` (include/efts_abi.h)"""
+    _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("vmax", vp), ("n", i64), ("sumsq", vp), ("max_norm", f32), ("gscale", f32),
+                ("algo", i32), ("amsgrad", i32), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("step", i32), ("reserved", i32), ("hyper", vp)]
+
+
 _SIGS = {
     "efts_version": (i32, []),
     "efts_last_error": (C.c_char_p, []),
@@ -166,6 +176,8 @@ _SIGS = {
     "efts_adam_hyper": (i32, [f32, f32, f32, i32, C.POINTER(f32)]),
     "efts_adam_amsgrad_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, f32, f32, vp, f32, f32, f32, f32, vp]),
     "efts_store_words": (i32, [vp, C.POINTER(C.c_uint32), i32, vp]),
+    "efts_optim_step": (i32, [C.POINTER(OptimArgs), vp]),
+    "efts_optim_hyper": (i32, [i32, C.c_double, C.c_double, C.c_double, C.c_double, i32, C.POINTER(f32)]),
     # log-mel front-end
     "efts_frame_pack": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
     "efts_logmel": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

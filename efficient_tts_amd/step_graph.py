@@ -1,11 +1,12 @@
-"""One optimisation step -- forward, backward, clip, Adam-amsgrad (nntts/trainers/efficient_tts_trainer.py:139-160) -- captured once per
+"""One optimisation step -- forward, backward, clip, optimizer update (nntts/trainers/efficient_tts_trainer.py:139-160) -- captured once per
 batch shape and replayed as ONE hipGraph.
 
 Why: the step is ~190 launches.  Issued eagerly the host needs 1.9 ms for them on an idle box against 3.6 ms of device time, but
 4.5-5.7 ms on a loaded host (observed on the measurement pool), where the HOST then sets the step time.  A replay costs the host a
 few tens of microseconds.  What changes from step to step lives in device memory, refreshed by one tiny stream-ordered launch in
-front of every replay (efts_store_words): the learning rate and Adam's two bias corrections (efts_adam_amsgrad_dev) and the step
-word of the duration predictor's Dropout seeds (`drop_seed_add` of efts_layernorm_rows / _dot / _bwd).  Parameters, optimizer
+front of every replay (efts_store_words): the learning rate and Adam's two bias corrections (efts_adam_amsgrad_dev; words 0-2), the step
+word of the duration predictor's Dropout seeds (`drop_seed_add` of efts_layernorm_rows / _dot / _bwd; word 3), and the four words of
+the other fused optimizers (efts_optim_step `hyper`: Adam without amsgrad, AdamW, RAdam; words 4-7, 16-byte aligned).  Parameters, optimizer
 state and every result are bit-identical to the eager loop's (tests/test_gpu_train.py).
 
 Data parallel (round 4): `GraphedStep(DistributedEFTS(model), ...)` captures the three bucket collectives too.  The reducer issues
@@ -15,7 +16,7 @@ a replay contains forward, backward, the RCCL exchanges overlapped with the back
 one launch per step instead of ~190.
 
 Not captured (the step then runs eagerly, same results): conv / prenet Dropout (dropout_rate > 0: their seeds are by-value launch
-arguments), optimizers other than EftsAdam."""
+arguments), optimizers other than the fused ones (optim.FlatOptimizer)."""
 from __future__ import annotations
 
 import logging
@@ -27,7 +28,7 @@ from . import ops as O
 from . import train as T
 from .autograd import engine_of
 from .model import LazyStats
-from .optim import EftsAdam
+from .optim import FlatOptimizer
 
 
 class GraphedStep:
@@ -47,7 +48,7 @@ class GraphedStep:
     def _eligible(self) -> bool:
         m = self.model
         conv_dropout = m.training and float(getattr(m, "dropout_rate", 0.0)) >= 1e-5
-        return isinstance(self.opt, EftsAdam) and hasattr(m, "planes") and not conv_dropout and not torch.cuda.is_current_stream_capturing()
+        return isinstance(self.opt, FlatOptimizer) and hasattr(m, "planes") and not conv_dropout and not torch.cuda.is_current_stream_capturing()
 
     def inputs(self, text, text_lengths, speech, speech_lengths):
         """The device tensors a captured step of this shape reads (text, text_lengths int32, speech, speech_lengths int32), or None before
@@ -68,14 +69,17 @@ class GraphedStep:
         """what a captured step is valid for: the buffers its launches point at and every argument they carry by value"""
         m, g = self.model, self.opt.param_groups[0]
         red = self.ddp.reducer if self.ddp is not None else None
-        return (ws.serial, id(eng), m.planes.tag(), float(self.opt.grad_norm), self.grad_scale, tuple(g["betas"]), float(g["eps"]),
+        return (ws.serial, id(eng), m.planes.tag(), self.opt.ALGO, self.opt.amsgrad, float(self.opt.grad_norm), self.grad_scale, tuple(g["betas"]), float(g["eps"]),
                 float(g["weight_decay"]), bool(m.training), id(red), None if red is None else red.algo, eng.bucket_hook is not None,
                 m.opt.tag(), T.switch_tag())
 
     def _refresh(self, eng) -> None:
-        """the words of the step about to run: Adam's scalars for step t + 1 and the Dropout step word of call dropout_calls + 1"""
+        """the words of the step about to run: the optimizer's scalars for step t + 1 and the Dropout step word of call dropout_calls + 1"""
         m = self.model
-        O.store_words(self.words, self.opt.hyper_words(self.opt.t + 1) + [2 * (int(getattr(m, "dropout_calls", 0)) + 1)])
+        words, hw, w0 = [0] * 8, self.opt.hyper_words(self.opt.t + 1), self.opt.hyper_word0
+        words[w0:w0 + len(hw)] = hw
+        words[3] = 2 * (int(getattr(m, "dropout_calls", 0)) + 1)
+        O.store_words(self.words, words)
 
     def __call__(self, text, text_lengths, speech, speech_lengths):
         m = self.model
@@ -118,7 +122,7 @@ class GraphedStep:
                             out3, _ = eng.forward_backward(*ent["static"])
                             if eng.join_reduce is not None:           # data parallel: the optimizer waits for the last bucket
                                 eng.join_reduce()
-                            self.opt.launch(self.grad_scale, hyper_ptr=self.words.data_ptr())
+                            self.opt.launch(self.grad_scale, hyper_ptr=self.words.data_ptr() + 4 * self.opt.hyper_word0)
                 except Exception as exc:                              # noqa: BLE001
                     logging.warning("hipGraph capture of the training step failed (%s): this shape stays on eager launches", exc)
                     ent["eager_only"] = True

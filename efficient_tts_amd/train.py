@@ -110,8 +110,10 @@ class TrainEngine:
         self.layout = grad_layout(model)
         self.named = list(model.named_parameters())     # model.parameters() order (what autograd's Function receives)
         self.params = tuple(p for _, p in self.named)
-        self.step_words = None                          # device uint32[4] {lr, 1 - b1^t, sqrt(1 - b2^t) as float bits, 2 * dropout step}: set while
-                                                        # a step is captured / replayed as a hipGraph (step_graph.GraphedStep)
+        self.step_words = None                          # device uint32[8], set while a step is captured / replayed as a hipGraph
+                                                        # (step_graph.GraphedStep).  This engine reads word 3 alone, 2 * dropout step; the rest are
+                                                        # the optimizer's float bits: words 0-2 {lr, 1 - b1^t, sqrt(1 - b2^t)} of efts_adam_amsgrad_dev,
+                                                        # words 4-7 those of efts_optim_hyper, whichever kernel the optimizer runs (the others stay 0)
         self.step_params = None                         # tuple(model.parameters()) of the running step (autograd.py), saves re-walks
         self.dev = next(model.parameters()).device
         self.numel = sum(p.numel() for _, p in self.layout)

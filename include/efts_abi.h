@@ -79,7 +79,8 @@ extern "C" {
  *   602  (this header): operand format 3 (EFTS_SPLIT_FP32); efts_reconst_alpha and efts_pack_vt take the format of their plane
  *        + efts_gl_init, efts_gl_synthesis, efts_gl_analysis, efts_gl_overlap_add (Griffin-Lim vocoder): exports added, nothing that existed
  *        changed size or meaning, so by the rule above the revision stays (a binding that needs them and meets an older library fails on the
- *        missing symbol) */
+ *        missing symbol)
+ *        + efts_optim_step, efts_optim_hyper (Adam / AdamW / RAdam): exports added, the revision stays by the same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -643,6 +644,46 @@ int efts_adam_amsgrad_dev(float* p, const float* g, float* m, float* v, float* v
                           float max_norm, float gscale, const float* hyper, float beta1, float beta2, float eps,
                           float weight_decay, void* stream);
 int efts_store_words(uint32_t* dst /* device */, const uint32_t* words /* host */, int32_t n, void* stream);
+
+/* The rest of the Adam family behind the reference's optimizer registry (nntts/optimizers/__init__.py: torch.optim + radam.py), same
+ * flat buffers and the same clip -- coef = gscale * min(1, max_norm / (gscale*sqrt(sumsq) + 1e-6)), gg = coef * g -- in ONE launch:
+ *   EFTS_OPTIM_ADAM   torch.optim.Adam : gg += wd p;  m = b1 m + (1-b1) gg;  v = b2 v + (1-b2) gg^2;  vh = amsgrad ? (vmax = max(vmax, v)) : v;
+ *                                        p -= lr / (1 - b1^t) * m / (sqrt(vh) / sqrt(1 - b2^t) + eps)
+ *   EFTS_OPTIM_ADAMW  torch.optim.AdamW: p *= 1 - lr wd first, no wd in gg, the rest as ADAM
+ *   EFTS_OPTIM_RADAM  nntts/optimizers/radam.py (NOT torch.optim.RAdam: threshold, eps placement and decay differ):
+ *                                        v, m from gg;  p *= 1 - wd lr;  N = N_max - 2 t b2^t / (1 - b2^t), N_max = 2 / (1 - b2) - 1;
+ *                                        N >= 5: p -= lr s m / (sqrt(v) + eps), s = sqrt((1 - b2^t)(N - 4)/(N_max - 4) (N - 2)/N N_max/(N_max - 2)) / (1 - b1^t)
+ *                                        else  : p -= lr m / (1 - b1^t).  No amsgrad form.
+ * Elementwise fp32; everything that depends on the step number or the learning rate is four words computed on the host in double,
+ *   ADAM / ADAMW {lr / (1 - b1^t), sqrt(1 - b2^t), 1 (ADAM) or 1 - lr wd (ADAMW), 0}      RADAM {lr s, 1, 1 - wd lr, N >= 5 ? 1 : 0}
+ * taken from lr / step by value, or, with hyper != NULL, read from DEVICE memory (lr and step are then ignored): efts_optim_hyper
+ * returns exactly the words the by-value path derives, so a hipGraph replay and an eager step give the same bits (as efts_adam_hyper
+ * for efts_adam_amsgrad_dev).  The scalars are doubles so that (float)(1 - beta) is rounded once, as torch's fp32 kernels receive it.
+ * amsgrad == 0: vmax is neither read nor written (may be NULL).  Two runs give the same bits (no atomics).
+ * EFTS_EINVAL: NULL p / g / m / v / out4, vmax NULL with amsgrad, n <= 0, step < 1 (by value), unknown algo, RADAM with amsgrad, a beta outside
+ * [0, 1).  EFTS_EALIGN: p, g, m, v, vmax not 16-byte aligned. */
+#define EFTS_OPTIM_ADAM 0
+#define EFTS_OPTIM_ADAMW 1
+#define EFTS_OPTIM_RADAM 2
+typedef struct efts_optim_args {
+    float* p;               /* [n] parameters, updated in place */
+    const float* g;         /* [n] gradients */
+    float* m;               /* [n] exp_avg */
+    float* v;               /* [n] exp_avg_sq */
+    float* vmax;            /* [n] max_exp_avg_sq, amsgrad only (NULL otherwise) */
+    int64_t n;
+    const float* sumsq;     /* device: sum(g^2) (efts_sumsq), or NULL: no clip */
+    float max_norm;         /* <= 0: no clip */
+    float gscale;
+    int32_t algo;           /* EFTS_OPTIM_* */
+    int32_t amsgrad;
+    double lr, beta1, beta2, eps, weight_decay;
+    int32_t step;           /* >= 1; by-value path only */
+    int32_t reserved;
+    const float* hyper;     /* device: the four words of efts_optim_hyper, or NULL: derive them from lr / step */
+} efts_optim_args;
+int efts_optim_step(const efts_optim_args* a, void* stream);
+int efts_optim_hyper(int32_t algo, double lr, double beta1, double beta2, double weight_decay, int32_t step, float* out4 /* host */);
 
 /* ------------------------------------------------------------------------------------
  * Log-mel front-end: the data format right before the path.
