@@ -16,7 +16,9 @@ HiFi-GAN V1 generator (efficient_tts_amd.vocoder).  Differences from the referen
   * every line of the list is processed (the reference stops after 10), alignment plots are not drawn;
   * RTF is reported as the reference does (wall time of model + vocoder over audio duration), synchronised per call;
   * `--length_scale S` multiplies every predicted duration (> 1: slower speech), `--write_durations` writes the frames per
-    phoneme next to each output (<id>_<step>.durations.txt: index, phoneme, start frame, frames, start time in seconds).
+    phoneme next to each output (<id>_<step>.durations.txt: index, phoneme, start frame, frames, start time in seconds);
+  * `--sampling_rate R [--resample_quality best|fast]` writes the wav files at R Hz instead of the vocoder's 22 050 Hz: the vocoder's
+    output is converted on the device (efficient_tts_amd.resample) in front of the 16-bit quantisation.
 """
 from __future__ import annotations
 
@@ -33,6 +35,7 @@ import yaml
 
 from efficient_tts_amd import models
 from efficient_tts_amd.griffinlim import GriffinLimVocoder
+from efficient_tts_amd.resample import QUALITIES, Resampler
 from efficient_tts_amd.vocoder import HiFiGANGenerator, load_hifigan_generator
 
 _V1 = dict(resblock="1", upsample_rates=[8, 8, 2, 2], upsample_kernel_sizes=[16, 16, 4, 4], upsample_initial_channel=512,
@@ -58,6 +61,9 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--length_scale", type=float, default=1.0, help="multiplies every predicted duration (default 1.0; > 1: slower speech)")
     p.add_argument("--write_durations", action="store_true",
                    help="also write <id>_<step>.durations.txt: token index, phoneme, start frame, frame count, start time in seconds")
+    p.add_argument("--sampling_rate", type=int, default=None,
+                   help=f"sampling rate of the written wav files in Hz (default: the vocoder's, {SAMPLING_RATE}); other rates are converted on the device")
+    p.add_argument("--resample_quality", type=str, default="best", choices=sorted(QUALITIES), help="filter of --sampling_rate (default best)")
     p.add_argument("--verbose", type=int, default=1)
     return p
 
@@ -75,10 +81,10 @@ def _read_list(path: str, phn2idx) -> List[Tuple[str, torch.Tensor]]:
     return items
 
 
-def _write_wav(path: str, samples: torch.Tensor) -> None:
+def _write_wav(path: str, samples: torch.Tensor, sampling_rate: int = SAMPLING_RATE) -> None:
     from scipy.io.wavfile import write
     pcm = (samples.clamp(-1.0, 1.0) * 32767.0).round().to(torch.int16).cpu().numpy()
-    write(path, SAMPLING_RATE, pcm)
+    write(path, sampling_rate, pcm)
 
 
 def _write_durations(path: str, phonemes: List[str], frames, hop: int, sampling_rate: int) -> None:
@@ -109,6 +115,9 @@ def run_tts(args) -> float:
     sampling_rate = int(config.get("sampling_rate", SAMPLING_RATE))
     if not args.length_scale > 0:
         raise ValueError("--length_scale must be > 0")
+    out_rate = SAMPLING_RATE if args.sampling_rate is None else int(args.sampling_rate)
+    if out_rate <= 0:
+        raise ValueError("--sampling_rate must be > 0")
     ctl = dict(length_scale=args.length_scale, return_durations=args.write_durations)
     items = _read_list(args.test_fid_scp, phn2idx)
     logging.info(f"{len(items)} utterances to synthesise")
@@ -131,6 +140,9 @@ def run_tts(args) -> float:
             logging.warning("no --vocoder_checkpoint: the HiFi-GAN generator runs with RANDOM weights (timing / smoke only)")
             vocoder = HiFiGANGenerator(_V1, precision=args.precision).to(device).eval()
             vocoder.remove_weight_norm()
+    resampler = None
+    if vocoder is not None and out_rate != SAMPLING_RATE:
+        resampler = Resampler(device, SAMPLING_RATE, out_rate, quality=args.resample_quality)
 
     total_rtf, done = 0.0, 0
     bs = max(1, int(args.batch_size))
@@ -156,9 +168,15 @@ def run_tts(args) -> float:
                 outs = mels
             elif len(chunk) == 1:
                 outs = [vocoder(mels[0].t()[None].contiguous())[0, 0]]
+                if resampler is not None:
+                    outs = [resampler(outs[0][None].float())[0][0]]
             else:                                       # one batched generator pass; every item equals its single-utterance result
                 audio = vocoder(mel.transpose(1, 2).contiguous(), mel_lens)
-                outs = [audio[n, 0, :int(mel_lens[n]) * 256] for n in range(len(chunk))]
+                if resampler is None:
+                    outs = [audio[n, 0, :int(mel_lens[n]) * 256] for n in range(len(chunk))]
+                else:                                   # ragged: every item is converted from its own samples only
+                    audio, audio_lens = resampler(audio[:, 0].float(), mel_lens.to(audio.device) * 256)
+                    outs = [audio[n, :int(audio_lens[n])] for n in range(len(chunk))]
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - start
         seconds = sum(m.shape[0] for m in mels) * 256 / SAMPLING_RATE
@@ -168,7 +186,7 @@ def run_tts(args) -> float:
             if vocoder is None:
                 np.save(os.path.join(args.outdir, f"{utt}_{step}.npy"), out.cpu().numpy())
             else:
-                _write_wav(os.path.join(args.outdir, f"{utt}_{step}.wav"), out)
+                _write_wav(os.path.join(args.outdir, f"{utt}_{step}.wav"), out, out_rate)
         if frames is not None:
             for (utt, ids1), fr in zip(chunk, frames):
                 _write_durations(os.path.join(args.outdir, f"{utt}_{step}.durations.txt"), [idx2phn[int(i)] for i in ids1],

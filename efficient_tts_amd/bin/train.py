@@ -31,6 +31,7 @@ import efficient_tts_amd as pkg
 from efficient_tts_amd import datasets, models, optimizers, schedulers, trainers
 from efficient_tts_amd.dist import DistributedEFTS
 from efficient_tts_amd.frontend import LogMelFrontend
+from efficient_tts_amd.resample import Resampler
 
 # (flags, kwargs) of the reference command line, kept as data so the parser and the docs cannot drift apart
 _CLI = (
@@ -129,7 +130,16 @@ def _build_trainer(config: Dict[str, Any], loaders, samplers, proc: _Process):
     trainer_class = getattr(trainers, config.get("trainer_type", "EfficientTTSTrainer"))
     trainer = trainer_class(steps=0, epochs=0, data_loader=loaders, sampler=samplers, model=model, optimizer=optimizer,
                             scheduler=scheduler, config=config, device=device)
-    trainer.frontend = LogMelFrontend(device, **(config.get("frontend_params") or {}))
+    front = config.get("frontend_params") or {}
+    trainer.frontend = LogMelFrontend(device, **front)
+    # a corpus at another rate than the front-end's is converted on the device, batch by batch (dataset_params.source_sampling_rate)
+    data = config.get("dataset_params") or {}
+    front_rate = int(front.get("sampling_rate", data.get("sampling_rate", 22050)))
+    source_rate = data.get("source_sampling_rate")
+    if source_rate is not None and int(source_rate) != front_rate:
+        trainer.resampler = Resampler(device, int(source_rate), front_rate, quality=config.get("resample_quality", "best"),
+                                      max_wav_value=float(front.get("max_wav_value", 32768.0)))
+        logging.info(f"resampling {source_rate} -> {front_rate} Hz on the device ({trainer.resampler.quality})")
     return trainer
 
 

@@ -29,18 +29,26 @@ def load_filepaths_and_text(filename: str, split: str = "|") -> List[List[str]]:
 class TextMelLoader(torch.utils.data.Dataset):
     """(phoneme ids, int16 waveform) pairs from an `audiopath|phoneme sequence` file list.
 
-    Same constructor arguments as the reference class (taco2_data.py:23-45).  Only the phoneme-sequence
+    Same constructor arguments as the reference class (taco2_data.py:23-45), plus `source_sampling_rate`: the rate the files are
+    recorded at when it is not `sampling_rate` (None: they must be at `sampling_rate`).  Only the phoneme-sequence
     input of the published recipe is supported (`use_phnseq: True` in egs/lj/conf/*.yaml); the grapheme
     path needs the reference's text cleaners (nntts/text), which are outside this package's scope."""
 
     def __init__(self, meta_file: str, text_cleaners: Sequence[str] = ("english_cleaners",), max_wav_value: float = 32768.0,
-                 sampling_rate: int = 22050, wav_path: str = "", use_phnseq: bool = False, phnset_path: Optional[str] = None):
+                 sampling_rate: int = 22050, wav_path: str = "", use_phnseq: bool = False, phnset_path: Optional[str] = None,
+                 source_sampling_rate: Optional[int] = None):
         if not use_phnseq:
             raise NotImplementedError("only use_phnseq=True (the egs/lj recipe) is supported: grapheme input needs nntts.text")
         if phnset_path is None:
             raise ValueError("Please provide phnset_path if want to use phone seq as input")
         self.audiopaths_and_text = load_filepaths_and_text(meta_file)
         self.max_wav_value, self.sampling_rate, self.wav_path = max_wav_value, sampling_rate, wav_path
+        # a corpus recorded at another rate (one rate per corpus): the files are yielded untouched, the trainer converts the padded batch
+        # on the device (efficient_tts_amd.resample.Resampler) in front of the log-mel front-end
+        if source_sampling_rate is not None and (isinstance(source_sampling_rate, bool) or not isinstance(source_sampling_rate, int)
+                                                 or source_sampling_rate <= 0):
+            raise ValueError(f"source_sampling_rate must be a positive integer (Hz), got {source_sampling_rate!r}")
+        self.source_sampling_rate = source_sampling_rate
         with open(phnset_path, "r") as f:
             phn_list = [l.strip() for l in f]
         self.phn2idx = dict(zip(phn_list, range(len(phn_list))))
@@ -53,7 +61,11 @@ class TextMelLoader(torch.utils.data.Dataset):
     def get_audio(self, filename: str) -> torch.Tensor:
         from scipy.io.wavfile import read
         sr, data = read(os.path.join(self.wav_path, filename.split("/")[-1]))
-        if sr != self.sampling_rate:
+        if self.source_sampling_rate is not None:
+            if sr != self.source_sampling_rate:
+                raise ValueError(f"{filename}: sampling rate {sr} != source_sampling_rate {self.source_sampling_rate} "
+                                 f"(converted to {self.sampling_rate} on the device)")
+        elif sr != self.sampling_rate:
             raise ValueError(f"{filename}: sampling rate {sr} != {self.sampling_rate}")
         if data.dtype != np.int16:
             raise ValueError(f"{filename}: expected 16-bit PCM")

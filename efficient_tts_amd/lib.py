@@ -192,6 +192,9 @@ _SIGS = {
     "efts_gl_synthesis": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "efts_gl_analysis": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, f32, i32, i32, i32, i32, vp]),
     "efts_gl_overlap_add": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
+    # sample-rate conversion
+    "efts_resample": (i32, [vp, i64, vp, vp, i32, i32, i32, vp, i64, vp, i32, vp]),
+    "efts_resample_pcm16": (i32, [vp, i64, f32, vp, vp, i32, i32, i32, vp, i64, vp, i32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -76,6 +76,7 @@ class EfficientTTSTrainer:
         self.config = config
         self.device = device
         self.frontend = None                   # optional LogMelFrontend (set by efficient_tts_amd.bin.train)
+        self.resampler = None                  # optional Resampler in front of it: corpus rate -> front-end rate (set by efficient_tts_amd.bin.train)
         self.finish_train = False
         self._tb = _TBWriter(config["outdir"]) if _TBWriter is not None else None
         self._bar = None
@@ -113,6 +114,9 @@ class EfficientTTSTrainer:
         text, text_lengths, third, third_lengths = (t.to(self.device) for t in batch)
         if self.frontend is None:
             return text, text_lengths, third, third_lengths
+        if self.resampler is not None:
+            # the padded int16 batch at the corpus' rate -> a padded fp32 batch at the front-end's rate, with the converted lengths
+            third, third_lengths = self.resampler(third, third_lengths)
         n_frames = int(self.frontend.frames_of(third_lengths).max())
         # default buckets: ragged LJSpeech batches otherwise bring a new (B, T1, T2) almost every step, and every new shape
         # allocates and zero-fills a multi-GB activation workspace (4 are cached); 0 in the YAML turns the padding off

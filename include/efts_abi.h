@@ -80,7 +80,8 @@ extern "C" {
  *        + efts_gl_init, efts_gl_synthesis, efts_gl_analysis, efts_gl_overlap_add (Griffin-Lim vocoder): exports added, nothing that existed
  *        changed size or meaning, so by the rule above the revision stays (a binding that needs them and meets an older library fails on the
  *        missing symbol)
- *        + efts_optim_step, efts_optim_hyper (Adam / AdamW / RAdam): exports added, the revision stays by the same rule */
+ *        + efts_optim_step, efts_optim_hyper (Adam / AdamW / RAdam): exports added, the revision stays by the same rule
+ *        + efts_resample, efts_resample_pcm16 (sample-rate conversion): exports added, the revision stays by the same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -778,6 +779,26 @@ int efts_gl_analysis(const float* wframes, const float* signal, int64_t ld_signa
                      int32_t hop, void* stream);
 int efts_gl_overlap_add(const float* wframes, const int32_t* frames, const float* window, float* out, int64_t ld_out, int32_t start,
                         int32_t n_out, int32_t B, int32_t T, int32_t n_fft, int32_t hop, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Sample-rate conversion between integer rates src and dst: a band-limited windowed-sinc interpolator (Kaiser window) in polyphase form.
+ * With g = gcd(src, dst), L = dst / g, M = src / g, fc = rolloff * min(1, dst / src), W = ceil(Z / fc), K = 2 W + 1 and, for tau in source
+ * samples and u = fc tau,  h(tau) = fc sinc(u) I0(beta sqrt(1 - (u / Z)^2)) / I0(beta) for |u| < Z, 0 otherwise (sinc(u) = sin(pi u) / (pi u)):
+ *   table : fp32 [L][K], table[p][kk] = h(p / L - (kk - W)), built by the caller (float64, once per rate pair; at most 4 MiB;
+ *           efficient_tts_amd/resample.py: Z 64, beta 14.77, rolloff 0.9476 ("best") or Z 16, beta 8.555, rolloff 0.85 ("fast"))
+ *   out[b * ld_out + n] = sum over kk = 0 .. K-1, in one fixed order, of x_b[i0 - W + kk] * table[p][kk],  i0 = floor(n M / L), p = (n M) mod L
+ *           (positions in 64 bits), for n < out_len(b) = (lengths[b] * L + M - 1) / M;  0 for out_len(b) <= n < ld_out: a padded batch.
+ *           x_b[i] = in[b * ld_in + i] for 0 <= i < lengths[b] (clamped to 0 .. ld_in) and 0 otherwise: nothing outside an item's samples is read.
+ *   out_lengths[b] = min(out_len(b), ld_out), written by the kernel.
+ * fp32 accumulation, no atomics: two runs give the same bits, and an item gives the same bits in any batch as alone.
+ * efts_resample_pcm16: the same kernel on int16 PCM, every sample multiplied by pcm_scale (1 / 32768: exact) at the load, as efts_logmel_fft_pcm16.
+ * EFTS_EINVAL: null pointer, non-positive or non-coprime L / M, W <= 0.  EFTS_ESHAPE: B outside 1 .. 65535, ld_in / ld_out outside 1 .. 2^31,
+ * a table above 4 MiB, or a rate ratio so steep that the input window of 512 outputs (511 M / L + K samples) does not fit 64 KiB of LDS.
+ * ---------------------------------------------------------------------------------- */
+int efts_resample(const float* in, int64_t ld_in, const int32_t* lengths, const float* table, int32_t L, int32_t M, int32_t W, float* out,
+                  int64_t ld_out, int32_t* out_lengths, int32_t B, void* stream);
+int efts_resample_pcm16(const int16_t* in, int64_t ld_in, float pcm_scale, const int32_t* lengths, const float* table, int32_t L, int32_t M,
+                        int32_t W, float* out, int64_t ld_out, int32_t* out_lengths, int32_t B, void* stream);
 
 #ifdef __cplusplus
 }
