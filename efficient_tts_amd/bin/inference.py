@@ -68,7 +68,8 @@ def get_parser() -> argparse.ArgumentParser:
     return p
 
 
-def _read_list(path: str, phn2idx) -> List[Tuple[str, torch.Tensor]]:
+def _read_list(path: str, phn2idx, with_paths: bool = False) -> List[Tuple[str, torch.Tensor]]:
+    """(utterance id, phoneme ids) per line of a `wav_path|phonemes` list; with_paths: (utterance id, phoneme ids, wav_path)"""
     items = []
     with open(path) as handle:
         for line in handle:
@@ -77,8 +78,27 @@ def _read_list(path: str, phn2idx) -> List[Tuple[str, torch.Tensor]]:
                 continue
             wav_path, text = line.split("|")[:2]
             utt = os.path.splitext(os.path.basename(wav_path))[0]
-            items.append((utt, torch.tensor([phn2idx[p] for p in text.split()], dtype=torch.long)))
+            ids = torch.tensor([phn2idx[p] for p in text.split()], dtype=torch.long)
+            items.append((utt, ids, wav_path) if with_paths else (utt, ids))
     return items
+
+
+def load_acoustic_model(args, device):
+    """(config, phn2idx, model) of --checkpoint / --config / --precision: the model in eval mode, weight norm removed"""
+    config_path = args.config or os.path.join(os.path.dirname(args.checkpoint), "config.yml")
+    with open(config_path) as handle:
+        config = yaml.safe_load(handle)
+    data_params = config.get("dataset_params") or {}
+    if not data_params.get("use_phnseq", False):
+        raise NotImplementedError("only phoneme-sequence recipes (dataset_params.use_phnseq: true) are supported")
+    with open(data_params["phnset_path"]) as handle:
+        phn2idx = {p.strip(): i for i, p in enumerate(handle)}
+    model = getattr(models, config["model_name"])(precision=args.precision, **config["model_params"])
+    state = torch.load(args.checkpoint, map_location="cpu")
+    model.load_state_dict(state["model"])
+    model = model.to(device).eval()
+    model.remove_weight_norm()
+    return config, phn2idx, model
 
 
 def _write_wav(path: str, samples: torch.Tensor, sampling_rate: int = SAMPLING_RATE) -> None:
@@ -102,14 +122,7 @@ def run_tts(args) -> float:
         raise RuntimeError("no MI355X (gfx950) device visible: efficient_tts_amd has no CPU path")
     device = torch.device("cuda")
     os.makedirs(args.outdir, exist_ok=True)
-    config_path = args.config or os.path.join(os.path.dirname(args.checkpoint), "config.yml")
-    with open(config_path) as handle:
-        config = yaml.safe_load(handle)
-    data_params = config.get("dataset_params") or {}
-    if not data_params.get("use_phnseq", False):
-        raise NotImplementedError("only phoneme-sequence recipes (dataset_params.use_phnseq: true) are supported")
-    with open(data_params["phnset_path"]) as handle:
-        phn2idx = {p.strip(): i for i, p in enumerate(handle)}
+    config, phn2idx, model = load_acoustic_model(args, device)
     idx2phn = {i: p for p, i in phn2idx.items()}
     hop = int(config.get("hop_size", 256))
     sampling_rate = int(config.get("sampling_rate", SAMPLING_RATE))
@@ -123,11 +136,6 @@ def run_tts(args) -> float:
     logging.info(f"{len(items)} utterances to synthesise")
     step = os.path.basename(args.checkpoint).split("-")[-1][:-4]
 
-    model = getattr(models, config["model_name"])(precision=args.precision, **config["model_params"])
-    state = torch.load(args.checkpoint, map_location="cpu")
-    model.load_state_dict(state["model"])
-    model = model.to(device).eval()
-    model.remove_weight_norm()
     vocoder = None
     if not args.no_vocoder and args.vocoder == "griffinlim":
         vocoder = GriffinLimVocoder(device, n_iter=args.gl_iters, precision="fp32" if args.precision == "fp32" else "bf16x3")

@@ -195,6 +195,9 @@ _SIGS = {
     # sample-rate conversion
     "efts_resample": (i32, [vp, i64, vp, vp, i32, i32, i32, vp, i64, vp, i32, vp]),
     "efts_resample_pcm16": (i32, [vp, i64, f32, vp, vp, i32, i32, i32, vp, i64, vp, i32, vp]),
+    # scoring: mel-cepstra and dynamic time warping
+    "efts_mel_cepstrum": (i32, [vp, i64, i64, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "efts_dtw": (i32, [vp, i64, i64, vp, i32, vp, i64, i64, vp, i32, i32, vp, vp, i32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

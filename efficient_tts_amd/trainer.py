@@ -19,6 +19,8 @@ Everything inside is organised for this engine rather than copied from the refer
   * an optional `frontend` (efficient_tts_amd.frontend.LogMelFrontend) turns waveform batches into
     log-mels on the GPU; `bucket_frames` / `bucket_phones` pad shapes up to multiples so the engine's
     per-shape workspaces are re-used across ragged batches;
+  * `eval_mcd: true` (YAML, default false) adds the free-running pass to every evaluation and publishes its mel-cepstral distortion
+    against the dev recordings (efficient_tts_amd.score) -- the only figure here that sees the duration predictor;
   * tensorboardX / tqdm are used when importable, silently skipped otherwise.
 """
 from __future__ import annotations
@@ -237,12 +239,24 @@ class EfficientTTSTrainer:
         net = self._net
         net.eval()
         batches = 0
+        scorer = None
+        if self.config.get("eval_mcd", False):                  # also the free-running pass, scored against the dev recordings
+            from .score import MelCepstralDistortion
+            scorer = MelCepstralDistortion(self.device, num_mels=int(getattr(net, "odim", 80)))
+            mcd_sum, ratio_sum, utterances = 0.0, 0.0, 0     # device sums: read once, behind the loop
         for batch in self.data_loader["dev"]:
             text, text_lengths, mel, mel_lengths = self._stage(batch)
             out = net(text=text, text_lengths=text_lengths, speech=mel, speech_lengths=mel_lengths)
             self._eval_meter.add(out[1])
             batches += 1
+            if scorer is not None:
+                syn, syn_lengths = net.inference_batch(text, text_lengths)[:2]
+                scores = scorer(syn, syn_lengths, mel, mel_lengths)
+                mcd_sum, ratio_sum = mcd_sum + scores["mcd"].sum(), ratio_sum + scores["frames_ratio"].sum()
+                utterances += text.shape[0]
         self._publish(self._eval_meter.means(batches))
+        if scorer is not None and utterances:
+            self._publish({"eval/mcd_db": float(mcd_sum) / utterances, "eval/frames_ratio": float(ratio_sum) / utterances})
         log.info(f"[step {self.steps}] evaluated {batches} dev batches")
         self._eval_meter.reset()
         net.train()

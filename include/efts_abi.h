@@ -81,7 +81,8 @@ extern "C" {
  *        changed size or meaning, so by the rule above the revision stays (a binding that needs them and meets an older library fails on the
  *        missing symbol)
  *        + efts_optim_step, efts_optim_hyper (Adam / AdamW / RAdam): exports added, the revision stays by the same rule
- *        + efts_resample, efts_resample_pcm16 (sample-rate conversion): exports added, the revision stays by the same rule */
+ *        + efts_resample, efts_resample_pcm16 (sample-rate conversion): exports added, the revision stays by the same rule
+ *        + efts_mel_cepstrum, efts_dtw (scoring synthesis against a recording): exports added, the revision stays by the same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -799,6 +800,34 @@ int efts_resample(const float* in, int64_t ld_in, const int32_t* lengths, const 
                   int64_t ld_out, int32_t* out_lengths, int32_t B, void* stream);
 int efts_resample_pcm16(const int16_t* in, int64_t ld_in, float pcm_scale, const int32_t* lengths, const float* table, int32_t L, int32_t M,
                         int32_t W, float* out, int64_t ld_out, int32_t* out_lengths, int32_t B, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Scoring synthesised speech against a recording: mel-cepstra, and the cost and length of the dynamic-time-warping path between two
+ * sequences of them (efficient_tts_amd/score.py turns the two into mel-cepstral distortion).  fp32, no atomics, one workgroup per item or
+ * pair and one fixed order of every sum: an item gives the same bits alone, in any batch and in any run.
+ *
+ * efts_mel_cepstrum: out[b][t][k] = sum over n = 0 .. n_mels - 1, in this order, of table[k][n] * mel[b * item_stride + t * ld + n] for
+ *   t < lengths[b] (clamped to 0 .. T), and 0 for lengths[b] <= t < T; rows at or beyond an item's length are not read.  out is dense
+ *   [B][T][n_coef]; table [n_coef][n_mels] is built by the caller (efficient_tts_amd/score.py: rows 1 .. n_coef of the orthonormal DCT-II,
+ *   sqrt(2 / N) cos(pi k (n + 1/2) / N), float64 rounded once to fp32; row 0 -- loudness -- is left out).
+ *   EFTS_EINVAL: null pointer.  EFTS_ESHAPE: n_mels outside 1 .. 128, n_coef outside 1 .. 32, B outside 1 .. 65535, T < 1, ld < n_mels.
+ *
+ * efts_dtw: x [B][Tx][D] and y [B][Ty][D] with row strides ldx, ldy and item strides (all in floats); item b has x_lengths[b] and
+ *   y_lengths[b] rows (clamped to Tx, Ty), rows beyond them are never read.  With the local cost d(i, j) = sqrt(sum over k = 0 .. D - 1,
+ *   in this order and fused, of (x_i[k] - y_j[k])^2), the square root correctly rounded:
+ *     A(0, 0) = d(0, 0), L(0, 0) = 1;   A(i, j) = d(i, j) + A(p), L(i, j) = 1 + L(p), p the cheapest existing predecessor among
+ *     (i-1, j-1), (i-1, j), (i, j-1), tried in this order, a later one replacing an earlier one only when strictly smaller;
+ *     cost[b] = A(last row, last column), path_len[b] = L(last row, last column).
+ *   An item with a length below 1 gets cost NaN and path_len 0 and nothing of it is read.  No cost matrix exists in memory: a band of
+ *   1024 rows advances as an anti-diagonal wavefront that lives in registers and LDS.
+ *   EFTS_EINVAL: null pointer.  EFTS_ESHAPE: D outside 1 .. 32, Tx or Ty outside 1 .. EFTS_DTW_MAX_FRAMES, B outside 1 .. 65535, a row
+ *   stride below D; nothing is launched.
+ * ---------------------------------------------------------------------------------- */
+#define EFTS_DTW_MAX_FRAMES 8192
+int efts_mel_cepstrum(const float* mel, int64_t ld, int64_t item_stride, const int32_t* lengths, const float* table, float* out, int32_t B,
+                      int32_t T, int32_t n_mels, int32_t n_coef, void* stream);
+int efts_dtw(const float* x, int64_t ldx, int64_t x_item_stride, const int32_t* x_lengths, int32_t Tx, const float* y, int64_t ldy,
+             int64_t y_item_stride, const int32_t* y_lengths, int32_t Ty, int32_t D, float* cost, int32_t* path_len, int32_t B, void* stream);
 
 #ifdef __cplusplus
 }
