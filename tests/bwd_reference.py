@@ -78,6 +78,19 @@ def masked_ralpha(e, sigma, mel_mask, text_mask):
     return reconstruct_alignment(e, sigma, mel_mask, text_mask).masked_fill(~both, 0.0)
 
 
+def duration_target(e, text_lengths, mel_lengths, offset, method1):
+    """log_delta_e of efts_oracle.forward (:307-314): method 1 e_i - e_{i-1} with e_{-1} = 0, otherwise e_{i+1} - e_i with
+    e_{text_len} = mel_len; log(. + offset), 0 at padded tokens"""
+    if method1:
+        delta_e = torch.cat([e[:, :1], e[:, 1:] - e[:, :-1]], dim=1)
+    else:
+        ee = torch.cat([e, torch.zeros(e.shape[0], 1, dtype=e.dtype)], dim=1)
+        for i in range(e.shape[0]):
+            ee[i, int(text_lengths[i])] = float(mel_lengths[i])
+        delta_e = ee[:, 1:] - ee[:, :-1]
+    return torch.log(delta_e + offset).masked_fill(~non_pad_mask(text_lengths, e.shape[1]), 0.0)
+
+
 def masked_losses(mel_pred, speech, dur_pred, log_delta_e, mel_mask, text_mask):
     """FastSpeechLoss(use_masking=True) as efts_oracle.forward takes it: (mel_loss, dur_loss)"""
     n_mel = mel_mask.sum() * speech.shape[2]

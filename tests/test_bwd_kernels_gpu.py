@@ -64,50 +64,16 @@ import pytest
 import torch
 
 import bwd_reference as R
+from kernel_check import COND, FACTOR, FLOOR, _call, _check, _dev, _rel, _st, load_lib   # noqa: F401  (the metric and the bound: tests/kernel_check.py)
 
 pytestmark = pytest.mark.gpu
 
 SIGMA, SIGMA_E = 0.01, 0.5
-FACTOR, FLOOR, COND = 8.0, 2e-6, 2e-4
-
-
-def _dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from efficient_tts_amd import lib as L
-    L.require_device()
-    return L.load()
-
-
-def _st():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _call(name, rc):
-    from efficient_tts_amd import lib as L
-    L.check(rc, name)
-
-
-def _rel(a, b):
-    return float((a - b).abs().max()) / (float(b.abs().max()) + 1e-12)
-
-
-def _check(kernel, case, got, ref64, ref32, chain=False):
-    """got (device or host tensor) against the float64 reference, bounded by the float32 transcription's own error.
-    chain: the bound is min(max(8 * e32, 2e-6), 2e-4) instead of the condition on e32 (see test_alignment_backward_chain_vs_fp64)"""
-    got = got.detach().cpu().double().reshape(ref64.shape)
-    e32 = _rel(ref32.detach().double().reshape(ref64.shape), ref64)
-    err = _rel(got, ref64)
-    ratio = err / e32 if e32 > 0 else float("inf") if err > 0 else 0.0
-    print(f"RATIO {kernel} {case} err={err:.3e} e32={e32:.3e} ratio={ratio:.2f}")
-    assert torch.isfinite(got).all()
-    if not chain:
-        assert FACTOR * e32 <= COND, f"{kernel} {case}: inputs too ill-conditioned for the bound to mean anything (e32 = {e32:.3e})"
-    assert err <= min(max(FACTOR * e32, FLOOR), COND), f"{kernel} {case}: error {err:.3e} vs float64, float32 transcription {e32:.3e}"
+    return load_lib()
 
 
 def _grad(fn, x32, up32, dtype):

@@ -84,6 +84,19 @@ def test_loss_twin_equals_the_oracle_forward(golden_dir):
     assert torch.equal(mel_loss + dur_loss, o["loss"])
 
 
+@pytest.mark.parametrize("method1", [True, False])
+def test_duration_target_twin_equals_the_oracle_forward(golden_dir, method1):
+    gz = np.load(os.path.join(golden_dir, "fwd_tiny.npz"))
+    text, tl, speech, ml = (torch.from_numpy(gz[k]) for k in ("text", "text_lengths", "speech", "speech_lengths"))
+    hp = dict(O.DEFAULT_HP, delta_e_method_1=method1)
+    with torch.no_grad():
+        o = O.forward(O.fill_params(), text, tl, speech, ml, hp)
+    assert int(tl.min()) < text.shape[1]                                             # (a padded token is in the batch)
+    got = R.duration_target(o["e"], tl, ml, hp["duration_offset"], method1)
+    assert got.dtype == torch.float32 and torch.equal(got, o["log_delta_e"])
+    assert R.duration_target(o["e"].double(), tl, ml, hp["duration_offset"], method1).dtype == torch.float64
+
+
 def test_twin_gradients_pass_gradcheck():
     B, T1, T2 = 2, 5, 11
     tl, ml = torch.tensor([5, 3], dtype=torch.int32), torch.tensor([11, 7], dtype=torch.int32)
