@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import torch
 
-from . import lib as L, ops as O
+from . import ops as O
 from .model import LazyStats
 from .train import TrainEngine
 
@@ -50,7 +50,7 @@ class _FusedStep(torch.autograd.Function):
         # d(loss) scaling (1.0 in the reference loop: the kernel returns at once, no pass over the buffer)
         gl = g_loss.detach().to(device=eng.flat.device, dtype=torch.float32).reshape(1)
         with O.stream_scope():
-            L.check(L.load().efts_scale_unless_one(eng.flat.data_ptr(), eng.numel, gl.data_ptr(), O._stream()), "efts_scale_unless_one")
+            O.scale_unless_one(eng.flat, eng.numel, gl)
         # The per-parameter gradients ARE views of the engine's flat buffer (what the fused clip + Adam and
         # the bucketed all-reduce work on).  They are attached as `.grad` directly: handing them to
         # autograd's AccumulateGrad would clone all ~75 of them every step.  Consequence: gradients do
@@ -64,8 +64,5 @@ class _FusedStep(torch.autograd.Function):
 def training_forward(model, text, text_lengths, speech, speech_lengths):
     params = tuple(model.parameters())
     loss, out3 = _FusedStep.apply(model, text, text_lengths, speech, speech_lengths, *params)
-    ws = model._workspace(("train", text.shape[0], text.shape[1], speech.shape[1]), text.device)
-    rs2 = ws.bufs[("f", "Tmel_pred", text.shape[0], speech.shape[1], model.odim)]
-    imv = ws.bufs[("t", "Timv", (text.shape[0], speech.shape[1]), torch.float32)]
-    ralpha = ws.bufs[("t", "Tralpha", (text.shape[0], text.shape[1], speech.shape[1]), torch.float32)]
-    return loss, LazyStats(out3), imv.clone(), ralpha.clone(), rs2.view().clone(), speech
+    out = model._engine.last                                 # (the engine _FusedStep.forward just ran the step on)
+    return loss, LazyStats(out3), out.imv.clone(), out.ralpha.clone(), out.mel.view().clone(), speech

@@ -350,12 +350,18 @@ def embed_conv(ids: torch.Tensor, lens: Optional[torch.Tensor], table: torch.Ten
                                      rs.B, rs.T, rs.Tp, c, nsym, taps, 1 if plane is None else plane.split, _stream()), "efts_embed_conv")
 
 
-def pack_rows(x: torch.Tensor, out: Optional[F32Rows], plane: Optional[Plane], rs: Rows) -> None:
-    c = x.shape[-1]
-    kp = roundup(c, 4) if plane is None else plane.nchunk * chunk_k(plane.split)
-    L.check(L.load().efts_pack_rows(x.data_ptr(), None if out is None else out.ptr,
+def pack_rows(x, out: Optional[F32Rows], plane: Optional[Plane], rs: Rows, kp: Optional[int] = None) -> None:
+    """x: a dense [B, T, c] tensor, or an F32Rows of `rs` (already in the padded layout: all Tp rows of every item are copied);
+    kp: columns written per row (default: the plane's whole chunks)"""
+    if isinstance(x, F32Rows):
+        x_ptr, c, T = x.ptr, x.c, rs.Tp
+    else:
+        x_ptr, c, T = x.data_ptr(), x.shape[-1], rs.T
+    if kp is None:
+        kp = roundup(c, 4) if plane is None else plane.nchunk * chunk_k(plane.split)
+    L.check(L.load().efts_pack_rows(x_ptr, None if out is None else out.ptr,
                                     None if plane is None else plane.ptr, 0 if plane is None else plane.ld,
-                                    rs.B, rs.T, rs.Tp, c, kp, 1 if plane is None else plane.split, _stream()),
+                                    rs.B, T, rs.Tp, c, kp, 1 if plane is None else plane.split, _stream()),
             "efts_pack_rows")
 
 
@@ -430,8 +436,10 @@ def expand(*, e, tl, ml, sigma: float, v: F32Rows, rs1: Rows, rs2: Rows, alpha_o
     L.check(L.load().efts_expand(C.byref(g), _stream()), "efts_expand")
 
 
-def pack_vt(v: F32Rows, plane: Plane, B, T1, T1p, c) -> None:
-    L.check(L.load().efts_pack_vt(v.ptr, v.c, plane.ptr, plane.ld, B, T1, T1p, c, plane.split, _stream()), "efts_pack_vt")
+def pack_vt(v, plane: Plane, B, T1, T1p, c) -> None:
+    """v: an F32Rows, or a dense [B, T1p, ldv >= c] tensor"""
+    v_ptr, ldv = (v.ptr, v.c) if isinstance(v, F32Rows) else (v.data_ptr(), v.shape[-1])
+    L.check(L.load().efts_pack_vt(v_ptr, ldv, plane.ptr, plane.ld, B, T1, T1p, c, plane.split, _stream()), "efts_pack_vt")
 
 
 def cumsum_rows(x, y, B, T) -> None:
@@ -476,9 +484,110 @@ def store_words(dst: torch.Tensor, words) -> None:
 
 def mask_rows(x_ptr, rowmask_ptr, out: Optional[F32Rows], plane: Optional[Plane], rows, c) -> None:
     """out[row] = x[row] * rowmask[row] (fp32 and/or operand plane): efts_act_bwd in identity mode"""
-    L.check(L.load().efts_act_bwd(x_ptr, None, None, rowmask_ptr, 0.0, 0, None if out is None else out.ptr,
-                                  None if plane is None else plane.ptr, 0 if plane is None else plane.ld,
-                                  1 if plane is None else plane.split, None, rows, c, _stream()), "efts_act_bwd")
+    act_bwd(x_ptr, None, None, rowmask_ptr, 0.0, 0, out, plane, None, rows, c)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# training side (csrc/efts_train.hip, csrc/efts_wgrad.hip).  `*_ptr` arguments are device addresses (an F32Rows' `.ptr`), the
+# others tensors, F32Rows or Planes; None where the entry takes NULL
+# ---------------------------------------------------------------------------------------------------------------------
+def _pl(plane: Optional[Plane]):
+    """(ptr, ld, split) of an optional output plane"""
+    return (None, 0, 1) if plane is None else (plane.ptr, plane.ld, plane.split)
+
+
+def act_bwd(g_ptr, y_ptr, x_ptr, rowmask_ptr, slope: float, mode: int, dz: Optional[F32Rows], plane: Optional[Plane], dbias, rows, c) -> None:
+    """dZ = G * rowmask * act'(.) as fp32 and / or operand plane, bias gradient += column sums (mode: include/efts_abi.h)"""
+    L.check(L.load().efts_act_bwd(g_ptr, y_ptr, x_ptr, rowmask_ptr, slope, mode, None if dz is None else dz.ptr, *_pl(plane), _p(dbias),
+                                  rows, c, _stream()), "efts_act_bwd")
+
+
+def act_bwd_dropout(g_ptr, y_ptr, x_ptr, rowmask_ptr, slope: float, mode: int, dz: Optional[F32Rows], plane: Optional[Plane], dbias, rows, c,
+                    drop_p: float = 0.0, drop_seed: int = 0) -> None:
+    """act_bwd behind a train-mode Dropout whose mask is regenerated from the forward's seed"""
+    L.check(L.load().efts_act_bwd_dropout(g_ptr, y_ptr, x_ptr, rowmask_ptr, slope, mode, None if dz is None else dz.ptr, *_pl(plane),
+                                          _p(dbias), rows, c, drop_p, drop_seed & 0xFFFFFFFF, _stream()), "efts_act_bwd_dropout")
+
+
+def loss_bwd(mel_pred_ptr, ldm, speech, ml, dur_pred, lde, tl, gscale, dmel_ptr, plane: Optional[Plane], ddur, B, T1, T1p, T2, T2p, odim,
+             split: int = 1) -> None:
+    """d loss / d mel_pred (fp32 and / or operand plane) and d loss / d dur_pred, times the device scalar gscale (None: 1).
+    split: without a plane, the operand format whose launch geometry the call takes (with one: the plane's)"""
+    pl = _pl(plane)
+    L.check(L.load().efts_loss_bwd(mel_pred_ptr, ldm, speech.data_ptr(), ml.data_ptr(), dur_pred.data_ptr(), lde.data_ptr(), tl.data_ptr(),
+                                   _p(gscale), dmel_ptr, pl[0], pl[1], split if plane is None else pl[2], ddur.data_ptr(), B, T1, T1p, T2, T2p,
+                                   odim, _stream()), "efts_loss_bwd")
+
+
+def layernorm_bwd(x_ptr, gamma, beta, eps, dy_ptr, ddur, w, rowmask_ptr, dz_ptr, plane: Optional[Plane], dgamma, dbeta, dbias, dw, db,
+                  rows, c, drop_p: float = 0.0, drop_seed: int = 0, seed_add_ptr: Optional[int] = None) -> None:
+    """backward of relu -> LayerNorm(c) (-> Linear(c, 1)): upstream either dy_ptr [rows, c] or ddur [rows] times w; the parameter
+    gradients are accumulated"""
+    L.check(L.load().efts_layernorm_bwd(x_ptr, gamma.data_ptr(), beta.data_ptr(), eps, dy_ptr, _p(ddur), _p(w), rowmask_ptr, dz_ptr, *_pl(plane),
+                                        dgamma.data_ptr(), dbeta.data_ptr(), _p(dbias), _p(dw), _p(db), rows, c, drop_p,
+                                        drop_seed & 0xFFFFFFFF, seed_add_ptr, _stream()), "efts_layernorm_bwd")
+
+
+def alpha_bwd(ralpha, dalpha, e, tl, ml, sigma: float, r, de, B, T1, T2) -> None:
+    L.check(L.load().efts_alpha_bwd(ralpha.data_ptr(), dalpha.data_ptr(), e.data_ptr(), tl.data_ptr(), ml.data_ptr(), sigma, r.data_ptr(),
+                                    de.data_ptr(), B, T1, T2, _stream()), "efts_alpha_bwd")
+
+
+def e_bwd(imv, e, de, tl, ml, sigma_e: float, stats, dpi, B, T1, T2) -> None:
+    """stats: scratch of 2 * B * T1 floats"""
+    L.check(L.load().efts_e_bwd(imv.data_ptr(), e.data_ptr(), de.data_ptr(), tl.data_ptr(), ml.data_ptr(), sigma_e, stats.data_ptr(),
+                                dpi.data_ptr(), B, T1, T2, _stream()), "efts_e_bwd")
+
+
+def imv_bwd(soft_idx, imv, dpi, tl, ml, dsoft_idx, B, T2) -> None:
+    L.check(L.load().efts_imv_bwd(soft_idx.data_ptr(), imv.data_ptr(), dpi.data_ptr(), tl.data_ptr(), ml.data_ptr(), dsoft_idx.data_ptr(), B, T2,
+                                  _stream()), "efts_imv_bwd")
+
+
+def attn_bwd(scores, ld, soft_idx, dsoft_idx, tl, ml, dscores, ldd, plane: Plane, B, T1, T2, T2p) -> None:
+    """d scores in fp32 (row stride ldd) and as the bf16x3 operand plane of the row space [B][T2p]"""
+    L.check(L.load().efts_attn_bwd(scores.data_ptr(), ld, soft_idx.data_ptr(), dsoft_idx.data_ptr(), tl.data_ptr(), ml.data_ptr(),
+                                   dscores.data_ptr(), ldd, plane.ptr, plane.ld, B, T1, T2, T2p, _stream()), "efts_attn_bwd")
+
+
+def embed_bwd(ids, g_ptr, dtable, B, T, Tp, c) -> None:
+    """dtable[ids[b, t]] += g[b * Tp + t]"""
+    L.check(L.load().efts_embed_bwd(ids.data_ptr(), g_ptr, dtable.data_ptr(), B, T, Tp, c, dtable.shape[0], _stream()), "efts_embed_bwd")
+
+
+def pack_t(x_ptr, ldx, dst, rows, c, kpad, shift: int = 0, taps: int = 1, tap_stride: int = 0) -> None:
+    """x[rows, c] (row stride ldx) transposed into `taps` planes [c][K = kpad rows] of `dst` (`.ptr`, `.ld`, `.split`), tap_stride bytes
+    apart, plane k shifted by shift + k rows"""
+    L.check(L.load().efts_pack_t(x_ptr, ldx, dst.ptr, dst.ld, tap_stride, dst.split, rows, c, shift, taps, kpad, _stream()), "efts_pack_t")
+
+
+def wgrad_reduce(part, nsplit, v, g, dw_or_dv, dg, cout, cin, taps) -> None:
+    """sum of the split-K partial products [taps][nsplit][cout][cin] into dW, or through the weight norm into dv, dg"""
+    L.check(L.load().efts_wgrad_reduce(part.data_ptr(), nsplit, _p(v), _p(g), dw_or_dv.data_ptr(), _p(dg), cout, cin, taps, _stream()),
+            "efts_wgrad_reduce")
+
+
+def wgrad_grouped(items, rows, cout, cin, taps, split, wgs, scratch) -> None:
+    """the direct weight gradients of up to L.WGRAD_MAX_ITEMS equally shaped layers as ONE stream-K launch and ONE reduction.
+    items: (dz_plane, x_plane, v, g, dw_or_dv, dg, bias_part, dbias) per layer; scratch(nbytes) -> the fp32 tensor of the partial products"""
+    lib = L.load()
+    n = len(items)
+    arr = (L.WgradItem * n)()
+    for a, (dz_p, x_p, v, g, dw, dg, bp, db) in zip(arr, items):
+        a.dz_plane, a.ldz, a.x_plane, a.ldx = dz_p.ptr, dz_p.ld, x_p.ptr, x_p.ld
+        a.v, a.g, a.dw_or_dv, a.dg = _p(v), _p(g), dw.data_ptr(), _p(dg)
+        a.bias_part, a.dbias, a.nparts = _p(bp), _p(db), 0 if bp is None else bp.shape[0]
+    nbytes = lib.efts_wgrad_grouped_part_bytes(n, rows, cout, cin, taps, split, wgs)
+    if nbytes < 0:
+        L.check(-1, "efts_wgrad_grouped_part_bytes")
+    part = scratch(nbytes)
+    L.check(lib.efts_wgrad_tn_grouped(arr, n, part.data_ptr(), rows, cout, cin, taps, split, wgs, _stream()), "efts_wgrad_tn_grouped")
+    L.check(lib.efts_wgrad_reduce_grouped(arr, n, part.data_ptr(), rows, cout, cin, taps, split, wgs, _stream()), "efts_wgrad_reduce_grouped")
+
+
+def scale_unless_one(x, n, scale) -> None:
+    """x[:n] *= *scale (a device scalar); 1 leaves every bit alone"""
+    L.check(L.load().efts_scale_unless_one(x.data_ptr(), n, scale.data_ptr(), _stream()), "efts_scale_unless_one")
 
 
 def losses_workspace(device) -> torch.Tensor:

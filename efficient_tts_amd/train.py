@@ -9,6 +9,7 @@ ranges that become final early: mel head + decoder first, text encoder + embeddi
 from __future__ import annotations
 
 import contextlib
+from collections import namedtuple
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
@@ -17,13 +18,6 @@ from . import lib as L
 from . import ops as O
 from .ops import F32Rows, PackedWeight, Plane, Rows
 from .model import require_trainable
-
-_lib = L.load
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
 
 # Test hooks and tuning constants of the training pass (module-level: bench.py --train-set NAME=INT, tests).  Round 6 removed the decided A/Bs
 # (_PACK_SPLIT, _NARROW_TN, _EARLY_PACKS: always on) and did not keep its own (_WGRAD_EARLY, _TEXT_RIDERS, _HEAD_ORDER, _PACK_LATE,
@@ -46,6 +40,8 @@ _WGRAD_STREAM = 3            # the mel-length weight gradients (mel head, decode
                              # 0.25 ms of small latency-bound launches that use neither the matrix pipes nor the power budget.  Joined in front of a gradient
                              # bucket's hand-over (data parallel) or of the optimizer.  Bit 0: decoder group, bit 1: head, mel-encoder group, prenet (A/B)
 _GV_ON_SIDE = 1              # eager steps: the dV branch of the alignment backward (pack_vt of dH + one batched product) on the text-side stream beside the d alpha' -> ... -> dK chain
+                             # (3.51-3.63 -> 3.46-3.56 ms per step).  Captured into the step's hipGraph the extra branch costs 0.1 ms (3.41 vs 3.30 ms,
+                             # bf16x3 6.55 vs 6.27: the replayed graph's stream assignment loses the overlap of the weight-gradient stream)
 _FUSE_ACT_BWD = 1            # stacks whose dgrad runs on efts_resconv5: the activation backward of layer l - 1 in the epilogue of layer l's dgrad launch
                              # (csrc/efts_resconv_bwd.hip) instead of an efts_act_bwd launch of its own (0: separate launches; tests compare)
 _WGRAD_GROUP_WGS = 384       # workgroups of a grouped launch (0: two per CU).  Swept 256..512 on the graphed B = 32 step: 3.27-3.32 ms at 384 against 3.33-3.34 at 512,
@@ -103,9 +99,53 @@ def grad_layout(model) -> List[Tuple[str, torch.nn.Parameter]]:
     return [(n, named[n]) for n in order]
 
 
+def _hand_over(src, dst=None):
+    """THE hand-over between streams: what is enqueued on `src` so far is visible to `dst`.  dst None: the wait happens later, on the
+    returned event (`dst.wait_event(ev)`) -- work enqueued on `dst` in between overlaps what `src` runs behind the record"""
+    ev = torch.cuda.Event()
+    ev.record(src)
+    if dst is not None:
+        dst.wait_event(ev)
+    return ev
+
+
+class _Step:
+    """What every stage of one training step reads.  ws: the workspace of the shape; rs1 / rs2: text- and mel-length row spaces;
+    gap* / len*: their row masks (0 on the gap rows / beyond each item's length as well); tl / ml: int32 lengths on the device;
+    pk: packed forward planes by layer name (set by the repack); main / side / wst: the streams of the mel-length work, the
+    text-length work (main itself without model.side_stream) and the mel-length weight gradients (None without _WGRAD_STREAM);
+    drop_p, seed0, seed1, sadd: the duration predictor's Dropout -- p, the seeds of its two layers, and the address of the device
+    word added to both in a captured step (else None)"""
+    __slots__ = ("ws", "text", "speech", "gscale", "B", "T1", "T2", "rs1", "rs2", "gap1", "len1", "gap2", "len2", "tl", "ml", "pk",
+                 "main", "side", "wst", "drop_p", "seed0", "seed1", "sadd")
+
+    def __init__(self, **fields):
+        self.pk = None
+        for k, v in fields.items():
+            setattr(self, k, v)
+
+
+# What a stage hands to the stages behind it (`_f`: F32Rows, `_p`: operand Plane, `*_saved`: per-layer activations of _stack_fwd).
+_StepOutputs = namedtuple("_StepOutputs", "imv ralpha mel")       # for the step's caller: workspace buffers, valid until the next step of the shape
+_TextFwd = namedtuple("_TextFwd", "te_f te_p te_saved key_f key_p val_f val_p")
+_DurFwd = namedtuple("_DurFwd", "h1_f l1_f l1_p h2_f dur")
+_MelFwd = namedtuple("_MelFwd", "mel_in_f mel_in pre_f pre_z pre_drop mh_f mh_p q_f q_p me_saved")    # mh_*: only in front of a query fc
+_AlignFwd = namedtuple("_AlignFwd", "scores sidx imv e lde ralpha ra_p h_f h_p")                               # ra_p: only where the expand is not fused
+_DecFwd = namedtuple("_DecFwd", "d_f d_p dec_saved")
+_LossFwd = namedtuple("_LossFwd", "out3 ml_loss tl_loss")
+_LossBwd = namedtuple("_LossBwd", "dmel_f dmel_p ddur")
+_Packs = namedtuple("_Packs", "val_p2 ra1_p kt qt")               # operands of the alignment backward that depend on forward tensors only
+_DV = namedtuple("_DV", "GV GV_p")
+_AlignBwd = namedtuple("_AlignBwd", "de dpi dsx dS GQ dSt")
+
+
 class TrainEngine:
     def __init__(self, model):
         require_trainable(model, "TrainEngine")
+        if len(model.duration_predictor.conv) != 2:
+            # the step's duration-predictor stages (_fwd_duration, _bwd_duration) are written out for the two layers of the shipped recipe
+            raise NotImplementedError(f"TrainEngine: n_duration_layer = {len(model.duration_predictor.conv)}: the training step implements "
+                                      "the two-layer duration predictor only (synthesis runs any depth)")
         self.m = model
         self.layout = grad_layout(model)
         self.named = list(model.named_parameters())     # model.parameters() order (what autograd's Function receives)
@@ -136,6 +176,7 @@ class TrainEngine:
         self.bucket_hook: Optional[Callable[[int], None]] = None
         self.join_reduce: Optional[Callable[[], None]] = None
         self.mark: Optional[Callable[[str], None]] = None      # timing probe of the data-parallel wrapper (bench only)
+        self.last: Optional[_StepOutputs] = None               # outputs of the last step (set by forward_backward)
         self.bound = set()                      # who holds views of `flat` (EftsAdam, DistributedEFTS): see autograd.engine_of
 
     def stale(self, model) -> bool:
@@ -163,13 +204,6 @@ class TrainEngine:
         return m.planes.schedule(m, self.folded, self.wt, self.step_params, self._pack_phase)
 
     # ------------------------------------------------------------------ small wrappers
-    def _act_bwd(self, g_ptr, y_ptr, x_ptr, mask_ptr, mode, dz: Optional[F32Rows], plane: Optional[Plane], dbias, rows, c,
-                 drop_p: float = 0.0, drop_seed: int = 0):
-        L.check(_lib().efts_act_bwd_dropout(g_ptr, y_ptr, x_ptr, mask_ptr, self.m.slope, mode, None if dz is None else dz.ptr,
-                                            None if plane is None else plane.ptr, 0 if plane is None else plane.ld,
-                                            1 if plane is None else plane.split, _ptr(dbias), rows, c, drop_p, drop_seed & 0xFFFFFFFF,
-                                            O._stream()), "efts_act_bwd")
-
     def _conv_drop(self, k: int):
         """(p, seed) of the train-mode Dropout behind the activation of conv / prenet launch k (efts_modules.py:38-47,
         efficient_tts.py:76-80): one mask per launch and step, regenerated by the backward from the same seed"""
@@ -207,17 +241,15 @@ class TrainEngine:
         kpad = O.roundup(S * nch * ck, 64)
         tag = self._ws_tag                       # the side stream owns its own scratch (both streams run wgrads at once)
         zt = ws.get(("zt", tag, cout, kpad, split), lambda: _TPlane(cout, kpad, split, self.dev))
-        L.check(_lib().efts_pack_t(dz_ptr, cout, zt.ptr, zt.ld, 0, split, rows, cout, 0, 1, kpad, O._stream()), "efts_pack_t")
+        O.pack_t(dz_ptr, cout, zt, rows, cout, kpad)
         part = ws.get(("part", tag, taps, S, cout, cin), lambda: torch.empty(taps, S, cout, cin, device=self.dev))
         pad = (taps - 1) // 2
         xts = ws.get(("xt", tag, cin, kpad, split, taps), lambda: _TPlaneStack(cin, kpad, split, taps, self.dev))
-        L.check(_lib().efts_pack_t(x_ptr, ldx, xts.ptr, xts.ld, xts.plane_bytes, split, rows, cin, -pad, taps, kpad, O._stream()),
-                "efts_pack_t")
+        O.pack_t(x_ptr, ldx, xts, rows, cin, kpad, shift=-pad, taps=taps, tap_stride=xts.plane_bytes)
         O.gemm(a=zt, b_ptr=xts.ptr, ldb=xts.ld, m=cout, n=cin, batch=S, nchunk=nch, a_batch_stride=nch * 128, b_batch_stride=nch * 128,
                out_f32_ptr=part.data_ptr(), ldo=cin, out_batch_stride=cout * cin, batch2=taps, b_batch2_stride=xts.plane_bytes,
                out_batch2_stride=S * cout * cin)
-        L.check(_lib().efts_wgrad_reduce(part.data_ptr(), S, _ptr(v), _ptr(g), out_dw.data_ptr(), _ptr(out_dg), cout, cin, taps,
-                                         O._stream()), "efts_wgrad_reduce")
+        O.wgrad_reduce(part, S, v, g, out_dw, out_dg, cout, cin, taps)
 
     def _wgrad_group(self, ws, items, cout, cin, rows, taps: int, split: int, wgs: Optional[int] = None):
         """the direct weight gradients of several layers of one stack (same shape, same row space) as ONE stream-K launch and ONE
@@ -227,21 +259,9 @@ class TrainEngine:
             for i in range(0, len(items), L.WGRAD_MAX_ITEMS):
                 self._wgrad_group(ws, items[i:i + L.WGRAD_MAX_ITEMS], cout, cin, rows, taps, split, wgs)
             return
-        lib = _lib()
-        n = len(items)
-        wgs = _WGRAD_GROUP_WGS if not wgs else wgs
-        arr = (L.WgradItem * n)()
-        for a, (dz_p, x_p, v, g, dw, dg, bp, db) in zip(arr, items):
-            a.dz_plane, a.ldz, a.x_plane, a.ldx = dz_p.ptr, dz_p.ld, x_p.ptr, x_p.ld
-            a.v, a.g, a.dw_or_dv, a.dg = _ptr(v), _ptr(g), dw.data_ptr(), _ptr(dg)
-            a.bias_part, a.dbias, a.nparts = _ptr(bp), _ptr(db), 0 if bp is None else bp.shape[0]
-        nbytes = lib.efts_wgrad_grouped_part_bytes(n, rows, cout, cin, taps, split, wgs)
-        if nbytes < 0:
-            L.check(-1, "efts_wgrad_grouped_part_bytes")
-        part = ws.get(("gpart", self._ws_tag, n, rows, cout, cin, taps, split, wgs), lambda: torch.empty(nbytes // 4, device=self.dev))
-        L.check(lib.efts_wgrad_tn_grouped(arr, n, part.data_ptr(), rows, cout, cin, taps, split, wgs, O._stream()), "efts_wgrad_tn_grouped")
-        L.check(lib.efts_wgrad_reduce_grouped(arr, n, part.data_ptr(), rows, cout, cin, taps, split, wgs, O._stream()),
-                "efts_wgrad_reduce_grouped")
+        n, wgs = len(items), _WGRAD_GROUP_WGS if not wgs else wgs
+        key = ("gpart", self._ws_tag, n, rows, cout, cin, taps, split, wgs)
+        O.wgrad_grouped(items, rows, cout, cin, taps, split, wgs, lambda nbytes: ws.get(key, lambda: torch.empty(nbytes // 4, device=self.dev)))
 
     @staticmethod
     def _narrow_ok(dz_split: int, x_split: int, cout: int, cin: int, ldz: int, ldx: int) -> bool:
@@ -316,12 +336,17 @@ class TrainEngine:
         if st is None:
             yield
             return
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.dev))
-        st.wait_event(ev)
+        _hand_over(torch.cuda.current_stream(self.dev), st)
+        with self._on(st, "w"):                 # (scratch of its own: the other streams run weight gradients at the same time)
+            yield
+
+    @contextlib.contextmanager
+    def _on(self, st, tag: str = "s"):
+        """launches of the body go to stream `st` and take their scratch from the namespace `tag` ("s": the text-side stream, which
+        runs weight gradients at the same time as the main one)"""
         keep_tag = self._ws_tag
         with O.on_stream(st):
-            self._ws_tag = "w"                  # (scratch of its own: the other streams run weight gradients at the same time)
+            self._ws_tag = tag
             try:
                 yield
             finally:
@@ -358,9 +383,9 @@ class TrainEngine:
                     bp = None
                     O.act_grad(m.act_general, G.ptr, sg[0].ptr, gap_ptr, dz_f, dz_p, self.g[pre + "bias"], rs.rows, C, dp, dseed)
                 elif sg is not None:                                 # (sign words of efts_gemm: mode 4; sign bits of efts_resconv5: mode 5)
-                    self._act_bwd(G.ptr, sg[0].data_ptr(), None, gap_ptr, sg[1] | parts, dz_f, dz_p, db, rs.rows, C, dp, dseed)
+                    O.act_bwd_dropout(G.ptr, sg[0].data_ptr(), None, gap_ptr, m.slope, sg[1] | parts, dz_f, dz_p, db, rs.rows, C, dp, dseed)
                 else:
-                    self._act_bwd(G.ptr, y_f.ptr, x_f.ptr, gap_ptr, 1 | parts, dz_f, dz_p, db, rs.rows, C, dp, dseed)
+                    O.act_bwd_dropout(G.ptr, y_f.ptr, x_f.ptr, gap_ptr, m.slope, 1 | parts, dz_f, dz_p, db, rs.rows, C, dp, dseed)
             wn = hasattr(conv, "weight_g")
             v_, g_ = (conv.weight_v.detach(), conv.weight_g.detach()) if wn else (None, None)
             dw_, dg_ = (self.g[pre + "weight_v"], self.g[pre + "weight_g"]) if wn else (self.g[pre + "weight"], None)
@@ -404,15 +429,116 @@ class TrainEngine:
         with O.stream_scope():
             return self._forward_backward(text, text_lengths, speech, speech_lengths, gscale, keep)
 
+    def _mark(self, name: str):
+        if self.mark is not None:
+            self.mark(name)
+
     def _forward_backward(self, text, text_lengths, speech, speech_lengths, gscale, keep):
+        """The schedule of the step: every stage call, stream fork and join, bucket hand-over and timing mark, in order.  Its only
+        device work of its own is the repack's two phases and the zeroing of the gradient buffer; every other launch is in a stage.
+        Three HIP streams.  The text-length work (embedding, text encoder, K/V, duration predictor and all of their backward) runs on
+        ~B*T1 = 4k rows: launches of 70-270 workgroups that leave most of the chip idle.  None of it depends on the mel-length work
+        except through K/V (forward) and dK/dV/d(dur) (backward), so it goes to the `side` stream and fills the idle CUs / tail rounds
+        of the mel-length kernels on `main`.  The mel-length weight gradients go to `wst` (the stages' `wgrad_stream`, forked inside them
+        by _forked behind their operands; joined here)."""
         m = self.m
-        dev = self.dev
         L.require_device()
+        st = self._begin_step(text, text_lengths, speech, speech_lengths, gscale)       # masks on main
+        main, side, wst = st.main, st.side, st.wst
+        wst2 = wst if (_WGRAD_STREAM & 2) else None
+        # the repack of the operand planes (weight-norm fold + bf16 planes + dgrad planes, ~110 us on one stream): the text-side planes on
+        # the stream the text side runs on, the mel-side planes here -- both behind the masks and the previous step's optimizer
+        side.wait_stream(main)
+        st.pk = self._prepare_weights()
+        m.planes.issue("me")
+        with self._on(side):
+            m.planes.issue("te")
+        self.flat.zero_()
+        self._mark("step_start")
+
+        # ============================ forward (efficient_tts.py:144-227), activations kept
+        with self._on(side):
+            tx = self._fwd_text(st)
+            ev_kv = _hand_over(side)
+            du = self._fwd_duration(st, tx)                          # needs V only
+            ev_dur = _hand_over(side)
+        mf = self._fwd_mel(st)
+        self._mark("fwd_mel_encoder_done")
+        main.wait_event(ev_kv)                                      # K, V from the side stream, behind the mel encoder
+        al = self._fwd_alignment(st, mf, tx)
+        self._mark("fwd_alignment_done")
+        dec = self._fwd_expand_decoder(st, al, tx)
+        self._mark("fwd_decoder_done")
+        mel = self._fwd_head(st, dec)
+        main.wait_event(ev_dur)                                     # predicted durations from the side stream
+        lo = self._fwd_losses(st, mel, du, al)
+        self.last = _StepOutputs(al.imv, al.ralpha, mel)
+
+        # ============================ backward
+        self._mark("backward_start")
+        lb = self._bwd_loss(st, mel, du, al, lo)
+        _hand_over(main, side)                                      # d(dur) is ready
+        with self._on(side):
+            dV_dur = self._bwd_duration(st, du, tx, lb)
+            ev_durb = _hand_over(side)
+            pa = self._bwd_operand_packs(st, tx, mf, al)
+            ev_packs = _hand_over(side)
+        dH, dH_p = self._bwd_head_decoder(st, lb, dec, wst2, wst if (_WGRAD_STREAM & 1) else None)
+        self._mark("bwd_decoder_done")
+        if self.bucket_hook and wst is None:
+            self.bucket_hook(0)
+        main.wait_event(ev_packs)
+        dAp, dHt, dv = self._bwd_dalpha(st, pa, dH_p)                 # dv: buffers only (allocated here to keep the order); _bwd_dv fills them
+        ev_gv = None
+        if _GV_ON_SIDE and m.side_stream and not torch.cuda.is_current_stream_capturing():
+            # nothing between here and dK reads dV: the branch runs on the text-side stream (idle until dK / dV exist, and the consumer of
+            # both) beside the chain d alpha' -> ... -> dQ, dK instead of in front of it; a capturing pass keeps it here (see _GV_ON_SIDE)
+            _hand_over(main, side)                                   # dH
+            with self._on(side):
+                self._bwd_dv(st, dH, dHt, pa, dV_dur, dv)            # (dV_dur and alpha' as an operand were produced on this stream)
+                ev_gv = _hand_over(side)
+        else:
+            main.wait_event(ev_durb)                                 # dV of the duration predictor (and its gradients: bucket 1)
+            self._bwd_dv(st, dH, dHt, pa, dV_dur, dv)
+        ab = self._bwd_alignment(st, al, dAp, pa)
+        if ev_gv is not None:
+            main.wait_event(ev_gv)                                   # (shared: dV is the residual of the next launch; else: one join for everything behind)
+        GK, GK_p = self._bwd_dk(st, ab, pa, dv)
+        ev_gk = _hand_over(main)
+        self._mark("bwd_alignment_done")
+        side.wait_event(ev_gk)                                      # dK, dV are ready
+        if wst is not None and self.bucket_hook:
+            # data parallel: bucket 0 (mel head + decoder) is final once the decoder's weight gradients are through; its exchange then
+            # overlaps the encoders' backward instead of the alignment block's as well
+            main.wait_stream(wst)
+            self.bucket_hook(0)
+        with self._on(side):
+            Ge = self._bwd_text(st, tx, dv, GK, GK_p)
+        Gm = self._bwd_mel_encoder(st, mf, ab.GQ, wst2)
+        self._mark("bwd_mel_encoder_done")
+        self._bwd_prenet(st, mf, Gm, wst2)
+        if self.bucket_hook:
+            if wst is not None:
+                main.wait_stream(wst)
+            self.bucket_hook(1)
+        main.wait_stream(side)                                      # text-side gradients (bucket 2) and everything else enqueued there
+        if wst is not None and not self.bucket_hook:
+            main.wait_stream(wst)                                   # the weight gradients of the mel-length layers
+        if self.bucket_hook:
+            self.bucket_hook(2)
+        aux = None
+        if keep:
+            aux = dict(imv=al.imv, ralpha=al.ralpha, mel=mel, e=al.e, dH=dH, dAp=dAp, de=ab.de, dpi=ab.dpi, dsx=ab.dsx, dS=ab.dS, GQ=ab.GQ,
+                       GK=GK, GV=dv.GV, Gm=Gm, Ge=Ge, rs1=st.rs1, rs2=st.rs2, ddur=lb.ddur)
+        return lo.out3, aux
+
+    # ------------------------------------------------------------------ the stages of the step (launches; no join, and no fork but _forked to the `wgrad_stream` a stage is given)
+    def _begin_step(self, text, text_lengths, speech, speech_lengths, gscale) -> _Step:
+        """workspace, row spaces, masks (launched on the current stream), streams and the step's Dropout words"""
+        m, dev = self.m, self.dev
         B, T1 = text.shape
         T2 = speech.shape[1]
-        C, odim, split = m.n_channels, m.odim, m.split
-        text = text.contiguous()
-        speech = speech.contiguous().float()
+        text, speech = text.contiguous(), speech.contiguous().float()
         ws = m._workspace(("train", B, T1, T2), dev)
         rs1, rs2 = Rows(B, T1, m.row_gap), Rows(B, T2, m.row_gap)
         gap1, len1 = ws.tensor("gap1", (rs1.rows,)), ws.tensor("len1", (rs1.rows,))
@@ -424,29 +550,9 @@ class TrainEngine:
             tl, ml = tl_.to(torch.int32), ml_.to(torch.int32)
             O.row_masks(tl, rs1, gap1, len1)
             O.row_masks(ml, rs2, gap2, len2)
-        # the repack of the operand planes (weight-norm fold + bf16 planes + dgrad planes, ~110 us on one stream): the text-side planes on
-        # the stream the text side runs on, the mel-side planes here -- both behind the masks and the previous step's optimizer
-        side0 = m._side_stream(dev)
-        side0.wait_stream(torch.cuda.current_stream(dev))
-        pk = self._prepare_weights()
-        m.planes.issue("me")
-        with O.on_stream(side0):
-            m.planes.issue("te")
-        self.flat.zero_()
-
-        # Two HIP streams.  The text-length work (embedding, text encoder, K/V, duration predictor and all of their
-        # backward) runs on ~B*T1 = 4k rows: launches of 70-270 workgroups that leave most of the chip idle.  None of it
-        # depends on the mel-length work except through K/V (forward) and dK/dV/d(dur) (backward), so it goes to a side
-        # stream and fills the idle CUs / tail rounds of the mel-length kernels; events mark the few hand-over points.
-        main = torch.cuda.current_stream(dev)
-        side = m._side_stream(dev)
-        if self.mark is not None:
-            self.mark("step_start")
-        dp = m.duration_predictor
-        ln0, ln1 = dp.conv[0][2], dp.conv[1][2]
         # Dropout(0.1) of the duration predictor is active in train() mode like the reference's
         # (duration_predictor.py:61; the model never forwards its own dropout_rate to it)
-        drop_p = float(dp.conv[0][3].p) if m.training else 0.0
+        drop_p = float(m.duration_predictor.conv[0][3].p) if m.training else 0.0
         # one mask family per (base seed, data-parallel rank, step counter): replicas draw different masks (the reference's ranks
         # have their own torch RNG streams); the trainer sets the counter to the step count when it loads a checkpoint, so that
         # --resume continues the sequence instead of replaying it
@@ -461,74 +567,83 @@ class TrainEngine:
         else:
             sadd = None
             seed0, seed1 = (self.seed_base + 2 * self.drop_calls) & 0xFFFFFFFF, (self.seed_base + 2 * self.drop_calls + 1) & 0xFFFFFFFF
+        return _Step(ws=ws, text=text, speech=speech, gscale=gscale, B=B, T1=T1, T2=T2, rs1=rs1, rs2=rs2,
+                     gap1=gap1, len1=len1, gap2=gap2, len2=len2, tl=tl, ml=ml, main=torch.cuda.current_stream(dev), side=m._side_stream(dev),
+                     wst=m._aux_stream(dev) if (_WGRAD_STREAM and m.side_stream) else None, drop_p=drop_p, seed0=seed0, seed1=seed1, sadd=sadd)
 
-        # ============================ forward (efficient_tts.py:144-227), activations kept
-        with O.on_stream(side):
-            self._ws_tag = "s"
-            emb_f, emb_p = ws.f32("Temb_f", rs1, C), ws.plane("Temb_p", rs1, C, split)
-            O.embed(text, m.text_embedding_table.weight.detach(), emb_f, emb_p, rs1)
-            te_f, te_p, te_saved = self._stack_fwd(ws, "te", "text_encoder", pk, rs1, emb_f, emb_p, gap1.data_ptr(), split)
-            key_f, key_p = ws.f32("Tkey_f", rs1, C), ws.plane("Tkey_p", rs1, C, 2)
-            val_f, val_p = ws.f32("Tval_f", rs1, C), ws.plane("Tval_p", rs1, C, split)
-            shared = m.share_text_encoder_key_value                 # efficient_tts.py:150-153: the value is the key projection
-            wk = pk["key"]
-            wv = wk if shared else pk["value"]
-            O.gemm(a=te_p, b_ptr=wk.ptr, ldb=wk.ld, m=rs1.rows, n=C, bias=m.text_encoder_key.bias, rowmask_ptr=len1.data_ptr(),
-                   out_f32_ptr=key_f.ptr, ldo=C, out_plane=key_p)
-            O.gemm(a=te_p, b_ptr=wv.ptr, ldb=wv.ld, m=rs1.rows, n=C, bias=(m.text_encoder_key if shared else m.text_encoder_value).bias,
-                   rowmask_ptr=len1.data_ptr(), out_f32_ptr=val_f.ptr, ldo=C, out_plane=val_p)
-            ev_kv = torch.cuda.Event()
-            ev_kv.record(side)
-            # duration predictor (efficient_tts.py:219): needs V only
-            h1_f, l1_f, l1_p = ws.f32("Tdur_h1", rs1, C), ws.f32("Tdur_l1", rs1, C), ws.plane("Tdur_l1p", rs1, C, split)
-            h2_f = ws.f32("Tdur_h2", rs1, C)
-            dur = ws.tensor("Tdur_out", (rs1.rows,))
-            w0, w1 = pk["dur.0"], pk["dur.1"]
-            O.gemm(a=val_p, b_ptr=w0.ptr, ldb=w0.ld, b_tap_stride=w0.tap_stride, taps=3, m=rs1.rows, n=C, act=L.ACT_RELU,
-                   bias=dp.conv[0][0].bias, out_f32_ptr=h1_f.ptr, ldo=C)
-            O.layernorm_rows(h1_f.ptr, ln0.weight.detach(), ln0.bias.detach(), ln0.eps, gap1.data_ptr(), l1_f.ptr, l1_p, rs1.rows, C,
-                             drop_p, seed0, sadd)
-            O.gemm(a=l1_p, b_ptr=w1.ptr, ldb=w1.ld, b_tap_stride=w1.tap_stride, taps=3, m=rs1.rows, n=C, act=L.ACT_RELU,
-                   bias=dp.conv[1][0].bias, out_f32_ptr=h2_f.ptr, ldo=C)
-            O.layernorm_dot(h2_f.ptr, ln1.weight.detach(), ln1.bias.detach(), ln1.eps, dp.linear.weight.detach(),
-                            dp.linear.bias.detach(), len1.data_ptr(), 0, float(dp.offset), dur, rs1.rows, C, drop_p, seed1, sadd)
-            ev_dur = torch.cuda.Event()
-            ev_dur.record(side)
-            self._ws_tag = ""
+    def _fwd_text(self, st: _Step) -> _TextFwd:
+        """embedding, text encoder, key / value Linears"""
+        m, ws, rs1, C, split = self.m, st.ws, st.rs1, self.m.n_channels, self.m.split
+        emb_f, emb_p = ws.f32("Temb_f", rs1, C), ws.plane("Temb_p", rs1, C, split)
+        O.embed(st.text, m.text_embedding_table.weight.detach(), emb_f, emb_p, rs1)
+        te_f, te_p, te_saved = self._stack_fwd(ws, "te", "text_encoder", st.pk, rs1, emb_f, emb_p, st.gap1.data_ptr(), split)
+        key_f, key_p = ws.f32("Tkey_f", rs1, C), ws.plane("Tkey_p", rs1, C, 2)
+        val_f, val_p = ws.f32("Tval_f", rs1, C), ws.plane("Tval_p", rs1, C, split)
+        shared = m.share_text_encoder_key_value                 # efficient_tts.py:150-153: the value is the key projection
+        wk = st.pk["key"]
+        wv = wk if shared else st.pk["value"]
+        O.gemm(a=te_p, b_ptr=wk.ptr, ldb=wk.ld, m=rs1.rows, n=C, bias=m.text_encoder_key.bias, rowmask_ptr=st.len1.data_ptr(),
+               out_f32_ptr=key_f.ptr, ldo=C, out_plane=key_p)
+        O.gemm(a=te_p, b_ptr=wv.ptr, ldb=wv.ld, m=rs1.rows, n=C, bias=(m.text_encoder_key if shared else m.text_encoder_value).bias,
+               rowmask_ptr=st.len1.data_ptr(), out_f32_ptr=val_f.ptr, ldo=C, out_plane=val_p)
+        return _TextFwd(te_f, te_p, te_saved, key_f, key_p, val_f, val_p)
 
+    def _fwd_duration(self, st: _Step, tx: _TextFwd) -> _DurFwd:
+        """duration predictor (efficient_tts.py:219) on V: two conv -> relu -> LayerNorm -> Dropout layers and the Linear"""
+        dp, ws, rs1, C = self.m.duration_predictor, st.ws, st.rs1, self.m.n_channels
+        ln0, ln1 = dp.conv[0][2], dp.conv[1][2]
+        h1_f, l1_f, l1_p = ws.f32("Tdur_h1", rs1, C), ws.f32("Tdur_l1", rs1, C), ws.plane("Tdur_l1p", rs1, C, self.m.split)
+        h2_f = ws.f32("Tdur_h2", rs1, C)
+        dur = ws.tensor("Tdur_out", (rs1.rows,))
+        w0, w1 = st.pk["dur.0"], st.pk["dur.1"]
+        O.gemm(a=tx.val_p, b_ptr=w0.ptr, ldb=w0.ld, b_tap_stride=w0.tap_stride, taps=3, m=rs1.rows, n=C, act=L.ACT_RELU,
+               bias=dp.conv[0][0].bias, out_f32_ptr=h1_f.ptr, ldo=C)
+        O.layernorm_rows(h1_f.ptr, ln0.weight.detach(), ln0.bias.detach(), ln0.eps, st.gap1.data_ptr(), l1_f.ptr, l1_p, rs1.rows, C,
+                         st.drop_p, st.seed0, st.sadd)
+        O.gemm(a=l1_p, b_ptr=w1.ptr, ldb=w1.ld, b_tap_stride=w1.tap_stride, taps=3, m=rs1.rows, n=C, act=L.ACT_RELU,
+               bias=dp.conv[1][0].bias, out_f32_ptr=h2_f.ptr, ldo=C)
+        O.layernorm_dot(h2_f.ptr, ln1.weight.detach(), ln1.bias.detach(), ln1.eps, dp.linear.weight.detach(),
+                        dp.linear.bias.detach(), st.len1.data_ptr(), 0, float(dp.offset), dur, rs1.rows, C, st.drop_p, st.seed1, st.sadd)
+        return _DurFwd(h1_f, l1_f, l1_p, h2_f, dur)
+
+    def _fwd_mel(self, st: _Step) -> _MelFwd:
+        """prenet, mel encoder and, where the model has one, the query fc"""
+        m, ws, rs2, C, odim, split = self.m, st.ws, st.rs2, self.m.n_channels, self.m.odim, self.m.split
+        gap2 = st.gap2.data_ptr()
         mel_in_f, mel_in = ws.f32("Tmel_in_f", rs2, odim), ws.plane("Tmel_in", rs2, odim, split)
-        O.pack_rows(speech, mel_in_f, mel_in, rs2)                  # (the backward's wgrad of the prenet reads both)
+        O.pack_rows(st.speech, mel_in_f, mel_in, rs2)               # (the backward's wgrad of the prenet reads both)
         pre_f, pre_p = ws.f32("Tpre_f", rs2, C), ws.plane("Tpre_p", rs2, C, split)
-        wp = pk["prenet"]
+        wp = st.pk["prenet"]
         pre_dp, pre_seed = self._conv_drop(40)                       # mel_prenet's Dropout (efficient_tts.py:76-80)
         pre_z = None
         if m.act_general is not None:
             pre_z = ws.f32("Tpre_z", rs2, C)
             O.gemm(a=mel_in, b_ptr=wp.ptr, ldb=wp.ld, m=rs2.rows, n=C, bias=m.mel_prenet[0].bias, out_f32_ptr=pre_z.ptr, ldo=C)
-            O.act_apply(m.act_general, pre_z.ptr, None, gap2.data_ptr(), pre_f, pre_p, rs2.rows, C, pre_dp, pre_seed)
+            O.act_apply(m.act_general, pre_z.ptr, None, gap2, pre_f, pre_p, rs2.rows, C, pre_dp, pre_seed)
         elif pre_dp == 0.0 and m.fuse_prenet and odim % 8 == 0 and odim <= 128 and C % 128 == 0:
             # no Dropout on the prenet (the shipped recipe): straight from the caller's frames, whole-line stores (efts_frame_linear;
             # bit-identical to the launch below)
-            O.frame_linear(x=speech, w=wp, bias=m.mel_prenet[0].bias, act=L.ACT_LEAKY, slope=m.slope, rs=rs2, y=pre_p, y_f32=pre_f)
+            O.frame_linear(x=st.speech, w=wp, bias=m.mel_prenet[0].bias, act=L.ACT_LEAKY, slope=m.slope, rs=rs2, y=pre_p, y_f32=pre_f)
         else:
             O.gemm(a=mel_in, b_ptr=wp.ptr, ldb=wp.ld, m=rs2.rows, n=C, act=L.ACT_LEAKY, slope=m.slope, bias=m.mel_prenet[0].bias,
-                   rowmask_ptr=gap2.data_ptr(), out_f32_ptr=pre_f.ptr, ldo=C, out_plane=pre_p, drop_p=pre_dp, drop_seed=pre_seed)
+                   rowmask_ptr=gap2, out_f32_ptr=pre_f.ptr, ldo=C, out_plane=pre_p, drop_p=pre_dp, drop_seed=pre_seed)
         if m.mel_query_fc is None:
-            q_f, q_p, me_saved = self._stack_fwd(ws, "me", "mel_encoder", pk, rs2, pre_f, pre_p, gap2.data_ptr(), 2)
+            mh_f = mh_p = None
+            q_f, q_p, me_saved = self._stack_fwd(ws, "me", "mel_encoder", st.pk, rs2, pre_f, pre_p, gap2, 2)
         else:                                                       # efficient_tts.py:163-164: Linear(C, C) in front of the attention
-            mh_f, mh_p, me_saved = self._stack_fwd(ws, "me", "mel_encoder", pk, rs2, pre_f, pre_p, gap2.data_ptr(), split)
+            mh_f, mh_p, me_saved = self._stack_fwd(ws, "me", "mel_encoder", st.pk, rs2, pre_f, pre_p, gap2, split)
             q_f, q_p = ws.f32("Tq_f", rs2, C), ws.plane("Tq_p", rs2, C, 2)
-            wq = pk["qfc"]
-            O.gemm(a=mh_p, b_ptr=wq.ptr, ldb=wq.ld, m=rs2.rows, n=C, bias=m.mel_query_fc.bias, rowmask_ptr=gap2.data_ptr(),
+            wq = st.pk["qfc"]
+            O.gemm(a=mh_p, b_ptr=wq.ptr, ldb=wq.ld, m=rs2.rows, n=C, bias=m.mel_query_fc.bias, rowmask_ptr=gap2,
                    out_f32_ptr=q_f.ptr, ldo=C, out_plane=q_p)
-        if self.mark is not None:
-            self.mark("fwd_mel_encoder_done")
+        return _MelFwd(mel_in_f, mel_in, pre_f, pre_z, (pre_dp, pre_seed), mh_f, mh_p, q_f, q_p, me_saved)
 
-        main.wait_event(ev_kv)                                      # K, V from the side stream
-        scale = O.INV_SQRT(C)
+    def _fwd_alignment(self, st: _Step, mf: _MelFwd, tx: _TextFwd) -> _AlignFwd:
+        """scores -> soft index -> IMV -> aligned positions e and the duration target; alpha' itself only where the expand is not fused"""
+        m, ws, B, T1, T2, tl, ml, rs1, rs2 = self.m, st.ws, st.B, st.T1, st.T2, st.tl, st.ml, st.rs1, st.rs2
         scores = ws.tensor("Tscores", (B, T2, T1))
-        O.gemm(a=q_p, b_ptr=key_p.ptr, ldb=key_p.ld, m=T2, n=T1, batch=B, a_batch_stride=rs2.Tp * q_p.ld,
-               b_batch_stride=rs1.Tp * key_p.ld, alpha=scale, out_f32_ptr=scores.data_ptr(), ldo=T1, out_batch_stride=T2 * T1)
+        O.gemm(a=mf.q_p, b_ptr=tx.key_p.ptr, ldb=tx.key_p.ld, m=T2, n=T1, batch=B, a_batch_stride=rs2.Tp * mf.q_p.ld,
+               b_batch_stride=rs1.Tp * tx.key_p.ld, alpha=O.INV_SQRT(m.n_channels), out_f32_ptr=scores.data_ptr(), ldo=T1, out_batch_stride=T2 * T1)
         sidx, imv = ws.tensor("Tsidx", (B, T2)), ws.tensor("Timv", (B, T2))
         O.attn_soft_index(scores, T1, tl, ml, sidx, None, B, T1, T2)
         e, lde = ws.tensor("Te", (B, T1)), ws.tensor("Tlde", (B, T1))
@@ -540,258 +655,215 @@ class TrainEngine:
             if not m.delta_e_method_1:                               # efficient_tts.py:205-213 (the target is detached either way)
                 O.duration_target(e, tl, ml, float(m.duration_offset), False, lde, B, T1)
         ralpha = ws.tensor("Tralpha", (B, T1, T2))
-        h_f, h_p = ws.f32("Texp_f", rs2, C), ws.plane("Texp_p", rs2, C, split)
-        if m._fused_expand(T1):
-            # alpha' produced in registers inside the expand contraction (efts_expand); the backward packs its own operands from
-            # the fp32 alpha' kept here
-            if self.mark is not None:
-                self.mark("fwd_alignment_done")
-            O.expand(e=e, tl=tl, ml=ml, sigma=float(m.sigma), v=val_f, rs1=rs1, rs2=rs2, alpha_out=ralpha, y_f32=h_f, y=h_p)
-        else:
+        h_f, h_p = ws.f32("Texp_f", rs2, m.n_channels), ws.plane("Texp_p", rs2, m.n_channels, m.split)
+        ra_p = None
+        if not m._fused_expand(T1):
             ra_p = ws.plane("Tra_p", rs2, T1, 2)
             O.reconst_alpha(e, tl, ml, float(m.sigma), ralpha, ra_p, B, T1, T2, rs2.Tp)
-            if self.mark is not None:
-                self.mark("fwd_alignment_done")
+        return _AlignFwd(scores, sidx, imv, e, lde, ralpha, ra_p, h_f, h_p)
+
+    def _fwd_expand_decoder(self, st: _Step, al: _AlignFwd, tx: _TextFwd) -> _DecFwd:
+        """H = alpha'^T V, then the decoder"""
+        m, ws, B, T1, T2, rs1, rs2, C = self.m, st.ws, st.B, st.T1, st.T2, st.rs1, st.rs2, self.m.n_channels
+        h_f, h_p = al.h_f, al.h_p
+        if al.ra_p is None:
+            # alpha' produced in registers inside the expand contraction (efts_expand); the backward packs its own operands from
+            # the fp32 alpha' kept here
+            O.expand(e=al.e, tl=st.tl, ml=st.ml, sigma=float(m.sigma), v=tx.val_f, rs1=rs1, rs2=rs2, alpha_out=al.ralpha, y_f32=h_f, y=h_p)
+        else:
             vt = ws.raw_plane("Tvt", B * C + 136, T1, 2)
-            O.pack_vt(val_f, vt, B, T1, rs1.Tp, C)
-            O.gemm(a=ra_p, b_ptr=vt.ptr, ldb=vt.ld, m=T2, n=C, batch=B, a_batch_stride=rs2.Tp * ra_p.ld, b_batch_stride=C * vt.ld,
-                   rowmask_ptr=len2.data_ptr(), rowmask_batch_stride=rs2.Tp, out_f32_ptr=h_f.ptr, ldo=C, out_batch_stride=rs2.Tp * C,
+            O.pack_vt(tx.val_f, vt, B, T1, rs1.Tp, C)
+            O.gemm(a=al.ra_p, b_ptr=vt.ptr, ldb=vt.ld, m=T2, n=C, batch=B, a_batch_stride=rs2.Tp * al.ra_p.ld, b_batch_stride=C * vt.ld,
+                   rowmask_ptr=st.len2.data_ptr(), rowmask_batch_stride=rs2.Tp, out_f32_ptr=h_f.ptr, ldo=C, out_batch_stride=rs2.Tp * C,
                    out_plane=h_p, outb_batch_stride=rs2.Tp * h_p.ld)
-        d_f, d_p, dec_saved = self._stack_fwd(ws, "dec", "decoder", pk, rs2, h_f, h_p, gap2.data_ptr(), split)
-        if self.mark is not None:
-            self.mark("fwd_decoder_done")
-        mel = ws.f32("Tmel_pred", rs2, odim)
-        wh = pk["head"]
-        O.gemm(a=d_p, b_ptr=wh.ptr, ldb=wh.ld, m=rs2.rows, n=odim, bias=m.mel_output_layer.bias, rowmask_ptr=len2.data_ptr(),
-               out_f32_ptr=mel.ptr, ldo=odim)
+        return _DecFwd(*self._stack_fwd(ws, "dec", "decoder", st.pk, rs2, h_f, h_p, st.gap2.data_ptr(), m.split))
 
-        main.wait_event(ev_dur)                                     # predicted durations from the side stream
-        out3 = torch.empty(3, dtype=torch.float32, device=dev)
+    def _fwd_head(self, st: _Step, dec: _DecFwd) -> F32Rows:
+        m, rs2 = self.m, st.rs2
+        mel = st.ws.f32("Tmel_pred", rs2, m.odim)
+        wh = st.pk["head"]
+        O.gemm(a=dec.d_p, b_ptr=wh.ptr, ldb=wh.ld, m=rs2.rows, n=m.odim, bias=m.mel_output_layer.bias, rowmask_ptr=st.len2.data_ptr(),
+               out_f32_ptr=mel.ptr, ldo=m.odim)
+        return mel
+
+    def _fwd_losses(self, st: _Step, mel: F32Rows, du: _DurFwd, al: _AlignFwd) -> _LossFwd:
+        m = self.m
+        out3 = torch.empty(3, dtype=torch.float32, device=self.dev)
         # use_masking=False (fastspeech_loss.py:63-67): means over the padded tensors = the masked sums taken with full lengths
-        ml_loss = ml if m.use_masking else torch.full_like(ml, T2)
-        tl_loss = tl if m.use_masking else torch.full_like(tl, T1)
-        O.masked_losses(mel.ptr, odim, speech, ml_loss, dur, lde, tl_loss, out3, ws.tensor("loss_ws", (1024,)), B, T1, rs1.Tp, T2, rs2.Tp, odim)
+        ml_loss = st.ml if m.use_masking else torch.full_like(st.ml, st.T2)
+        tl_loss = st.tl if m.use_masking else torch.full_like(st.tl, st.T1)
+        O.masked_losses(mel.ptr, m.odim, st.speech, ml_loss, du.dur, al.lde, tl_loss, out3, st.ws.tensor("loss_ws", (1024,)), st.B, st.T1, st.rs1.Tp,
+                        st.T2, st.rs2.Tp, m.odim)
+        return _LossFwd(out3, ml_loss, tl_loss)
 
-        # ============================ backward
-        if self.mark is not None:
-            self.mark("backward_start")
-        g = self.g
-        dmel_f = ws.f32("Bdmel_f", rs2, odim)
-        dmel_p = ws.plane("Bdmel_p", rs2, odim, split)
-        ddur = ws.tensor("Bddur", (rs1.rows,))
-        L.check(_lib().efts_loss_bwd(mel.ptr, odim, speech.data_ptr(), ml_loss.data_ptr(), dur.data_ptr(), lde.data_ptr(), tl_loss.data_ptr(),
-                                     _ptr(gscale), dmel_f.ptr, None, 0, split, ddur.data_ptr(), B, T1, rs1.Tp, T2, rs2.Tp, odim,
-                                     O._stream()), "efts_loss_bwd")
-        ev_loss = torch.cuda.Event()
-        ev_loss.record(main)
-        side.wait_event(ev_loss)                                    # d(dur) is ready
-        with O.on_stream(side):
-            self._ws_tag = "s"
-            # ---- duration predictor (input text_value is NOT detached: efficient_tts.py:219)
-            def gname(i, k):
-                return f"duration_predictor.conv.{i}.{k}"
-            dz2_f, dz2_p = ws.f32("Bdur_dz2", rs1, C), ws.plane("Bdur_dz2p", rs1, C, split)
-            L.check(_lib().efts_layernorm_bwd(h2_f.ptr, ln1.weight.data_ptr(), ln1.bias.data_ptr(), ln1.eps, None, ddur.data_ptr(),
-                                              dp.linear.weight.data_ptr(), None, dz2_f.ptr, dz2_p.ptr, dz2_p.ld, split,
-                                              g[gname(1, "2.weight")].data_ptr(), g[gname(1, "2.bias")].data_ptr(),
-                                              g[gname(1, "0.bias")].data_ptr(), g["duration_predictor.linear.weight"].data_ptr(),
-                                              g["duration_predictor.linear.bias"].data_ptr(), rs1.rows, C, drop_p, seed1, sadd, O._stream()),
-                    "efts_layernorm_bwd")
-            dur_items = []                                           # both k3 weight gradients in one grouped launch, below
-            self._wgrad_any(ws, dz2_f.ptr, dz2_p, l1_f.ptr, l1_p, C, C, 3, rs1.rows, g[gname(1, "0.weight")], defer=dur_items)
-            G1 = ws.f32("Bdur_G1", rs1, C)
-            wt = self.wt["dur.1"]
-            O.gemm(a=dz2_p, b_ptr=wt.ptr, ldb=wt.ld, b_tap_stride=wt.tap_stride, taps=3, m=rs1.rows, n=C, out_f32_ptr=G1.ptr, ldo=C)
-            dz1_f, dz1_p = ws.f32("Bdur_dz1", rs1, C), ws.plane("Bdur_dz1p", rs1, C, split)
-            L.check(_lib().efts_layernorm_bwd(h1_f.ptr, ln0.weight.data_ptr(), ln0.bias.data_ptr(), ln0.eps, G1.ptr, None, None,
-                                              gap1.data_ptr(), dz1_f.ptr, dz1_p.ptr, dz1_p.ld, split,
-                                              g[gname(0, "2.weight")].data_ptr(), g[gname(0, "2.bias")].data_ptr(),
-                                              g[gname(0, "0.bias")].data_ptr(), None, None, rs1.rows, C, drop_p, seed0, sadd, O._stream()),
-                    "efts_layernorm_bwd")
-            self._wgrad_any(ws, dz1_f.ptr, dz1_p, val_f.ptr, val_p, C, C, 3, rs1.rows, g[gname(0, "0.weight")], defer=dur_items)
-            if dur_items:
-                self._wgrad_group(ws, dur_items, C, C, rs1.rows, 3, split)
-            dV_dur = ws.f32("BdV_dur", rs1, C)
-            wt = self.wt["dur.0"]
-            O.gemm(a=dz1_p, b_ptr=wt.ptr, ldb=wt.ld, b_tap_stride=wt.tap_stride, taps=3, m=rs1.rows, n=C, out_f32_ptr=dV_dur.ptr, ldo=C)
-            ev_durb = torch.cuda.Event()
-            ev_durb.record(side)
-            # operand copies of the alignment backward that depend on forward tensors only (V as an A operand, alpha' as an A operand,
-            # K^T, Q^T): this stream idles through the decoder's backward, the main one would run them one after the other in front of
-            # their GEMMs
-            val_p2 = ws.plane("Bval_p2", rs1, C, 2)
-            L.check(_lib().efts_pack_rows(val_f.ptr, None, val_p2.ptr, val_p2.ld, B, rs1.Tp, rs1.Tp, C, C, 2, O._stream()), "efts_pack_rows")
-            ra1_p = ws.plane("Bra1_p", rs1, T2, 2)
-            O.pack_rows(ralpha, None, ra1_p, rs1)
-            kt = ws.raw_plane("Bkt", B * C + 136, T1, 2)
-            O.pack_vt(key_f, kt, B, T1, rs1.Tp, C)
-            qt = ws.raw_plane("Bqt", B * C + 136, T2, 2)
-            O.pack_vt(q_f, qt, B, T2, rs2.Tp, C)
-            ev_packs = torch.cuda.Event()
-            ev_packs.record(side)
-            self._ws_tag = ""
-        # mel head (Linear 512->80, masked): bias grad + operand plane, wgrad, dgrad
+    def _bwd_loss(self, st: _Step, mel: F32Rows, du: _DurFwd, al: _AlignFwd, lo: _LossFwd) -> _LossBwd:
+        m, ws, odim = self.m, st.ws, self.m.odim
+        dmel_f = ws.f32("Bdmel_f", st.rs2, odim)
+        dmel_p = ws.plane("Bdmel_p", st.rs2, odim, m.split)
+        ddur = ws.tensor("Bddur", (st.rs1.rows,))
+        O.loss_bwd(mel.ptr, odim, st.speech, lo.ml_loss, du.dur, al.lde, lo.tl_loss, st.gscale, dmel_f.ptr, None, ddur,
+                   st.B, st.T1, st.rs1.Tp, st.T2, st.rs2.Tp, odim, split=m.split)
+        return _LossBwd(dmel_f, dmel_p, ddur)
+
+    def _bwd_duration(self, st: _Step, du: _DurFwd, tx: _TextFwd, lb: _LossBwd) -> F32Rows:
+        """duration predictor (its input text_value is NOT detached: efficient_tts.py:219); returns its gradient w.r.t. V"""
+        dp, ws, rs1, C, split, g = self.m.duration_predictor, st.ws, st.rs1, self.m.n_channels, self.m.split, self.g
+        ln0, ln1 = dp.conv[0][2], dp.conv[1][2]
+
+        def gname(i, k):
+            return g[f"duration_predictor.conv.{i}.{k}"]
+        dz2_f, dz2_p = ws.f32("Bdur_dz2", rs1, C), ws.plane("Bdur_dz2p", rs1, C, split)
+        O.layernorm_bwd(du.h2_f.ptr, ln1.weight, ln1.bias, ln1.eps, None, lb.ddur, dp.linear.weight, None, dz2_f.ptr, dz2_p,
+                        gname(1, "2.weight"), gname(1, "2.bias"), gname(1, "0.bias"), g["duration_predictor.linear.weight"],
+                        g["duration_predictor.linear.bias"], rs1.rows, C, st.drop_p, st.seed1, st.sadd)
+        dur_items = []                                           # both k3 weight gradients in one grouped launch, below
+        self._wgrad_any(ws, dz2_f.ptr, dz2_p, du.l1_f.ptr, du.l1_p, C, C, 3, rs1.rows, gname(1, "0.weight"), defer=dur_items)
+        G1 = ws.f32("Bdur_G1", rs1, C)
+        wt = self.wt["dur.1"]
+        O.gemm(a=dz2_p, b_ptr=wt.ptr, ldb=wt.ld, b_tap_stride=wt.tap_stride, taps=3, m=rs1.rows, n=C, out_f32_ptr=G1.ptr, ldo=C)
+        dz1_f, dz1_p = ws.f32("Bdur_dz1", rs1, C), ws.plane("Bdur_dz1p", rs1, C, split)
+        O.layernorm_bwd(du.h1_f.ptr, ln0.weight, ln0.bias, ln0.eps, G1.ptr, None, None, st.gap1.data_ptr(), dz1_f.ptr, dz1_p,
+                        gname(0, "2.weight"), gname(0, "2.bias"), gname(0, "0.bias"), None, None, rs1.rows, C, st.drop_p, st.seed0, st.sadd)
+        self._wgrad_any(ws, dz1_f.ptr, dz1_p, tx.val_f.ptr, tx.val_p, C, C, 3, rs1.rows, gname(0, "0.weight"), defer=dur_items)
+        if dur_items:
+            self._wgrad_group(ws, dur_items, C, C, rs1.rows, 3, split)
+        dV_dur = ws.f32("BdV_dur", rs1, C)
+        wt = self.wt["dur.0"]
+        O.gemm(a=dz1_p, b_ptr=wt.ptr, ldb=wt.ld, b_tap_stride=wt.tap_stride, taps=3, m=rs1.rows, n=C, out_f32_ptr=dV_dur.ptr, ldo=C)
+        return dV_dur
+
+    def _bwd_operand_packs(self, st: _Step, tx: _TextFwd, mf: _MelFwd, al: _AlignFwd) -> _Packs:
+        """operand copies of the alignment backward that depend on forward tensors only: V and alpha' as A operands, K^T, Q^T (the side
+        stream idles through the decoder's backward; the main one would run them one after the other in front of their GEMMs)"""
+        ws, B, T1, T2, rs1, rs2, C = st.ws, st.B, st.T1, st.T2, st.rs1, st.rs2, self.m.n_channels
+        val_p2 = ws.plane("Bval_p2", rs1, C, 2)
+        O.pack_rows(tx.val_f, None, val_p2, rs1, kp=C)
+        ra1_p = ws.plane("Bra1_p", rs1, T2, 2)
+        O.pack_rows(al.ralpha, None, ra1_p, rs1)
+        kt = ws.raw_plane("Bkt", B * C + 136, T1, 2)
+        O.pack_vt(tx.key_f, kt, B, T1, rs1.Tp, C)
+        qt = ws.raw_plane("Bqt", B * C + 136, T2, 2)
+        O.pack_vt(mf.q_f, qt, B, T2, rs2.Tp, C)
+        return _Packs(val_p2, ra1_p, kt, qt)
+
+    def _bwd_head_decoder(self, st: _Step, lb: _LossBwd, dec: _DecFwd, head_wgrad_stream, dec_wgrad_stream) -> Tuple[F32Rows, Plane]:
+        """mel head (Linear 512->80, masked): bias grad + operand plane, wgrad, dgrad; then the decoder.  Returns dH, the gradient of the
+        decoder's input, masked like H (efficient_tts.py:193-194), in fp32 and as a split-2 plane"""
+        m, ws, rs2, C, odim, g = self.m, st.ws, st.rs2, self.m.n_channels, self.m.odim, self.g
         if m.use_masking:
-            dmel_m = dmel_f                                          # already zero beyond each item's length
-            self._act_bwd(dmel_f.ptr, None, None, None, 0, None, dmel_p, g["mel_output_layer.bias"], rs2.rows, odim)
+            dmel_m = lb.dmel_f                                       # already zero beyond each item's length
+            O.act_bwd_dropout(lb.dmel_f.ptr, None, None, None, m.slope, 0, None, lb.dmel_p, g["mel_output_layer.bias"], rs2.rows, odim)
         else:
             # the unmasked loss sees (0 - speech) on padded frames; mel_pred = masked_fill(head output) blocks that gradient (:199-200)
             dmel_m = ws.f32("Bdmel_m", rs2, odim)
-            self._act_bwd(dmel_f.ptr, None, None, len2.data_ptr(), 0, dmel_m, dmel_p, g["mel_output_layer.bias"], rs2.rows, odim)
-        wst = m._aux_stream(dev) if (_WGRAD_STREAM and m.side_stream) else None
-        wst2 = wst if (_WGRAD_STREAM & 2) else None
-        with self._forked(wst2):
-            if not self._wgrad_narrow(ws, "head", dmel_p, d_p, odim, C, rs2.rows, g["mel_output_layer.weight"]):
-                self._wgrad(ws, dmel_m.ptr, odim, d_f.ptr, C, C, 1, rs2.rows, None, None, g["mel_output_layer.weight"], None)
+            O.act_bwd_dropout(lb.dmel_f.ptr, None, None, st.len2.data_ptr(), m.slope, 0, dmel_m, lb.dmel_p, g["mel_output_layer.bias"], rs2.rows, odim)
+        with self._forked(head_wgrad_stream):
+            if not self._wgrad_narrow(ws, "head", lb.dmel_p, dec.d_p, odim, C, rs2.rows, g["mel_output_layer.weight"]):
+                self._wgrad(ws, dmel_m.ptr, odim, dec.d_f.ptr, C, C, 1, rs2.rows, None, None, g["mel_output_layer.weight"], None)
         G = ws.f32("Bdec_Gh", rs2, C)
         wt = self.wt["head"]
-        O.gemm(a=dmel_p, b_ptr=wt.ptr, ldb=wt.ld, m=rs2.rows, n=C, rowmask_ptr=gap2.data_ptr(), out_f32_ptr=G.ptr, ldo=C)
-        # decoder; its input gradient dH is masked like H (efficient_tts.py:193-194) and also emitted as a split-2 plane
+        O.gemm(a=lb.dmel_p, b_ptr=wt.ptr, ldb=wt.ld, m=rs2.rows, n=C, rowmask_ptr=st.gap2.data_ptr(), out_f32_ptr=G.ptr, ldo=C)
         dH_p = ws.plane("BdH_p", rs2, C, 2)
-        dH = self._stack_bwd(ws, "dec", "decoder", rs2, G, dec_saved, gap2.data_ptr(), len2.data_ptr(), dH_p, wgrad_stream=wst if (_WGRAD_STREAM & 1) else None)
-        if self.mark is not None:
-            self.mark("bwd_decoder_done")
-        if self.bucket_hook and wst is None:
-            self.bucket_hook(0)
+        dH = self._stack_bwd(ws, "dec", "decoder", rs2, G, dec.dec_saved, st.gap2.data_ptr(), st.len2.data_ptr(), dH_p, wgrad_stream=dec_wgrad_stream)
+        return dH, dH_p
 
-        # ---- expand bmm backward: d alpha' [B,T1,T2] and dV
-        main.wait_event(ev_packs)
+    def _bwd_dalpha(self, st: _Step, pa: _Packs, dH_p: Plane):
+        """expand backward, first half: d alpha' [B, T1, T2] = V . dH^T; also allocates the buffers of the second half (_bwd_dv), which
+        may run on another stream"""
+        ws, B, T1, T2, C = st.ws, st.B, st.T1, st.T2, self.m.n_channels
         dAp = ws.tensor("BdAp", (B, T1, T2))
-        O.gemm(a=val_p2, b_ptr=dH_p.ptr, ldb=dH_p.ld, m=T1, n=T2, batch=B, a_batch_stride=rs1.Tp * val_p2.ld,
-               b_batch_stride=rs2.Tp * dH_p.ld, out_f32_ptr=dAp.data_ptr(), ldo=T2, out_batch_stride=T1 * T2)
+        O.gemm(a=pa.val_p2, b_ptr=dH_p.ptr, ldb=dH_p.ld, m=T1, n=T2, batch=B, a_batch_stride=st.rs1.Tp * pa.val_p2.ld,
+               b_batch_stride=st.rs2.Tp * dH_p.ld, out_f32_ptr=dAp.data_ptr(), ldo=T2, out_batch_stride=T1 * T2)
         dHt = ws.raw_plane("BdHt", B * C + 136, T2, 2)              # dH^T per item: [B][C][K = j]
-        GV = ws.f32("BGV", rs1, C)
-        GV_p = ws.plane("BGV_p", rs1, C, split)
+        return dAp, dHt, _DV(ws.f32("BGV", st.rs1, C), ws.plane("BGV_p", st.rs1, C, self.m.split))
 
-        def dv_branch():                                             # dV = alpha' . dH (+ the duration predictor's dV): transpose of dH + one batched product
-            O.pack_vt(dH, dHt, B, T2, rs2.Tp, C)
-            O.gemm(a=ra1_p, b_ptr=dHt.ptr, ldb=dHt.ld, m=T1, n=C, batch=B, a_batch_stride=rs1.Tp * ra1_p.ld, b_batch_stride=C * dHt.ld,
-                   resid_ptr=dV_dur.ptr, ldr=C, resid_batch_stride=rs1.Tp * C, rowmask_ptr=len1.data_ptr(), rowmask_batch_stride=rs1.Tp,
-                   out_f32_ptr=GV.ptr, ldo=C, out_batch_stride=rs1.Tp * C, out_plane=GV_p, outb_batch_stride=rs1.Tp * GV_p.ld)
+    def _bwd_dv(self, st: _Step, dH: F32Rows, dHt: Plane, pa: _Packs, dV_dur: F32Rows, dv: _DV) -> None:
+        """expand backward, second half: dV = alpha' . dH (+ the duration predictor's dV): transpose of dH + one batched product"""
+        B, T1, T2, rs1, rs2, C, (GV, GV_p) = st.B, st.T1, st.T2, st.rs1, st.rs2, self.m.n_channels, dv
+        O.pack_vt(dH, dHt, B, T2, rs2.Tp, C)
+        O.gemm(a=pa.ra1_p, b_ptr=dHt.ptr, ldb=dHt.ld, m=T1, n=C, batch=B, a_batch_stride=rs1.Tp * pa.ra1_p.ld, b_batch_stride=C * dHt.ld,
+               resid_ptr=dV_dur.ptr, ldr=C, resid_batch_stride=rs1.Tp * C, rowmask_ptr=st.len1.data_ptr(), rowmask_batch_stride=rs1.Tp,
+               out_f32_ptr=GV.ptr, ldo=C, out_batch_stride=rs1.Tp * C, out_plane=GV_p, outb_batch_stride=rs1.Tp * GV_p.ld)
 
-        ev_gv = None
-        if _GV_ON_SIDE and m.side_stream and not torch.cuda.is_current_stream_capturing():
-            # nothing between here and dK reads dV: the branch runs on the text-side stream (idle until dK / dV exist, and the consumer of both)
-            # beside the chain d alpha' -> e -> pi -> soft index -> scores -> dQ, dK instead of in front of it.  Eager launches only: 3.51-3.63 -> 3.46-3.56 ms per
-            # step; captured into the step's hipGraph the extra branch costs 0.1 ms (3.41 vs 3.30 ms, bf16x3 6.55 vs 6.27: the replayed graph's stream
-            # assignment loses the overlap of the weight-gradient stream), so a capturing pass keeps the branch on the main stream
-            ev_dh = torch.cuda.Event()
-            ev_dh.record(main)
-            side.wait_event(ev_dh)
-            with O.on_stream(side):
-                dv_branch()                                          # (dV_dur and alpha' as an operand were produced on this stream)
-                ev_gv = torch.cuda.Event()
-                ev_gv.record(side)
-        else:
-            main.wait_event(ev_durb)                                 # dV of the duration predictor (and its gradients: bucket 1)
-            dv_branch()
-
-        # ---- alpha' -> e -> pi -> soft index -> scores
+    def _bwd_alignment(self, st: _Step, al: _AlignFwd, dAp: torch.Tensor, pa: _Packs) -> _AlignBwd:
+        """alpha' -> e -> pi -> soft index -> scores, then dQ = scale * dS K and dS^T as the operand of dK"""
+        m, ws, B, T1, T2, tl, ml, rs2, C = self.m, st.ws, st.B, st.T1, st.T2, st.tl, st.ml, st.rs2, self.m.n_channels
         de, dpi, dsx = ws.tensor("Bde", (B, T1)), ws.tensor("Bdpi", (B, T2)), ws.tensor("Bdsx", (B, T2))
-        L.check(_lib().efts_alpha_bwd(ralpha.data_ptr(), dAp.data_ptr(), e.data_ptr(), tl.data_ptr(), ml.data_ptr(), float(m.sigma),
-                                      ws.tensor("Br", (B, T2)).data_ptr(), de.data_ptr(), B, T1, T2, O._stream()), "efts_alpha_bwd")
-        L.check(_lib().efts_e_bwd(imv.data_ptr(), e.data_ptr(), de.data_ptr(), tl.data_ptr(), ml.data_ptr(), float(m.sigma_e),
-                                  ws.tensor("Bstats", (2, B, T1)).data_ptr(), dpi.data_ptr(), B, T1, T2, O._stream()), "efts_e_bwd")
-        L.check(_lib().efts_imv_bwd(sidx.data_ptr(), imv.data_ptr(), dpi.data_ptr(), tl.data_ptr(), ml.data_ptr(), dsx.data_ptr(), B, T2,
-                                    O._stream()), "efts_imv_bwd")
+        O.alpha_bwd(al.ralpha, dAp, al.e, tl, ml, float(m.sigma), ws.tensor("Br", (B, T2)), de, B, T1, T2)
+        O.e_bwd(al.imv, al.e, de, tl, ml, float(m.sigma_e), ws.tensor("Bstats", (2, B, T1)), dpi, B, T1, T2)
+        O.imv_bwd(al.sidx, al.imv, dpi, tl, ml, dsx, B, T2)
         dS = ws.tensor("BdS", (B, T2, T1))
         dS_p = ws.plane("BdS_p", rs2, T1, 2)
-        L.check(_lib().efts_attn_bwd(scores.data_ptr(), T1, sidx.data_ptr(), dsx.data_ptr(), tl.data_ptr(), ml.data_ptr(), dS.data_ptr(),
-                                     T1, dS_p.ptr, dS_p.ld, B, T1, T2, rs2.Tp, O._stream()), "efts_attn_bwd")
-        # dQ = scale * dS K ; dK = scale * dS^T Q
+        O.attn_bwd(al.scores, T1, al.sidx, dsx, tl, ml, dS, T1, dS_p, B, T1, T2, rs2.Tp)
         GQ = ws.f32("BGQ", rs2, C)
-        O.gemm(a=dS_p, b_ptr=kt.ptr, ldb=kt.ld, m=T2, n=C, batch=B, a_batch_stride=rs2.Tp * dS_p.ld, b_batch_stride=C * kt.ld, alpha=scale,
-               out_f32_ptr=GQ.ptr, ldo=C, out_batch_stride=rs2.Tp * C)
+        O.gemm(a=dS_p, b_ptr=pa.kt.ptr, ldb=pa.kt.ld, m=T2, n=C, batch=B, a_batch_stride=rs2.Tp * dS_p.ld, b_batch_stride=C * pa.kt.ld,
+               alpha=O.INV_SQRT(C), out_f32_ptr=GQ.ptr, ldo=C, out_batch_stride=rs2.Tp * C)
         dSt = ws.raw_plane("BdSt", B * T1 + 264, T2, 2)             # dS^T: rows (b,i), K = j
-        L.check(_lib().efts_pack_vt(dS.data_ptr(), T1, dSt.ptr, dSt.ld, B, T2, T2, T1, dSt.split, O._stream()), "efts_pack_vt")
+        O.pack_vt(dS, dSt, B, T2, T2, T1)
+        return _AlignBwd(de, dpi, dsx, dS, GQ, dSt)
+
+    def _bwd_dk(self, st: _Step, ab: _AlignBwd, pa: _Packs, dv: _DV) -> Tuple[F32Rows, Plane]:
+        """dK = scale * dS^T Q; with a shared key / value projection the value's gradient joins it here (residual)"""
+        ws, B, T1, rs1, C = st.ws, st.B, st.T1, st.rs1, self.m.n_channels
         GK = ws.f32("BGK", rs1, C)
-        GK_p = ws.plane("BGK_p", rs1, C, split)
-        shared = m.share_text_encoder_key_value                     # value = key projection: its gradient joins dK here (residual)
-        if ev_gv is not None:
-            main.wait_event(ev_gv)                                   # (shared: dV is the residual of the next launch; else: one join for everything behind)
-        O.gemm(a=dSt, b_ptr=qt.ptr, ldb=qt.ld, m=T1, n=C, batch=B, a_batch_stride=T1 * dSt.ld, b_batch_stride=C * qt.ld, alpha=scale,
-               resid_ptr=GV.ptr if shared else None, ldr=C, resid_batch_stride=rs1.Tp * C,
-               rowmask_ptr=len1.data_ptr(), rowmask_batch_stride=rs1.Tp, out_f32_ptr=GK.ptr, ldo=C, out_batch_stride=rs1.Tp * C,
+        GK_p = ws.plane("BGK_p", rs1, C, self.m.split)
+        O.gemm(a=ab.dSt, b_ptr=pa.qt.ptr, ldb=pa.qt.ld, m=T1, n=C, batch=B, a_batch_stride=T1 * ab.dSt.ld, b_batch_stride=C * pa.qt.ld,
+               alpha=O.INV_SQRT(C), resid_ptr=dv.GV.ptr if self.m.share_text_encoder_key_value else None, ldr=C, resid_batch_stride=rs1.Tp * C,
+               rowmask_ptr=st.len1.data_ptr(), rowmask_batch_stride=rs1.Tp, out_f32_ptr=GK.ptr, ldo=C, out_batch_stride=rs1.Tp * C,
                out_plane=GK_p, outb_batch_stride=rs1.Tp * GK_p.ld)
+        return GK, GK_p
 
-        ev_gk = torch.cuda.Event()
-        ev_gk.record(main)
-        if self.mark is not None:
-            self.mark("bwd_alignment_done")
-        side.wait_event(ev_gk)                                      # dK, dV are ready
-        if wst is not None and self.bucket_hook:
-            # data parallel: bucket 0 (mel head + decoder) is final once the decoder's weight gradients are through; its exchange then
-            # overlaps the encoders' backward instead of the alignment block's as well
-            main.wait_stream(wst)
-            self.bucket_hook(0)
+    def _bwd_text(self, st: _Step, tx: _TextFwd, dv: _DV, GK: F32Rows, GK_p: Plane) -> F32Rows:
+        """value / key Linears -> text encoder -> embedding; returns the gradient of the embedded text"""
+        m, ws, rs1, C, g = self.m, st.ws, st.rs1, self.m.n_channels, self.g
+        gap1 = st.gap1.data_ptr()
+        shared = m.share_text_encoder_key_value                     # GK already holds dK + dV then
+        sc = ws.f32("Bscratch1" + self._ws_tag, rs1, C)
+        kv_items = []                                                # (value and key Linears: one grouped launch)
+        if not shared:
+            O.act_bwd(dv.GV.ptr, None, None, None, 0.0, 0, sc, None, g["text_encoder_value.bias"], rs1.rows, C)
+            self._wgrad_any(ws, dv.GV.ptr, dv.GV_p, tx.te_f.ptr, tx.te_p, C, C, 1, rs1.rows, g["text_encoder_value.weight"], defer=kv_items)
+        O.act_bwd(GK.ptr, None, None, None, 0.0, 0, sc, None, g["text_encoder_key.bias"], rs1.rows, C)
+        self._wgrad_any(ws, GK.ptr, GK_p, tx.te_f.ptr, tx.te_p, C, C, 1, rs1.rows, g["text_encoder_key.weight"], defer=kv_items)
+        if kv_items:
+            self._wgrad_group(ws, kv_items, C, C, rs1.rows, 1, m.split)
+        Gt0, Gt = ws.f32("Bte_G0", rs1, C), ws.f32("Bte_G1x", rs1, C)
+        wtk = self.wt["key"]
+        if shared:
+            O.gemm(a=GK_p, b_ptr=wtk.ptr, ldb=wtk.ld, m=rs1.rows, n=C, rowmask_ptr=gap1, out_f32_ptr=Gt.ptr, ldo=C)
+        else:
+            wtv = self.wt["value"]
+            O.gemm(a=dv.GV_p, b_ptr=wtv.ptr, ldb=wtv.ld, m=rs1.rows, n=C, rowmask_ptr=gap1, out_f32_ptr=Gt0.ptr, ldo=C)
+            O.gemm(a=GK_p, b_ptr=wtk.ptr, ldb=wtk.ld, m=rs1.rows, n=C, resid_ptr=Gt0.ptr, ldr=C, rowmask_ptr=gap1, out_f32_ptr=Gt.ptr, ldo=C)
+        Ge = self._stack_bwd(ws, "te", "text_encoder", rs1, Gt, tx.te_saved, gap1, gap1, None)
+        O.embed_bwd(st.text, Ge.ptr, g["text_embedding_table.weight"], st.B, st.T1, rs1.Tp, C)
+        return Ge
 
-        def kv_param_grads():                                        # bias + weight gradients of the value / key Linears
-            sc = ws.f32("Bscratch1" + self._ws_tag, rs1, C)
-            kv_items = []                                            # (value and key Linears: one grouped launch)
-            if not shared:
-                L.check(_lib().efts_act_bwd(GV.ptr, None, None, None, 0.0, 0, sc.ptr, None, 0, 1,
-                                            g["text_encoder_value.bias"].data_ptr(), rs1.rows, C, O._stream()), "efts_act_bwd")
-                self._wgrad_any(ws, GV.ptr, GV_p, te_f.ptr, te_p, C, C, 1, rs1.rows, g["text_encoder_value.weight"], defer=kv_items)
-            L.check(_lib().efts_act_bwd(GK.ptr, None, None, None, 0.0, 0, sc.ptr, None, 0, 1,
-                                        g["text_encoder_key.bias"].data_ptr(), rs1.rows, C, O._stream()), "efts_act_bwd")
-            self._wgrad_any(ws, GK.ptr, GK_p, te_f.ptr, te_p, C, C, 1, rs1.rows, g["text_encoder_key.weight"], defer=kv_items)
-            if kv_items:
-                self._wgrad_group(ws, kv_items, C, C, rs1.rows, 1, split)
-
-        with O.on_stream(side):
-            self._ws_tag = "s"
-            # ---- value / key Linears -> text encoder -> embedding
-            kv_param_grads()
-            Gt0, Gt = ws.f32("Bte_G0", rs1, C), ws.f32("Bte_G1x", rs1, C)
-            wtk = self.wt["key"]
-            if shared:                                               # GK already holds dK + dV
-                O.gemm(a=GK_p, b_ptr=wtk.ptr, ldb=wtk.ld, m=rs1.rows, n=C, rowmask_ptr=gap1.data_ptr(), out_f32_ptr=Gt.ptr, ldo=C)
-            else:
-                wtv = self.wt["value"]
-                O.gemm(a=GV_p, b_ptr=wtv.ptr, ldb=wtv.ld, m=rs1.rows, n=C, rowmask_ptr=gap1.data_ptr(), out_f32_ptr=Gt0.ptr, ldo=C)
-                O.gemm(a=GK_p, b_ptr=wtk.ptr, ldb=wtk.ld, m=rs1.rows, n=C, resid_ptr=Gt0.ptr, ldr=C, rowmask_ptr=gap1.data_ptr(),
-                       out_f32_ptr=Gt.ptr, ldo=C)
-            Ge = self._stack_bwd(ws, "te", "text_encoder", rs1, Gt, te_saved, gap1.data_ptr(), gap1.data_ptr(), None)
-            L.check(_lib().efts_embed_bwd(text.data_ptr(), Ge.ptr, g["text_embedding_table.weight"].data_ptr(), B, T1, rs1.Tp, C,
-                                          m.num_symbols, O._stream()), "efts_embed_bwd")
-            self._ws_tag = ""
-
-        # ---- mel encoder + prenet
+    def _bwd_mel_encoder(self, st: _Step, mf: _MelFwd, GQ: F32Rows, wgrad_stream) -> F32Rows:
+        """query fc (where the model has one) and the mel encoder; returns the gradient of the prenet's output"""
+        m, ws, rs2, C, g = self.m, st.ws, st.rs2, self.m.n_channels, self.g
+        gap2 = st.gap2.data_ptr()
         G_me = GQ
         if m.mel_query_fc is not None:                               # backward of q = Linear(mel_h) (efficient_tts.py:163-164)
-            GQ_p = ws.plane("BGQ_p", rs2, C, split)
-            self._act_bwd(GQ.ptr, None, None, gap2.data_ptr(), 0, None, GQ_p, g["mel_query_fc.bias"], rs2.rows, C)
-            self._wgrad_any(ws, GQ.ptr, GQ_p, mh_f.ptr, mh_p, C, C, 1, rs2.rows, g["mel_query_fc.weight"])
+            GQ_p = ws.plane("BGQ_p", rs2, C, m.split)
+            O.act_bwd_dropout(GQ.ptr, None, None, gap2, m.slope, 0, None, GQ_p, g["mel_query_fc.bias"], rs2.rows, C)
+            self._wgrad_any(ws, GQ.ptr, GQ_p, mf.mh_f.ptr, mf.mh_p, C, C, 1, rs2.rows, g["mel_query_fc.weight"])
             G_me = ws.f32("BG_mh", rs2, C)
             wtq = self.wt["qfc"]
-            O.gemm(a=GQ_p, b_ptr=wtq.ptr, ldb=wtq.ld, m=rs2.rows, n=C, rowmask_ptr=gap2.data_ptr(), out_f32_ptr=G_me.ptr, ldo=C)
-        Gm = self._stack_bwd(ws, "me", "mel_encoder", rs2, G_me, me_saved, gap2.data_ptr(), gap2.data_ptr(), None, wgrad_stream=wst2)
-        if self.mark is not None:
-            self.mark("bwd_mel_encoder_done")
-        narrow = self._narrow_ok(split, mel_in.split, C, odim, max(C, 128) * 2, mel_in.ld)        # (the dZ plane allocated below is C wide)
+            O.gemm(a=GQ_p, b_ptr=wtq.ptr, ldb=wtq.ld, m=rs2.rows, n=C, rowmask_ptr=gap2, out_f32_ptr=G_me.ptr, ldo=C)
+        return self._stack_bwd(ws, "me", "mel_encoder", rs2, G_me, mf.me_saved, gap2, gap2, None, wgrad_stream=wgrad_stream)
+
+    def _bwd_prenet(self, st: _Step, mf: _MelFwd, Gm: F32Rows, wgrad_stream) -> None:
+        m, ws, rs2, C, odim, g = self.m, st.ws, st.rs2, self.m.n_channels, self.m.odim, self.g
+        gap2 = st.gap2.data_ptr()
+        narrow = self._narrow_ok(m.split, mf.mel_in.split, C, odim, max(C, 128) * 2, mf.mel_in.ld)        # (the dZ plane allocated below is C wide)
         dzp_f = None if narrow else ws.f32("Bpre_dz", rs2, C)
-        dzp_p = ws.plane("Bpre_dzp", rs2, C, split) if narrow else None
-        if pre_z is not None:
-            O.act_grad(m.act_general, Gm.ptr, pre_z.ptr, gap2.data_ptr(), dzp_f, dzp_p, g["mel_prenet.0.bias"], rs2.rows, C, pre_dp, pre_seed)
+        dzp_p = ws.plane("Bpre_dzp", rs2, C, m.split) if narrow else None
+        if mf.pre_z is not None:
+            O.act_grad(m.act_general, Gm.ptr, mf.pre_z.ptr, gap2, dzp_f, dzp_p, g["mel_prenet.0.bias"], rs2.rows, C, *mf.pre_drop)
         else:
-            self._act_bwd(Gm.ptr, pre_f.ptr, None, gap2.data_ptr(), 3, dzp_f, dzp_p, g["mel_prenet.0.bias"], rs2.rows, C, pre_dp, pre_seed)
-        with self._forked(wst2):
-            if not (narrow and self._wgrad_narrow(ws, "pre", dzp_p, mel_in, C, odim, rs2.rows, g["mel_prenet.0.weight"])):
+            O.act_bwd_dropout(Gm.ptr, mf.pre_f.ptr, None, gap2, m.slope, 3, dzp_f, dzp_p, g["mel_prenet.0.bias"], rs2.rows, C, *mf.pre_drop)
+        with self._forked(wgrad_stream):
+            if not (narrow and self._wgrad_narrow(ws, "pre", dzp_p, mf.mel_in, C, odim, rs2.rows, g["mel_prenet.0.weight"])):
                 assert dzp_f is not None
-                self._wgrad(ws, dzp_f.ptr, C, mel_in_f.ptr, odim, odim, 1, rs2.rows, None, None, g["mel_prenet.0.weight"], None)
-        if self.bucket_hook:
-            if wst is not None:
-                main.wait_stream(wst)
-            self.bucket_hook(1)
-
-        main.wait_stream(side)                                      # text-side gradients (bucket 2) and everything else enqueued there
-        if wst is not None and not self.bucket_hook:
-            main.wait_stream(wst)                                   # the weight gradients of the mel-length layers
-        if self.bucket_hook:
-            self.bucket_hook(2)
-
-        aux = None
-        if keep:
-            aux = dict(imv=imv, ralpha=ralpha, mel=mel, e=e, dH=dH, dAp=dAp, de=de, dpi=dpi, dsx=dsx, dS=dS, GQ=GQ, GK=GK, GV=GV,
-                       Gm=Gm, Ge=Ge, rs1=rs1, rs2=rs2, ddur=ddur)
-        return out3, aux
+                self._wgrad(ws, dzp_f.ptr, C, mf.mel_in_f.ptr, odim, odim, 1, rs2.rows, None, None, g["mel_prenet.0.weight"], None)

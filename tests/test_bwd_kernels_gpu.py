@@ -1,7 +1,8 @@
 """GPU (-m gpu): every training-side pointwise / reduction kernel alone against a float64 reference of the same operation.
 
-The exports below are called directly through `efficient_tts_amd.lib` with torch tensors as buffers, the way
-efficient_tts_amd/train.py does -- no model, no TrainEngine, no golden file:
+The exports below are called with torch tensors as buffers through their wrappers in `efficient_tts_amd.ops`, the way
+efficient_tts_amd/train.py does (the forward-side ones, and the refusal cases, directly through `efficient_tts_amd.lib`) -- no model,
+no TrainEngine, no golden file:
 
     efts_alpha_bwd  efts_e_bwd  efts_imv_bwd  efts_attn_bwd  efts_embed_bwd  efts_loss_bwd  efts_masked_losses
     efts_layernorm_rows  efts_layernorm_dot  efts_layernorm_bwd  efts_cumsum_rows  efts_sumsq  efts_scale_unless_one
@@ -60,10 +61,13 @@ Measured on one MI355X: the worst `kernel error / e32` of each kernel over its c
 Every ratio is below 8 (the largest, 3.0, is the order of the 513 atomic adds per column in efts_layernorm_bwd's dbeta); no factor was widened.
 `chain` is test_alignment_backward_chain_vs_fp64, whose bound is capped at 2e-4 instead (its docstring says why).
 """
+from types import SimpleNamespace
+
 import pytest
 import torch
 
 import bwd_reference as R
+from efficient_tts_amd import ops as O
 from kernel_check import COND, FACTOR, FLOOR, _call, _check, _dev, _rel, _st, load_lib   # noqa: F401  (the metric and the bound: tests/kernel_check.py)
 
 pytestmark = pytest.mark.gpu
@@ -116,8 +120,7 @@ def _run_alpha_bwd(lib, ralpha, dA, e, tl, ml, B, T1, T2):
     dev = _dev()
     r = torch.full((B, T2), 7.0, device=dev)
     de = torch.full((B, T1), 7.0, device=dev)
-    _call("efts_alpha_bwd", lib.efts_alpha_bwd(ralpha.data_ptr(), dA.data_ptr(), e.data_ptr(), tl.data_ptr(), ml.data_ptr(), SIGMA,
-                                               r.data_ptr(), de.data_ptr(), B, T1, T2, _st()))
+    O.alpha_bwd(ralpha, dA, e, tl, ml, SIGMA, r, de, B, T1, T2)
     return r, de
 
 
@@ -145,8 +148,7 @@ def _run_e_bwd(lib, imv, e, de, tl, ml, B, T1, T2):
     dev = _dev()
     ws = torch.empty(2 * B * T1, device=dev)
     dpi = torch.full((B, T2), 7.0, device=dev)
-    _call("efts_e_bwd", lib.efts_e_bwd(imv.data_ptr(), e.data_ptr(), de.data_ptr(), tl.data_ptr(), ml.data_ptr(), SIGMA_E, ws.data_ptr(),
-                                       dpi.data_ptr(), B, T1, T2, _st()))
+    O.e_bwd(imv, e, de, tl, ml, SIGMA_E, ws, dpi, B, T1, T2)
     return dpi
 
 
@@ -218,7 +220,7 @@ def test_imv_bwd_vs_fp64(lib, T2):
         assert float(imv[2].abs().max()) == 0.0 and bool((s[3, int(ml[3]):].diff() > 0).any())
     ds = torch.full((B, T2), 7.0, device=dev)
     d = [t.to(dev) for t in (s, imv, dpi, tl, ml)]                                  # (kept alive until the kernel has run)
-    _call("efts_imv_bwd", lib.efts_imv_bwd(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), d[4].data_ptr(), ds.data_ptr(), B, T2, _st()))
+    O.imv_bwd(d[0], d[1], d[2], d[3], d[4], ds, B, T2)
     torch.cuda.synchronize()
     fn = lambda t: R.imv_from_soft_index(t, mm, tl)                                 # noqa: E731
     ref64, ref32 = _grad(fn, s, dpi, torch.float64), _grad(fn, s, dpi, torch.float32)
@@ -240,14 +242,18 @@ def _unpack_plane(pl, B, Tp, T, kp):
     return (w[:, :, :, 0] + w[:, :, :, 1]).reshape(B, T, kp)
 
 
+def _raw_plane(buf, ld):
+    """a caller-owned byte buffer [rows, ld] as the bf16x3 output plane of a wrapper (what ops.Plane carries, with this test's own ld)"""
+    return SimpleNamespace(ptr=buf.data_ptr(), ld=ld, split=2)
+
+
 def _run_attn_bwd(lib, scores, ld, sidx, ds, tl, ml, B, T1, T2, ldd, pad_ldp):
     dev = _dev()
     kp = (T1 + 31) // 32 * 32
     T2p, ldp = T2 + 2, kp * 4 + pad_ldp
     dS = torch.full((B, T2, ldd), 7.0, device=dev)
     pl = torch.full((B * T2p, ldp), 0xAB, dtype=torch.uint8, device=dev)
-    _call("efts_attn_bwd", lib.efts_attn_bwd(scores.data_ptr(), ld, sidx.data_ptr(), ds.data_ptr(), tl.data_ptr(), ml.data_ptr(), dS.data_ptr(), ldd,
-                                             pl.data_ptr(), ldp, B, T1, T2, T2p, _st()))
+    O.attn_bwd(scores, ld, sidx, ds, tl, ml, dS, ldd, _raw_plane(pl, ldp), B, T1, T2, T2p)
     return dS, pl, kp, T2p, ldp
 
 
@@ -310,8 +316,7 @@ def test_alignment_backward_chain_vs_fp64(lib, B, T1, T2):
     _, de = _run_alpha_bwd(lib, f32["ralpha"], dA.to(dev), f32["e"], tld, mld, B, T1, T2)
     dpi = _run_e_bwd(lib, f32["imv"], f32["e"], de, tld, mld, B, T1, T2)
     dsx = torch.full((B, T2), 7.0, device=dev)
-    _call("efts_imv_bwd", lib.efts_imv_bwd(f32["soft_idx"].data_ptr(), f32["imv"].data_ptr(), dpi.data_ptr(), tld.data_ptr(), mld.data_ptr(),
-                                           dsx.data_ptr(), B, T2, _st()))
+    O.imv_bwd(f32["soft_idx"], f32["imv"], dpi, tld, mld, dsx, B, T2)
     dS, pl, kp, T2p, ldp = _run_attn_bwd(lib, scores.to(dev), T1, f32["soft_idx"], dsx, tld, mld, B, T1, T2, T1, 0)
     torch.cuda.synchronize()
     fn = lambda t: R.alignment_block(t, tl, ml, SIGMA, SIGMA_E)["ralpha"]           # noqa: E731
@@ -339,7 +344,7 @@ def test_embed_bwd_vs_fp64(lib, c):
     table = torch.randn(nsym, c, generator=g)
     out = table.clone().to(dev)
     ids_d, rows_d = ids.to(dev), rows.to(dev)
-    _call("efts_embed_bwd", lib.efts_embed_bwd(ids_d.data_ptr(), rows_d.data_ptr(), out.data_ptr(), B, T, Tp, c, nsym, _st()))
+    O.embed_bwd(ids_d, rows_d.data_ptr(), out, B, T, Tp, c)
     torch.cuda.synchronize()
     valid = rows[:, :T].reshape(B * T, c)
     ref64 = table.double().index_add_(0, ids.reshape(-1), valid.double())
@@ -379,9 +384,7 @@ def test_loss_bwd_vs_fp64(lib, ldm, gscale):
     ddur = torch.full((B, T1p), 7.0, device=dev)
     gs = None if gscale is None else torch.tensor([gscale], device=dev)
     d = [t.to(dev) for t in (mel, speech, ml, dur, lde, tl)]
-    _call("efts_loss_bwd", lib.efts_loss_bwd(d[0].data_ptr(), ldm, d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
-                                             d[4].data_ptr(), d[5].data_ptr(), None if gs is None else gs.data_ptr(), dmel.data_ptr(),
-                                             pl.data_ptr(), ldp, 2, ddur.data_ptr(), B, T1, T1p, T2, T2p, odim, _st()))
+    O.loss_bwd(d[0].data_ptr(), ldm, d[1], d[2], d[3], d[4], d[5], gs, dmel.data_ptr(), _raw_plane(pl, ldp), ddur, B, T1, T1p, T2, T2p, odim)
     torch.cuda.synchronize()
 
     def grads(dtype):
@@ -492,13 +495,11 @@ def test_layernorm_bwd_vs_fp64(lib, rows, c, form):
     dz = torch.full((rows, c), 7.0, device=dev)
     gd, bd, wd, rmd, dyd, ddurd = gamma.to(dev), beta.to(dev), w.to(dev), rm.to(dev), dy.to(dev), ddur.to(dev)
     if form == "dy":
-        rc = lib.efts_layernorm_bwd(x.data_ptr(), gd.data_ptr(), bd.data_ptr(), LN_EPS, dyd.data_ptr(), None, None, rmd.data_ptr(), dz.data_ptr(), None, 0,
-                                    2, acc["dgamma"].data_ptr(), acc["dbeta"].data_ptr(), acc["dbias"].data_ptr(), None, None, rows, c, 0.0, 0, None, _st())
+        O.layernorm_bwd(x.data_ptr(), gd, bd, LN_EPS, dyd.data_ptr(), None, None, rmd.data_ptr(), dz.data_ptr(), None,
+                        acc["dgamma"], acc["dbeta"], acc["dbias"], None, None, rows, c)
     else:
-        rc = lib.efts_layernorm_bwd(x.data_ptr(), gd.data_ptr(), bd.data_ptr(), LN_EPS, None, ddurd.data_ptr(), wd.data_ptr(),
-                                    rmd.data_ptr() if form == "ddur_rowmask" else None, dz.data_ptr(), None, 0, 2, acc["dgamma"].data_ptr(),
-                                    acc["dbeta"].data_ptr(), acc["dbias"].data_ptr(), acc["dw"].data_ptr(), acc["db"].data_ptr(), rows, c, 0.0, 0, None, _st())
-    _call("efts_layernorm_bwd", rc)
+        O.layernorm_bwd(x.data_ptr(), gd, bd, LN_EPS, None, ddurd, wd, rmd.data_ptr() if form == "ddur_rowmask" else None, dz.data_ptr(), None,
+                        acc["dgamma"], acc["dbeta"], acc["dbias"], acc["dw"], acc["db"], rows, c)
     torch.cuda.synchronize()
 
     def ref(dtype):
@@ -574,7 +575,7 @@ def test_scale_unless_one(lib, n):
     for s in (1.0, 0.5, 3.0):
         buf = xcpu.clone().to(dev)                                                   # 5 elements past n: not the kernel's
         sc = torch.tensor([s], device=dev)
-        _call("efts_scale_unless_one", lib.efts_scale_unless_one(buf.data_ptr(), n, sc.data_ptr(), _st()))
+        O.scale_unless_one(buf, n, sc)
         torch.cuda.synchronize()
         got = buf.cpu()
         assert torch.equal(got[n:], xcpu[n:])

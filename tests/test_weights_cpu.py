@@ -305,3 +305,16 @@ def test_a_model_is_freed_without_the_cyclic_collector(stub):
         assert ref() is None
     finally:
         gc.enable()
+
+
+@pytest.mark.parametrize("k", [1, 2, 3])
+def test_the_engine_refuses_a_duration_predictor_it_cannot_train(k):
+    """the training step is written out for two duration-predictor layers: another depth is refused when the engine is built, by name,
+    instead of an IndexError deep in the step (one layer) or a third layer that silently gets a zero gradient"""
+    torch.manual_seed(0)
+    m = EfficientTTSCNN(**CONFIGS["a"], n_duration_layer=k)
+    if k == 2:
+        assert TrainEngine(m).last is None
+    else:
+        with pytest.raises(NotImplementedError, match="n_duration_layer"):
+            TrainEngine(m)
