@@ -18,7 +18,9 @@ HiFi-GAN V1 generator (efficient_tts_amd.vocoder).  Differences from the referen
   * `--length_scale S` multiplies every predicted duration (> 1: slower speech), `--write_durations` writes the frames per
     phoneme next to each output (<id>_<step>.durations.txt: index, phoneme, start frame, frames, start time in seconds);
   * `--sampling_rate R [--resample_quality best|fast]` writes the wav files at R Hz instead of the vocoder's 22 050 Hz: the vocoder's
-    output is converted on the device (efficient_tts_amd.resample) in front of the 16-bit quantisation.
+    output is converted on the device (efficient_tts_amd.resample) in front of the 16-bit quantisation;
+  * `--write_f0` writes the pitch contour of every utterance next to its wav (<id>_<step>.f0.txt: frame index, time in seconds, f0 in Hz with 0 for an
+    unvoiced frame), tracked on the device from the vocoder's output (efficient_tts_amd.pitch) on the mel frames' grid.
 """
 from __future__ import annotations
 
@@ -35,6 +37,7 @@ import yaml
 
 from efficient_tts_amd import models
 from efficient_tts_amd.griffinlim import GriffinLimVocoder
+from efficient_tts_amd.pitch import PitchTracker
 from efficient_tts_amd.resample import QUALITIES, Resampler
 from efficient_tts_amd.vocoder import HiFiGANGenerator, load_hifigan_generator
 
@@ -64,6 +67,8 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--sampling_rate", type=int, default=None,
                    help=f"sampling rate of the written wav files in Hz (default: the vocoder's, {SAMPLING_RATE}); other rates are converted on the device")
     p.add_argument("--resample_quality", type=str, default="best", choices=sorted(QUALITIES), help="filter of --sampling_rate (default best)")
+    p.add_argument("--write_f0", action="store_true",
+                   help="also write <id>_<step>.f0.txt: frame index, time in seconds, f0 in Hz (0: unvoiced) of the vocoder's output")
     p.add_argument("--verbose", type=int, default=1)
     return p
 
@@ -101,6 +106,26 @@ def load_acoustic_model(args, device):
     return config, phn2idx, model
 
 
+def build_vocoder(args, device):
+    """the vocoder of --vocoder / --vocoder_config / --vocoder_checkpoint / --gl_iters / --precision (shared with efficient_tts_amd.bin.score)"""
+    if args.vocoder == "griffinlim":
+        return GriffinLimVocoder(device, n_iter=args.gl_iters, precision="fp32" if args.precision == "fp32" else "bf16x3")
+    if args.vocoder_checkpoint:
+        if not args.vocoder_config:
+            raise ValueError("--vocoder_checkpoint needs --vocoder_config")
+        return load_hifigan_generator(device, args.vocoder_config, args.vocoder_checkpoint, precision=args.precision)
+    logging.warning("no --vocoder_checkpoint: the HiFi-GAN generator runs with RANDOM weights (timing / smoke only)")
+    vocoder = HiFiGANGenerator(_V1, precision=args.precision).to(device).eval()
+    vocoder.remove_weight_norm()
+    return vocoder
+
+
+def _write_f0(path: str, f0, hop: int, sampling_rate: int) -> None:
+    with open(path, "w") as handle:
+        for t, f in enumerate(f0):
+            handle.write(f"{t}\t{t * hop / sampling_rate:.6f}\t{f:.3f}\n")
+
+
 def _write_wav(path: str, samples: torch.Tensor, sampling_rate: int = SAMPLING_RATE) -> None:
     from scipy.io.wavfile import write
     pcm = (samples.clamp(-1.0, 1.0) * 32767.0).round().to(torch.int16).cpu().numpy()
@@ -136,18 +161,10 @@ def run_tts(args) -> float:
     logging.info(f"{len(items)} utterances to synthesise")
     step = os.path.basename(args.checkpoint).split("-")[-1][:-4]
 
-    vocoder = None
-    if not args.no_vocoder and args.vocoder == "griffinlim":
-        vocoder = GriffinLimVocoder(device, n_iter=args.gl_iters, precision="fp32" if args.precision == "fp32" else "bf16x3")
-    elif not args.no_vocoder:
-        if args.vocoder_checkpoint:
-            if not args.vocoder_config:
-                raise ValueError("--vocoder_checkpoint needs --vocoder_config")
-            vocoder = load_hifigan_generator(device, args.vocoder_config, args.vocoder_checkpoint, precision=args.precision)
-        else:
-            logging.warning("no --vocoder_checkpoint: the HiFi-GAN generator runs with RANDOM weights (timing / smoke only)")
-            vocoder = HiFiGANGenerator(_V1, precision=args.precision).to(device).eval()
-            vocoder.remove_weight_norm()
+    if args.write_f0 and args.no_vocoder:
+        raise ValueError("--write_f0 tracks the vocoder's output: it cannot be combined with --no_vocoder")
+    vocoder = None if args.no_vocoder else build_vocoder(args, device)
+    tracker = PitchTracker(device, sampling_rate=SAMPLING_RATE, n_fft=1024, hop_size=256) if args.write_f0 else None
     resampler = None
     if vocoder is not None and out_rate != SAMPLING_RATE:
         resampler = Resampler(device, SAMPLING_RATE, out_rate, quality=args.resample_quality)
@@ -175,11 +192,12 @@ def run_tts(args) -> float:
             if vocoder is None:
                 outs = mels
             elif len(chunk) == 1:
-                outs = [vocoder(mels[0].t()[None].contiguous())[0, 0]]
+                outs = raw = [vocoder(mels[0].t()[None].contiguous())[0, 0]]
                 if resampler is not None:
                     outs = [resampler(outs[0][None].float())[0][0]]
             else:                                       # one batched generator pass; every item equals its single-utterance result
                 audio = vocoder(mel.transpose(1, 2).contiguous(), mel_lens)
+                raw = [audio[n, 0, :int(mel_lens[n]) * 256] for n in range(len(chunk))]
                 if resampler is None:
                     outs = [audio[n, 0, :int(mel_lens[n]) * 256] for n in range(len(chunk))]
                 else:                                   # ragged: every item is converted from its own samples only
@@ -195,6 +213,11 @@ def run_tts(args) -> float:
                 np.save(os.path.join(args.outdir, f"{utt}_{step}.npy"), out.cpu().numpy())
             else:
                 _write_wav(os.path.join(args.outdir, f"{utt}_{step}.wav"), out, out_rate)
+        if tracker is not None:                         # outside the timed span: the contour of the vocoder's own output, before any rate conversion
+            for (utt, _), wav in zip(chunk, raw):
+                with torch.no_grad():
+                    f0, _, n = tracker(wav[None].float(), torch.tensor([wav.shape[0]]), short_ok=True)
+                _write_f0(os.path.join(args.outdir, f"{utt}_{step}.f0.txt"), f0[0, :int(n[0])].cpu().tolist(), 256, SAMPLING_RATE)
         if frames is not None:
             for (utt, ids1), fr in zip(chunk, frames):
                 _write_durations(os.path.join(args.outdir, f"{utt}_{step}.durations.txt"), [idx2phn[int(i)] for i in ids1],

@@ -2,12 +2,19 @@
 
     python -m efficient_tts_amd.bin.score --checkpoint exp/efts/checkpoint-100000steps.pkl --test_fid_scp test.txt --outdir exp/efts/score \\
         [--config exp/efts/config.yml] [--batch_size 16] [--precision bf16x3] [--length_scale 1.0]
+        [--f0 --vocoder griffinlim|hifigan [--vocoder_config c.json --vocoder_checkpoint g.pt] [--gl_iters 32] [--f0_min 60] [--f0_max 600] [--f0_threshold 0.15]]
 
 Reads the `wav_path|phonemes` list of `efficient_tts_amd.bin.inference` (16-bit wav files at the front-end's rate; a path that does not
 exist is looked up by its file name under dataset_params.wav_path).  Per batch, on the device: the recordings' log-mels (`LogMelFrontend`
 with the recipe's frontend_params), the free-running mels (`inference_batch`), and `MelCepstralDistortion` of synthesis against recording.
 Writes outdir/mcd.tsv -- utterance id, MCD in dB, frames synthesised, frames recorded, length of the warping path; the last line is the
 mean -- and prints the mean.  An utterance whose synthesis has no frames has no path: its line says nan and the mean leaves it out.
+
+`--f0` adds the two pitch axes.  The synthesis is vocoded as `efficient_tts_amd.bin.inference` would (the same `--vocoder` switches), a YIN pitch
+tracker (`efficient_tts_amd.pitch`) runs on the synthesis and on the recording, the MCD's own warping path is kept, and along it
+`F0Error` gives the F0 error in cents over the cells voiced on both sides and the share of cells whose voicing differs.  mcd.tsv gets three more
+columns behind its own -- f0_rmse_cents, vuv_error, voiced_pairs -- and the last line their means over the utterances that have a value.
+Without `--f0` nothing changes.
 
 The numbers compare checkpoints of this project with each other (natural-log mels of this front-end); they are not comparable to MCDs
 computed from SPTK cepstra of waveforms.
@@ -21,9 +28,10 @@ import sys
 import numpy as np
 import torch
 
-from efficient_tts_amd.bin.inference import _read_list, load_acoustic_model
+from efficient_tts_amd.bin.inference import SAMPLING_RATE, _read_list, build_vocoder, load_acoustic_model
 from efficient_tts_amd.frontend import LogMelFrontend
-from efficient_tts_amd.score import MelCepstralDistortion
+from efficient_tts_amd.pitch import PitchTracker, lag_range
+from efficient_tts_amd.score import F0Error, MelCepstralDistortion
 
 
 def get_parser() -> argparse.ArgumentParser:
@@ -35,7 +43,31 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--batch_size", type=int, default=16, help="utterances per call (default 16; every item is scored as if alone)")
     p.add_argument("--precision", type=str, default="bf16x3", choices=["bf16x3", "bf16", "fp32"], help="MFMA operand mode of the acoustic model")
     p.add_argument("--length_scale", type=float, default=1.0, help="multiplies every predicted duration (default 1.0)")
+    p.add_argument("--f0", action="store_true", help="also score pitch along the MCD's warping path: F0 error in cents and voiced/unvoiced error")
+    p.add_argument("--vocoder", type=str, default="hifigan", choices=["hifigan", "griffinlim"],
+                   help="--f0: what turns the synthesised mel into audio (as efficient_tts_amd.bin.inference); hifigan needs --vocoder_checkpoint")
+    p.add_argument("--vocoder_config", type=str, default=None, help="--f0: HiFi-GAN config.json")
+    p.add_argument("--vocoder_checkpoint", type=str, default=None, help='--f0: HiFi-GAN checkpoint with a "generator" state_dict')
+    p.add_argument("--gl_iters", type=int, default=32, help="--f0: Griffin-Lim iterations (--vocoder griffinlim; default 32)")
+    p.add_argument("--f0_min", type=float, default=60.0, help="--f0: lowest fundamental searched, Hz (default 60)")
+    p.add_argument("--f0_max", type=float, default=600.0, help="--f0: highest fundamental searched, Hz (default 600)")
+    p.add_argument("--f0_threshold", type=float, default=0.15, help="--f0: YIN threshold on the normalised difference function (default 0.15)")
     return p
+
+
+def check_f0_args(args, front=None) -> None:
+    """--f0 needs audio of the synthesis that means something: refused on the host, before anything is loaded"""
+    if not args.f0:
+        return
+    if args.vocoder == "hifigan" and not (args.vocoder_checkpoint and args.vocoder_config):
+        raise ValueError("--f0 needs audio of the synthesis: give --vocoder griffinlim, or --vocoder hifigan with --vocoder_checkpoint and "
+                         "--vocoder_config (a generator with random weights has no pitch to score)")
+    if front is not None:
+        rate, n_fft, hop = int(front.get("sampling_rate", SAMPLING_RATE)), int(front.get("n_fft", 1024)), int(front.get("hop_size", 256))
+        if (rate, n_fft, hop) != (SAMPLING_RATE, 1024, 256):
+            raise ValueError(f"--f0: the vocoders produce {SAMPLING_RATE} Hz audio of 256 samples per frame; the recipe's front-end has "
+                             f"sampling_rate {rate}, n_fft {n_fft}, hop_size {hop}")
+        lag_range(rate, n_fft, args.f0_min, args.f0_max)
 
 
 def _read_wav(path: str, wav_dir, rate: int) -> torch.Tensor:
@@ -49,6 +81,7 @@ def _read_wav(path: str, wav_dir, rate: int) -> torch.Tensor:
 
 
 def run_score(args) -> float:
+    check_f0_args(args)
     if not torch.cuda.is_available():
         raise RuntimeError("no MI355X (gfx950) device visible: efficient_tts_amd has no CPU path")
     if not args.length_scale > 0:
@@ -60,10 +93,16 @@ def run_score(args) -> float:
     frontend = LogMelFrontend(device, **front)
     rate = int(front.get("sampling_rate", 22050))
     scorer = MelCepstralDistortion(device, num_mels=frontend.n_mels)
+    check_f0_args(args, front)
+    if args.f0:
+        vocoder = build_vocoder(args, device)
+        tracker = PitchTracker(device, sampling_rate=rate, n_fft=frontend.n_fft, hop_size=frontend.hop, fmin=args.f0_min, fmax=args.f0_max,
+                               threshold=args.f0_threshold, max_wav_value=frontend.max_wav_value)
+        f0_error = F0Error(device)
     wav_dir = (config.get("dataset_params") or {}).get("wav_path")
     items = _read_list(args.test_fid_scp, phn2idx, with_paths=True)
     bs = max(1, int(args.batch_size))
-    rows = []
+    rows, extra = [], []
     for lo in range(0, len(items), bs):
         chunk = items[lo:lo + bs]
         wavs = [_read_wav(path, wav_dir, rate) for _, _, path in chunk]
@@ -73,16 +112,28 @@ def run_score(args) -> float:
             rec, rec_len = frontend(audio, torch.tensor([w.shape[0] for w in wavs]))
             syn, syn_len = model.inference_batch(ids.to(device), torch.tensor([len(t) for _, t, _ in chunk], device=device),
                                                  length_scale=args.length_scale)[:2]
-            out = scorer(syn, syn_len, rec, rec_len)
+            out = scorer(syn, syn_len, rec, rec_len, return_path=True) if args.f0 else scorer(syn, syn_len, rec, rec_len)
+            if args.f0:
+                wav = vocoder(syn.transpose(1, 2).contiguous(), syn_len)[:, 0].float()
+                f0_syn = tracker(wav, syn_len * frontend.hop, max_frames=syn.shape[1], short_ok=True)[0]
+                f0_rec = tracker(audio, torch.tensor([w.shape[0] for w in wavs]), max_frames=rec.shape[1])[0]
+                pitch = f0_error(f0_syn, f0_rec, out["path"], out["path_len"])
+                extra.extend(zip(pitch["f0_rmse_cents"].tolist(), pitch["vuv_error"].tolist(), pitch["voiced_pairs"].tolist()))
         for (utt, _, _), m, a, b, n in zip(chunk, out["mcd"].tolist(), syn_len.tolist(), rec_len.tolist(), out["path_len"].tolist()):
             rows.append((utt, m, a, b, n))
     scored = [r[1] for r in rows if np.isfinite(r[1])]
     mean = float(np.mean(scored)) if scored else float("nan")
+    mean_of = lambda k: float(np.mean([e[k] for e in extra if np.isfinite(e[k])])) if any(np.isfinite(e[k]) for e in extra) else float("nan")
     with open(os.path.join(args.outdir, "mcd.tsv"), "w") as handle:
-        for utt, m, a, b, n in rows:
-            handle.write(f"{utt}\t{m:.6f}\t{a}\t{b}\t{n}\n")
-        handle.write(f"mean\t{mean:.6f}\n")
+        for i, (utt, m, a, b, n) in enumerate(rows):
+            tail = f"\t{extra[i][0]:.4f}\t{extra[i][1]:.6f}\t{extra[i][2]}" if args.f0 else ""
+            handle.write(f"{utt}\t{m:.6f}\t{a}\t{b}\t{n}{tail}\n")
+        tail = f"\t{mean_of(0):.4f}\t{mean_of(1):.6f}\t{mean_of(2):.1f}" if args.f0 else ""
+        handle.write(f"mean\t{mean:.6f}{tail}\n")
     print(f"mean MCD over {len(scored)} of {len(rows)} utterances: {mean:.4f} dB")
+    if args.f0:
+        print(f"mean F0 error {mean_of(0):.2f} cents over {sum(np.isfinite(e[0]) for e in extra)} utterances with a voiced pair, "
+              f"mean voiced/unvoiced error {mean_of(1):.4f}")
     return mean
 
 

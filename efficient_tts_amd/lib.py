@@ -198,6 +198,13 @@ _SIGS = {
     # scoring: mel-cepstra and dynamic time warping
     "efts_mel_cepstrum": (i32, [vp, i64, i64, vp, vp, vp, i32, i32, i32, i32, vp]),
     "efts_dtw": (i32, [vp, i64, i64, vp, i32, vp, i64, i64, vp, i32, i32, vp, vp, i32, vp]),
+    # the warping path and the F0 error along it
+    "efts_dtw_path_workspace_bytes": (i64, [i32, i32]),
+    "efts_dtw_path": (i32, [vp, i64, i64, vp, i32, vp, i64, i64, vp, i32, i32, vp, vp, vp, vp, i64, i32, vp]),
+    "efts_f0_path_error": (i32, [vp, i64, i32, vp, i64, i32, vp, i64, vp, vp, vp, vp, i32, vp]),
+    # pitch tracking
+    "efts_yin": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp]),
+    "efts_yin_pcm16": (i32, [vp, i64, f32, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

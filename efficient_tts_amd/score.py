@@ -8,6 +8,10 @@ A free-running mel has its own length, so it is compared with the recording's lo
     (ties: the diagonal, then (i-1, j), then (i, j-1); a later one wins only when strictly smaller)
     mcd = (10 / ln 10) sqrt(2) A(last, last) / L(last, last)   dB
 
+`dtw_path` returns the chosen path itself (`efts_dtw_path`: the same kernel body records every cell's move in a workspace and walks them back
+inside the launch), `MelCepstralDistortion(...)(..., return_path=True)` passes it on, and `F0Error` reads two F0 contours (`pitch.PitchTracker`)
+along it: the F0 error in cents on the cells voiced on both sides, and the share of cells whose voicing differs.
+
 The DCT table is computed once on the host in float64 and kept as fp32 in device memory; the sums and the recurrence run in
 csrc/efts_score.hip (`efts_mel_cepstrum`, `efts_dtw`): fp32, one fixed order, no atomics, no cost matrix in memory.  An item gives the same
 bits alone, in any batch and in any run.  No CPU path: the HIP library is required.
@@ -30,6 +34,7 @@ MCD_DB = 10.0 * math.sqrt(2.0) / math.log(10.0)
 MAX_MELS, MAX_COEF = 128, 32                                      # limits of efts_mel_cepstrum (include/efts_abi.h)
 
 _tables: Dict[tuple, torch.Tensor] = {}
+_workspaces: Dict[tuple, torch.Tensor] = {}                        # the move record of dtw_path, per (device, B, Tx, Ty)
 
 
 def dct_table(n_mels: int, n_coef: int) -> torch.Tensor:
@@ -105,12 +110,80 @@ def dtw(x: torch.Tensor, x_lengths: torch.Tensor, y: torch.Tensor, y_lengths: to
     return cost, path_len
 
 
+def _workspace(dev: torch.device, B: int, Tx: int, Ty: int) -> torch.Tensor:
+    key = (dev, B, Tx, Ty)
+    if key not in _workspaces:
+        if len(_workspaces) > 4:
+            _workspaces.pop(next(iter(_workspaces)))
+        _workspaces[key] = torch.empty(B * int(L_.load().efts_dtw_path_workspace_bytes(Tx, Ty)), dtype=torch.uint8, device=dev)
+    return _workspaces[key]
+
+
+@torch.no_grad()
+def dtw_path(x: torch.Tensor, x_lengths: torch.Tensor, y: torch.Tensor, y_lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(cost [B] fp32, path_len [B] int32, path [B, Tx + Ty - 1, 2] int32): `dtw`'s cost and path_len, bit for bit, and the path itself.
+    path[b, k] = (i, j) is the k-th cell in forward order, from (0, 0) to (x_lengths[b] - 1, y_lengths[b] - 1); rows at and beyond
+    path_len[b] are not written (they hold whatever the allocation held).  The move record lives in a workspace of
+    ceil(Tx / 1024) (Ty + 255) 256 bytes per pair, cached per (device, B, Tx, Ty) and shared by the calls on one stream."""
+    x, xl = _rows("x", x, x_lengths)
+    y, yl = _rows("y", y, y_lengths)
+    if y.shape[0] != x.shape[0] or y.shape[2] != x.shape[2] or y.device != x.device:
+        raise ValueError("x and y must agree in B, D and device")
+    B, Tx, D = x.shape
+    Ty = y.shape[1]
+    lib = L_.load()
+    L_.require_device()
+    if lib.efts_dtw_path_workspace_bytes(Tx, Ty) <= 0:
+        raise ValueError(f"dtw_path: Tx and Ty must be 1 .. 8192 frames (got {Tx}, {Ty})")
+    ws = _workspace(x.device, B, Tx, Ty)
+    cost = torch.empty(B, dtype=torch.float32, device=x.device)
+    path_len = torch.empty(B, dtype=torch.int32, device=x.device)
+    path = torch.empty(B, Tx + Ty - 1, 2, dtype=torch.int32, device=x.device)
+    with O.stream_scope():
+        L_.check(lib.efts_dtw_path(x.data_ptr(), x.stride(1), x.stride(0), xl.data_ptr(), Tx, y.data_ptr(), y.stride(1), y.stride(0), yl.data_ptr(),
+                                   Ty, D, cost.data_ptr(), path_len.data_ptr(), path.data_ptr(), ws.data_ptr(), ws.numel(), B, O._stream()), "efts_dtw_path")
+    return cost, path_len, path
+
+
+class F0Error:
+    """F0Error(device)(f0_a [B, Ta], f0_b [B, Tb], path [B, P, 2] int32, path_len [B]) -> dict of device tensors, nothing read back:
+    `voiced_pairs` [B] int32, the path cells voiced (f0 > 0) on both sides; `f0_rmse_cents` [B] = sqrt(mean over those cells of
+    (1200 log2(f0_a / f0_b))^2), NaN without such a cell; `vuv_error` [B], the share of path cells whose voicing differs, NaN for an empty path."""
+
+    def __init__(self, device):
+        self.dev = torch.device(device)
+
+    @torch.no_grad()
+    def __call__(self, f0_a: torch.Tensor, f0_b: torch.Tensor, path: torch.Tensor, path_len: torch.Tensor) -> Dict[str, torch.Tensor]:
+        for name, f in (("f0_a", f0_a), ("f0_b", f0_b)):
+            if f.dim() != 2 or f.dtype != torch.float32 or f.shape[0] != f0_a.shape[0] or f.shape[1] < 1:
+                raise ValueError(f"{name}: expected float32 [B, T]")
+        B = f0_a.shape[0]
+        if path.dim() != 3 or path.shape[0] != B or path.shape[1] < 1 or path.shape[2] != 2 or path.dtype != torch.int32 or path_len.shape != (B,):
+            raise ValueError("expected path [B, P, 2] int32 and path_len [B]")
+        if not f0_a.is_cuda:
+            raise RuntimeError("efficient_tts_amd.score runs on an MI355X device only (no CPU path)")
+        f0_a, f0_b, path = f0_a.contiguous(), f0_b.to(f0_a.device).contiguous(), path.to(f0_a.device).contiguous()
+        pl = path_len.to(device=f0_a.device, dtype=torch.int32)
+        lib = L_.load()
+        L_.require_device()
+        rmse = torch.empty(B, dtype=torch.float32, device=f0_a.device)
+        vuv = torch.empty(B, dtype=torch.float32, device=f0_a.device)
+        pairs = torch.empty(B, dtype=torch.int32, device=f0_a.device)
+        with O.stream_scope():
+            L_.check(lib.efts_f0_path_error(f0_a.data_ptr(), f0_a.stride(0), f0_a.shape[1], f0_b.data_ptr(), f0_b.stride(0), f0_b.shape[1], path.data_ptr(),
+                                            path.shape[1], pl.data_ptr(), rmse.data_ptr(), vuv.data_ptr(), pairs.data_ptr(), B, O._stream()),
+                     "efts_f0_path_error")
+        return dict(f0_rmse_cents=rmse, vuv_error=vuv, voiced_pairs=pairs)
+
+
 class MelCepstralDistortion:
     """MelCepstralDistortion(device, num_mels=80, n_coef=13)(mel_a [B, Ta, num_mels], len_a [B], mel_b [B, Tb, num_mels], len_b [B]) -> dict of
     device tensors: `mcd` [B] in dB = (10 / ln 10) sqrt(2) cost / path_len, `cost` and `path_len` as `dtw` returns them for the two
     mel-cepstra, `frames_ratio` [B] = len_a / len_b with the lengths clamped to the padded sizes as the kernels clamp them.  An item with
     a length below 1 on either side has no path: its `mcd`, `cost` and `frames_ratio` are NaN and its `path_len` 0 -- a caller that averages
     leaves such items out (bin/score.py does).  Three launches; nothing is read back, and with the lengths on the device nothing is copied.
+    `return_path=True` runs `dtw_path` in the place of `dtw` and adds `path` [B, Ta + Tb - 1, 2]; every other entry keeps its bits.
 
     The mels are this project's natural-log mels: the numbers compare checkpoints of this project with each other and are not comparable
     to MCDs computed from SPTK cepstra of waveforms."""
@@ -121,9 +194,14 @@ class MelCepstralDistortion:
         self.table = _table_on(self.dev, self.num_mels, self.n_coef)
 
     @torch.no_grad()
-    def __call__(self, mel_a: torch.Tensor, len_a: torch.Tensor, mel_b: torch.Tensor, len_b: torch.Tensor) -> Dict[str, torch.Tensor]:
-        cost, path_len = dtw(_cepstrum(mel_a, len_a, self.table), len_a, _cepstrum(mel_b, len_b, self.table), len_b)
+    def __call__(self, mel_a: torch.Tensor, len_a: torch.Tensor, mel_b: torch.Tensor, len_b: torch.Tensor, *,
+                 return_path: bool = False) -> Dict[str, torch.Tensor]:
+        extra = {}
+        if return_path:
+            cost, path_len, extra["path"] = dtw_path(_cepstrum(mel_a, len_a, self.table), len_a, _cepstrum(mel_b, len_b, self.table), len_b)
+        else:
+            cost, path_len = dtw(_cepstrum(mel_a, len_a, self.table), len_a, _cepstrum(mel_b, len_b, self.table), len_b)
         la = len_a.to(device=cost.device, dtype=torch.float32).clamp(max=mel_a.shape[1])
         lb = len_b.to(device=cost.device, dtype=torch.float32).clamp(max=mel_b.shape[1])
         ratio = torch.where((la >= 1) & (lb >= 1), la / lb, torch.full_like(la, float("nan")))
-        return dict(mcd=MCD_DB * cost / path_len, cost=cost, path_len=path_len, frames_ratio=ratio)
+        return dict(mcd=MCD_DB * cost / path_len, cost=cost, path_len=path_len, frames_ratio=ratio, **extra)

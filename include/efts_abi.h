@@ -82,7 +82,9 @@ extern "C" {
  *        missing symbol)
  *        + efts_optim_step, efts_optim_hyper (Adam / AdamW / RAdam): exports added, the revision stays by the same rule
  *        + efts_resample, efts_resample_pcm16 (sample-rate conversion): exports added, the revision stays by the same rule
- *        + efts_mel_cepstrum, efts_dtw (scoring synthesis against a recording): exports added, the revision stays by the same rule */
+ *        + efts_mel_cepstrum, efts_dtw (scoring synthesis against a recording): exports added, the revision stays by the same rule
+ *        + efts_yin, efts_yin_pcm16 (pitch tracking), efts_dtw_path, efts_dtw_path_workspace_bytes, efts_f0_path_error (the warping path and
+ *          the F0 error along it): exports added, the revision stays by the same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -828,6 +830,68 @@ int efts_mel_cepstrum(const float* mel, int64_t ld, int64_t item_stride, const i
                       int32_t T, int32_t n_mels, int32_t n_coef, void* stream);
 int efts_dtw(const float* x, int64_t ldx, int64_t x_item_stride, const int32_t* x_lengths, int32_t Tx, const float* y, int64_t ldy,
              int64_t y_item_stride, const int32_t* y_lengths, int32_t Ty, int32_t D, float* cost, int32_t* path_len, int32_t B, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The warping path itself, and the F0 error read along it.
+ *
+ * efts_dtw_path: the recurrence, tie rule, limits and error codes of efts_dtw (the same kernel body); cost and path_len are bit-identical
+ *   to efts_dtw's on the same input.  In addition
+ *     path : int32 [B][Tx + Ty - 1][2], 8-byte aligned.  path[b][k] = (i, j), the k-th cell of the chosen path in FORWARD order:
+ *            path[b][0] = (0, 0), path[b][path_len[b] - 1] = (x_lengths[b] - 1, y_lengths[b] - 1), every step one of (1, 1), (1, 0), (0, 1).
+ *            Rows at and beyond path_len[b] are left untouched; an item with a length below 1 gets cost NaN, path_len 0 and no path.
+ *     workspace : device memory, 16-byte aligned, B times the per-pair size that the workspace-size entry below returns for the same
+ *            (Tx, Ty); workspace_bytes is what the caller holds.  The forward pass records which predecessor won at every cell -- 2 bits,
+ *            a lane's four rows at one column are one byte, laid out by (band of 1024 rows, wavefront step, lane) so that one step
+ *            stores 256 contiguous bytes; the per-pair size is ceil(Tx / 1024) (Ty + 255) 256 bytes.  The back-trace runs in the same
+ *            launch behind a workgroup barrier and reads the record through LDS, 64 steps at a time.  Contents afterwards: unspecified.
+ *   EFTS_EINVAL: null pointer.  EFTS_ESHAPE: as efts_dtw, or a workspace smaller than B pairs need.  EFTS_EALIGN: workspace or path misaligned.
+ * The workspace-size entry returns that per-pair size in bytes, 0 when Tx or Ty lies outside 1 .. EFTS_DTW_MAX_FRAMES; it is monotone in both.
+ *
+ * efts_f0_path_error: f0_a [B][Ta] and f0_b [B][Tb] (row strides lda, ldb in floats; a value > 0 is a voiced frame's F0 in Hz, anything else
+ *   unvoiced), path as efts_dtw_path writes it with path_item_stride cells per item, path_len [B] (clamped to 0 .. path_item_stride).
+ *   Over the cells (i, j) = path[b][k], k < path_len[b]:
+ *     voiced_pairs[b]  = cells with f0_a[b][i] > 0 and f0_b[b][j] > 0
+ *     f0_rmse_cents[b] = sqrt(mean over those cells of (1200 log2(f0_a[b][i] / f0_b[b][j]))^2); NaN when voiced_pairs[b] == 0
+ *     vuv_error[b]     = cells whose two sides differ in voicing / path_len[b]; NaN when path_len[b] == 0
+ *   A cell that points outside a contour counts as unvoiced on that side and nothing is read for it.  One workgroup per item: lane t sums
+ *   cells t, t + 256, ... in order, the 256 partial sums are added in one fixed tree.
+ *   EFTS_EINVAL: null pointer.  EFTS_ESHAPE: B, Ta or Tb < 1, a row stride below its T, path_item_stride < 1.  EFTS_EALIGN: path misaligned.
+ * ---------------------------------------------------------------------------------- */
+int64_t efts_dtw_path_workspace_bytes(int32_t Tx, int32_t Ty);
+int efts_dtw_path(const float* x, int64_t ldx, int64_t x_item_stride, const int32_t* x_lengths, int32_t Tx, const float* y, int64_t ldy,
+                  int64_t y_item_stride, const int32_t* y_lengths, int32_t Ty, int32_t D, float* cost, int32_t* path_len, int32_t* path,
+                  void* workspace, int64_t workspace_bytes, int32_t B, void* stream);
+int efts_f0_path_error(const float* f0_a, int64_t lda, int32_t Ta, const float* f0_b, int64_t ldb, int32_t Tb, const int32_t* path,
+                       int64_t path_item_stride, const int32_t* path_len, float* f0_rmse_cents, float* vuv_error, int32_t* voiced_pairs, int32_t B,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Pitch tracking: YIN (de Cheveigne & Kawahara 2002) on the frame grid of efts_logmel_fft, so that f0[b][t] belongs to mel[b][t].
+ *   audio   : [B][ld] fp32 in [-1, 1]; the pcm16 entry takes int16 PCM and multiplies every sample by pcm_scale at the load
+ *   lengths : [B] samples per item (clamped to 0 .. ld).  Item b has frames(b) = lengths[b] / hop frames when lengths[b] > pad, else none
+ *   framing : pad = (n_fft - hop) / 2; sample s of frame t is audio index t hop - pad + s, s = 0 .. n_fft - 1, and an index outside
+ *             [0, lengths[b]) is reflected: i < 0 -> -i, i >= lengths[b] -> 2 (lengths[b] - 1) - i.  Nothing outside an item's samples is read.
+ * Per frame x[0 .. n_fft - 1], with W = n_fft / 2, tau_min = floor(sampling_rate / fmax), tau_max = floor(sampling_rate / fmin) (in double):
+ *   d(tau)  = sum over j = 0 .. W - 1, ascending and fused, of (x[j] - x[j + tau])^2,  tau = 1 .. tau_max  (the direct form: the
+ *             energy-plus-autocorrelation form cancels in fp32 on periodic frames)
+ *   d'(tau) = d(tau) tau / (d(1) + .. + d(tau)), and 1 where that running sum is 0; d'(0) = 1.  The running sum is taken in one fixed order:
+ *             lane l of a wave owns the lags l c + 1 .. l c + c, c = ceil(tau_max / 64); the 64 lane totals are scanned, and every lane adds
+ *             its lags in ascending order to the total in front of it.
+ *   decision: the smallest tau in [tau_min, tau_max - 1] with d'(tau) < threshold; then tau advances while tau + 1 <= tau_max - 1 and
+ *             d'(tau + 1) < d'(tau); with s0, s1, s2 = d'(tau - 1), d'(tau), d'(tau + 1): den = (s0 - s1) + (s2 - s1),
+ *             shift = 0.5 (s0 - s2) / den clamped to [-1, 1] (0 when den == 0), f0 = sampling_rate / (tau + shift), aperiodicity = s1.
+ *             No such tau: the frame is unvoiced, f0 = 0 and aperiodicity = the smallest d' over [tau_min, tau_max - 1].
+ *   f0, aperiodicity : [B][T] fp32; 0 for frames at or beyond frames(b)
+ *   cmnd    : optional (NULL: not written) [B][T][tau_max + 1], every d'(tau), tau = 0 .. tau_max; 0 for frames at or beyond frames(b)
+ * fp32, no atomics: an item gives the same bits alone, in any batch position and in any run.
+ * EFTS_EINVAL: null pointer (cmnd excepted).  EFTS_ESHAPE, nothing launched: n_fft other than 512, 1024, 2048; hop outside 1 .. n_fft or
+ * n_fft - hop odd; tau_min < 2; tau_max > W (fmin too low for the window); tau_min >= tau_max - 1; fmin, fmax or threshold not positive;
+ * B outside 1 .. 65535, T < 1, ld outside 1 .. 2^31 - 1.
+ * ---------------------------------------------------------------------------------- */
+int efts_yin(const float* audio, int64_t ld, const int32_t* lengths, float* f0, float* aperiodicity, float* cmnd, int32_t B, int32_t T,
+             int32_t n_fft, int32_t hop, int32_t sampling_rate, float fmin, float fmax, float threshold, void* stream);
+int efts_yin_pcm16(const int16_t* audio, int64_t ld, float pcm_scale, const int32_t* lengths, float* f0, float* aperiodicity, float* cmnd, int32_t B,
+                   int32_t T, int32_t n_fft, int32_t hop, int32_t sampling_rate, float fmin, float fmax, float threshold, void* stream);
 
 #ifdef __cplusplus
 }
