@@ -13,6 +13,7 @@ from __future__ import annotations
 import dataclasses
 import os
 import logging
+from collections import namedtuple
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -179,6 +180,61 @@ class LaunchOptions:
 
     def tag(self) -> tuple:
         return dataclasses.astuple(self) + (O.RC_KERNEL, O.GEMM_TILING)       # (the launch-level switches of ops.py change the launches too)
+
+
+def lengths_and_masks(text_lengths, speech_lengths, dev, rs1: Rows, rs2: Rows, gap1, len1, gap2, len2):
+    """The lengths as int32 device tensors and, where ONE launch can do it, the row masks of both row spaces (efficient_tts.py:137-139)
+    -> (tl, ml, masks_done).  masks_done False (lengths of two dtypes, or not contiguous): only the two casts are enqueued, and the
+    caller launches efts_row_masks per row space where its schedule wants them"""
+    tl_d, ml_d = text_lengths.to(dev), speech_lengths.to(dev)
+    if tl_d.dtype == ml_d.dtype and tl_d.dtype in (torch.int64, torch.int32) and tl_d.is_contiguous() and ml_d.is_contiguous():
+        # both masks + the int32 copies of the lengths in one launch (two casts + two mask launches before)
+        return (*O.row_masks_pair(tl_d, ml_d, rs1, rs2, gap1, len1, gap2, len2), True)
+    return tl_d.to(torch.int32), ml_d.to(torch.int32), False
+
+
+class _Pass:
+    """What every stage of one teacher-forced forward reads.  ws: the workspace of the shape; pk: packed planes by layer name;
+    rs1 / rs2: text- and mel-length row spaces; gap* / len*: their row masks (0 on the gap rows / beyond each item's length as well);
+    tl / ml: int32 lengths on the device; main / side: the streams of the mel-length and the text-length work (main itself without
+    side_stream); vt: the V^T plane of an unfused expand, else None; masks_done: gap1 / len1 are already enqueued (else only
+    gap2 / len2 are, and the schedule launches the text masks behind the fork)"""
+    __slots__ = ("ws", "pk", "text", "speech", "B", "T1", "T2", "rs1", "rs2", "gap1", "len1", "gap2", "len2", "tl", "ml", "main", "side",
+                 "vt", "masks_done")
+
+    def __init__(self, **fields):
+        for k, v in fields.items():
+            setattr(self, k, v)
+
+
+# What a stage of the forward hands to the stages behind it (`_f`: F32Rows, `_p`: operand Plane, `_l`: lo plane of a split-1 stream).
+_Embedded = namedtuple("_Embedded", "x_f x_p start")              # start: the first text-encoder layer still to run
+_TextSide = namedtuple("_TextSide", "key_p val_f val_p")
+_Prenet = namedtuple("_Prenet", "pre_f pre_p pre_l")
+_Front = namedtuple("_Front", "q_p key_p val_f dur v_ready")      # val_f, dur, v_ready: None where an alignment-only pass skips them
+_Aligned = namedtuple("_Aligned", "sidx imv e lde alpha")         # alpha: only for keep=True
+_Head = namedtuple("_Head", "mel sqerr_part n_part")              # sqerr_part: the squared-error partials the head's epilogue left, or None
+
+
+class _TextCursor:
+    """The next text-encoder layer's efts_resconv5 keyword set: where the text stack stands while its layers are launched one by one
+    (by themselves, or as riders of the mel-encoder launches).  x_p is the last launched layer's operand plane."""
+    __slots__ = ("m", "st", "i", "ride_from", "x_f", "x_p", "x_lo")
+
+    def __init__(self, model, st: _Pass, emb: _Embedded, ride_from: int):
+        self.m, self.st, self.i, self.ride_from = model, st, emb.start, ride_from
+        self.x_f, self.x_p, self.x_lo = emb.x_f, emb.x_p, None
+
+    def next(self) -> dict:
+        m, st = self.m, self.st
+        kw, _, y, y_lo = m._res_layer_args(st.ws, "te", "text_encoder", st.pk, st.rs1, self.i, len(m.text_encoder.layers), self.x_f, self.x_p,
+                                           self.x_lo, st.gap1.data_ptr(), m.split, False)
+        self.i, self.x_f, self.x_p, self.x_lo = self.i + 1, None, y, y_lo
+        return kw
+
+    def ride(self, i: int) -> Optional[dict]:
+        """`rider` of _res_stack: the remaining text layers share the launches of mel-encoder layers `ride_from` on"""
+        return self.next() if i >= self.ride_from else None
 
 
 class EfficientTTSCNN(torch.nn.Module):
@@ -456,29 +512,37 @@ class EfficientTTSCNN(torch.nn.Module):
             x_f32, x_pl = o_f32, o_pl
         return x_f32, x_pl
 
-    def _text_side(self, ws, pk, text, rs1: Rows, gap1, len1, on_key=None, vt: Optional[Plane] = None):
-        """embed -> text encoder -> key (split-2 plane, masked), value (fp32 + plane, masked)
-        (efficient_tts.py:144-157 / :246-255).  `on_key()` is called as soon as the key projection is enqueued (the q.k^T launch
-        of the other stream waits for that, not for the value); `vt`: also pack V^T for the alpha'.V launch here."""
+    def _embed_text(self, ws, pk, text, rs1: Rows, lens: Optional[torch.Tensor], mask: Optional[torch.Tensor]) -> _Embedded:
+        """The embedding (efficient_tts.py:144 / :246), or the embedding + text-encoder layer 0 as table look-ups where that form applies.
+        lens (int32 [B]) / mask (the row mask `len1`): zero beyond each item's length (the ragged free-running path); both None: padded
+        ids are real symbols (the teacher-forced forward)"""
         C = self.n_channels
         tab = self._te0_table()
-        if tab is not None:                                    # embedding + layer 0 as table look-ups; padded ids are real symbols here
-            x_f, x_p = self._embed_te0(ws, pk, text, rs1, None, tab)
-            start = 1
+        if tab is not None:
+            return _Embedded(*self._embed_te0(ws, pk, text, rs1, lens, tab), 1)
+        table = self.text_embedding_table.weight.detach()
+        if mask is None:
+            x_f, x_p = ws.f32("emb_f", rs1, C), ws.plane("emb_p", rs1, C, self.split)
+            O.embed(text, table, x_f, x_p, rs1)
         else:
-            x_f = ws.f32("emb_f", rs1, C)
-            x_p = ws.plane("emb_p", rs1, C, self.split)
-            O.embed(text, self.text_embedding_table.weight.detach(), x_f, x_p, rs1)
-            start = 0
-        if start < len(self.text_encoder.layers):
-            _, h_p = self._res_stack(ws, "te", "text_encoder", pk, rs1, x_f, x_p, gap1.data_ptr(), self.split, False, start=start)
-        else:
-            h_p = x_p
+            e_f = ws.f32("emb_raw", rs1, C)
+            O.embed(text, table, e_f, None, rs1)
+            x_f, x_p = ws.f32("emb_f", rs1, C), ws.plane("emb_p", rs1, C, self.split)
+            O.mask_rows(e_f.ptr, mask.data_ptr(), x_f, x_p, rs1.rows, C)
+        return _Embedded(x_f, x_p, 0)
+
+    def _text_stack(self, ws, pk, rs1: Rows, emb: _Embedded, mask_ptr) -> Plane:
+        """the text-encoder layers behind `emb` (efficient_tts.py:148 / :250) -> the operand plane of the last one"""
+        if emb.start >= len(self.text_encoder.layers):
+            return emb.x_p
+        return self._res_stack(ws, "te", "text_encoder", pk, rs1, emb.x_f, emb.x_p, mask_ptr, self.split, False, start=emb.start)[1]
+
+    def _text_side(self, ws, pk, text, rs1: Rows, gap1, len1, vt: Optional[Plane] = None) -> _TextSide:
+        """embed -> text encoder -> key (split-2 plane, masked), value (fp32 + plane, masked)
+        (efficient_tts.py:144-157 / :246-255) on one stream; `vt`: also pack V^T for the alpha'.V launch here."""
+        h_p = self._text_stack(ws, pk, rs1, self._embed_text(ws, pk, text, rs1, None, None), gap1.data_ptr())
         key_p = self._key_proj(ws, pk, rs1, h_p, gap1, len1)
-        if on_key is not None:
-            on_key()
-        val_f, val_p = self._value_proj(ws, pk, rs1, h_p, gap1, len1, vt)
-        return key_p, val_f, val_p
+        return _TextSide(key_p, *self._value_proj(ws, pk, rs1, h_p, gap1, len1, vt))
 
     def _key_proj(self, ws, pk, rs1: Rows, h_p: Plane, gap1, len1) -> Plane:
         """text_encoder_key, zero at padded text (efficient_tts.py:149, :155-156): split-2 operand plane of q.k^T"""
@@ -541,7 +605,8 @@ class EfficientTTSCNN(torch.nn.Module):
                        vt: Optional[Plane] = None, rider=None, after=None, loss_target: Optional[torch.Tensor] = None):
         """Gaussian re-alignment from e, bmm(V^T, alpha') -> decoder -> mel head (efficient_tts.py:184-200 / :270-284).
         `ralpha` [B, T1, T2] receives alpha' (the API tensor); tl / ml: int32 lengths or None (no masks, :270-274);
-        `vt`: V^T already packed (unfused path only)."""
+        `vt`: V^T already packed (unfused path only); `loss_target`: the frames of the loss's mel term, which the head's epilogue takes
+        where its launch fills the chip.  -> _Head: the mel and the squared-error partials that epilogue left (or None, 0)."""
         C = self.n_channels
         h_f, h_p, h_l = self._stream_in(ws, "exp", rs2)
         if self._fused_expand(T1):
@@ -562,20 +627,19 @@ class EfficientTTSCNN(torch.nn.Module):
         # launch: no row-space copy of mel_pred, no clone)
         mel = torch.empty(B, rs2.T, self.odim, dtype=torch.float32, device=h_p.buf.device)
         wh = pk["head"]
-        loss_kw = {}
+        loss_kw, part, n_part = {}, None, 0
         if loss_target is not None and self.fuse_mel_loss and self.use_masking and len2_ptr is not None and self.odim % 4 == 0 and self.odim <= 128:
             # the mel term of the loss (:220, fastspeech_loss.py:54-67) in the head's epilogue: the tile is in LDS, the target frames arrive
             # where a residual would, the row mask IS the loss mask -- one launch less at the end of every forward.  Only where AUTO picks the
             # generic tiling anyway (one workgroup per CU or more): a short launch keeps its 64-column tiles and the separate loss launch
             mt = (rs2.T + 127) // 128
             if B * mt >= (self.fuse_mel_loss_min_wgs or torch.cuda.get_device_properties(mel.device).multi_processor_count):
-                part = ws.tensor("sqerr_part", (B * mt * 4,))
+                part, n_part = ws.tensor("sqerr_part", (B * mt * 4,)), B * mt * 4
                 loss_kw = dict(sqerr_target=loss_target, sqerr_part=part)
-                object.__setattr__(self, "_sqerr_parts", (part, B * mt * 4))
         O.gemm(a=d_p, b_ptr=wh.ptr, ldb=wh.ld, m=rs2.T, n=self.odim, batch=B, a_batch_stride=rs2.Tp * d_p.ld, bias=self.mel_output_layer.bias,
                rowmask_ptr=len2_ptr if len2_ptr is not None else gap2.data_ptr(), rowmask_batch_stride=rs2.Tp,
                out_f32_ptr=mel.data_ptr(), ldo=self.odim, out_batch_stride=rs2.T * self.odim, **loss_kw)
-        return mel
+        return _Head(mel, part, n_part)
 
     def _require(self, t: torch.Tensor):
         if not t.is_cuda:
@@ -642,13 +706,104 @@ class EfficientTTSCNN(torch.nn.Module):
         finally:
             object.__setattr__(self, "_drop_now", prev)
 
-    def _forward_body(self, text, text_lengths, speech, speech_lengths, keep: bool = False, upto_align: bool = False):
-        """upto_align (align()): stop after the IMV block -- no value projection of the merged path, no duration predictor, decoder,
-        mel head or losses -- and return (imv, e, tl, ml) (e: this workspace's buffer)"""
+    # ------------------------------------------------------------------ the schedule of the forward: every stage call, fork, hand-over and join
+    def _forward_body(self, text, text_lengths, speech, speech_lengths, keep: bool = False):
+        """The whole teacher-forced forward.  Two HIP streams: the text side (masks, embed, 5 convs, K/V) and the duration predictor do
+        not depend on the mel side (prenet, 3 convs) and run on `side` beside the mel-length kernels on `main`."""
+        st = self._begin_forward(text, text_lengths, speech, speech_lengths)    # masks on main
+        fr, al = self._to_alignment(st, keep, full=True)
+        ralpha = torch.empty(st.B, st.T1, st.T2, dtype=torch.float32, device=st.text.device)
+        st.main.wait_event(fr.v_ready)                                          # V from the side stream
+        head = self._expand_decode(st.ws, st.pk, st.B, st.T1, st.rs1, st.rs2, fr.val_f, al.e, st.tl, st.ml, ralpha, st.len2.data_ptr(), st.gap2,
+                                   vt=st.vt, loss_target=st.speech)             # :184-200
+        st.main.wait_stream(st.side)                                            # duration predictor done
+        out3 = self._losses(st, head, fr.dur, al.lde)                           # :220-227
+        # (for inspection only -- tests look whether the head's epilogue took the loss's mel term; nothing reads it back)
+        object.__setattr__(self, "_sqerr_parts", None if head.sqerr_part is None else (head.sqerr_part, head.n_part))
+        ret = (out3[0], LazyStats(out3), al.imv, ralpha, head.mel, st.speech)
+        extra = dict(e=al.e, log_delta_e=al.lde, dur_pred=fr.dur.view(st.B, st.rs1.Tp)[:, :st.T1], ws=st.ws) if keep else None
+        return ret, extra
+
+    def _align_body(self, text, text_lengths, speech, speech_lengths) -> Tuple[_Pass, _Aligned]:
+        """The forward through the IMV block and nothing behind it (align()): no decoder, mel head or losses, and none of the launches
+        only they read.  al.e is the workspace's buffer."""
+        st = self._begin_forward(text, text_lengths, speech, speech_lengths)
+        _, al = self._to_alignment(st, False, full=False)
+        st.main.wait_stream(st.side)
+        return st, al
+
+    def _to_alignment(self, st: _Pass, keep: bool, full: bool) -> Tuple[_Front, _Aligned]:
+        """fork, both encoders on their streams, K behind the mel encoder, then the alignment block on main.  full False: without what
+        only the decoder and the losses read (_front_merged, _front_split)"""
+        st.side.wait_stream(st.main)
+        merged = self._on_resconv(st.rs2) and len(self.text_encoder.layers) >= 1 and len(self.mel_encoder.layers) >= 1
+        fr = self._front_merged(st, full) if merged else self._front_split(st, full)
+        sidx, alpha = self._soft_index(st, fr.q_p, fr.key_p, keep)
+        return fr, self._imv(st, sidx, alpha)
+
+    def _front_merged(self, st: _Pass, full: bool) -> _Front:
+        """Long row spaces.  The last min(nt, nm) text-encoder layers ride in the persistent launches of the mel-encoder layers (one
+        grouped efts_resconv5_multi launch per pair: the text rows are scheduled behind the mel rows at the long launch's efficiency).
+        A persistent launch owns every CU's LDS, so a text-length launch of its own beside it would get the 4 spare CUs: only the
+        first nt - nm text layers run by themselves (efts_resconv5 on the short row space), beside the HBM-bound prenet on the second
+        stream.  full False skips the value projection and the duration predictor."""
+        main, side = st.main, st.side
+        nt, nm = len(self.text_encoder.layers), len(self.mel_encoder.layers)
+        first = 0 if self._te0_table() is None else 1                          # (layer 0 may be table look-ups: it never rides)
+        nr = min(nt - first, nm)
+        ns = nt - nr                                                           # text layers that run by themselves first
+        # The first text layers and the prenet share the chip by halves: both kinds of workgroup take a whole CU (LDS), the
+        # prenet is bound by HBM -- which half the CUs saturate -- and a text-length layer by streaming its weights, so the
+        # prenet's grid is capped at half the CUs and the text layers are scheduled onto the other half.
+        cus = torch.cuda.get_device_properties(st.text.device).multi_processor_count
+        share = ns > first and cus >= 64
+        with O.on_stream(side):
+            pre = self._prenet(st, cus // 2 if share else 0)                   # (r6: 128 / 144 / 160 / 176 CUs for the prenet measured: no difference)
+            pre_ready = O.hand_over(side)
+        te_plan = O.resconv5_plan_buf(st.rs1.rows, self.n_channels, cus // 2 - 2) if share else None      # (a host-side table: no launch)
+        if not st.masks_done:
+            O.row_masks(st.tl, st.rs1, st.gap1, st.len1)                       # :137 (behind the fork, on main: beside the prenet)
+        cur = _TextCursor(self, st, self._embed_text(st.ws, st.pk, st.text, st.rs1, None, None), ride_from=nm - nr)    # :144
+        self._text_layers_alone(cur, ns, te_plan)                              # :148
+        main.wait_event(pre_ready)
+        q_p = self._mel_stack(st, pre, rider=cur.ride)
+        te_done = O.hand_over(main)
+        key_p = self._key_proj(st.ws, st.pk, st.rs1, cur.x_p, st.gap1, st.len1)       # :149, :155-156 (q.k^T is next on this stream)
+        side.wait_event(te_done)
+        val_f = dur = v_ready = None
+        if full:
+            # the value projection beside the key projection, then the duration predictor (needed by the loss only).  (Its k3
+            # convolutions as riders of decoder launches: measured slower, 1.665 vs 1.633 ms, r3.)
+            with O.on_stream(side):
+                val_f, val_p = self._value_proj(st.ws, st.pk, st.rs1, cur.x_p, st.gap1, st.len1, st.vt)      # :150-157
+                v_ready = O.hand_over(side)
+                dur = self._duration(st.ws, st.pk, st.rs1, val_p, st.gap1, st.len1.data_ptr(), 0)            # :219
+        return _Front(q_p, key_p, val_f, dur, v_ready)
+
+    def _front_split(self, st: _Pass, full: bool) -> _Front:
+        """Short row spaces.  The text-side launches, on the second HIP stream, fill the tail rounds of the mel-length kernels; the
+        q.k^T launch waits for the key projection, not for the value.  full False skips the duration predictor."""
+        ws, pk, rs1, gap1, len1, side = st.ws, st.pk, st.rs1, st.gap1, st.len1, st.side
+        with O.on_stream(side):
+            if not st.masks_done:
+                O.row_masks(st.tl, rs1, gap1, len1)                            # :137 (behind the fork, on side)
+            h_p = self._text_stack(ws, pk, rs1, self._embed_text(ws, pk, st.text, rs1, None, None), gap1.data_ptr())    # :144-148
+            key_p = self._key_proj(ws, pk, rs1, h_p, gap1, len1)               # :149, :155-156
+            k_ready = O.hand_over(side)
+            val_f, val_p = self._value_proj(ws, pk, rs1, h_p, gap1, len1, st.vt)      # :150-157
+            v_ready = O.hand_over(side)
+            dur = self._duration(ws, pk, rs1, val_p, gap1, len1.data_ptr(), 0) if full else None     # :219
+        q_p = self._mel_stack(st, self._prenet(st))
+        st.main.wait_event(k_ready)
+        return _Front(q_p, key_p, val_f, dur, v_ready)
+
+    # ------------------------------------------------------------------ the stages of the forward (launches on the current stream; no fork, no join)
+    def _begin_forward(self, text, text_lengths, speech, speech_lengths) -> _Pass:
+        """workspace, row spaces, streams and the masks that go in front of the fork: both row spaces' in one launch, else (lengths of
+        two dtypes) the mel mask only -- the prenet on the side stream reads gap2"""
         dev = text.device
         B, T1 = text.shape
         T2 = speech.shape[1]
-        C = self.n_channels
         text = text.contiguous()
         speech = speech.contiguous().float()
         pk = self.planes.get(self)
@@ -656,124 +811,64 @@ class EfficientTTSCNN(torch.nn.Module):
         rs1, rs2 = Rows(B, T1, self.row_gap), Rows(B, T2, self.row_gap)
         gap1, len1 = ws.tensor("gap1", (rs1.rows,)), ws.tensor("len1", (rs1.rows,))
         gap2, len2 = ws.tensor("gap2", (rs2.rows,)), ws.tensor("len2", (rs2.rows,))
-        tl_d, ml_d = text_lengths.to(dev), speech_lengths.to(dev)
-        masks_done = tl_d.dtype == ml_d.dtype and tl_d.dtype in (torch.int64, torch.int32) and tl_d.is_contiguous() and ml_d.is_contiguous()
-        if masks_done:
-            # :137-139 for both row spaces + the int32 copies of the lengths in ONE launch (two casts + two mask launches before)
-            tl, ml = O.row_masks_pair(tl_d, ml_d, rs1, rs2, gap1, len1, gap2, len2)
-        else:
-            tl, ml = tl_d.to(torch.int32), ml_d.to(torch.int32)
-        # The text side (masks, embed, 5 convs, K/V) and the duration predictor do not depend on the mel side (prenet, 3 convs).
-        main = torch.cuda.current_stream(dev)
-        side = self._side_stream(dev)
+        tl, ml, masks_done = lengths_and_masks(text_lengths, speech_lengths, dev, rs1, rs2, gap1, len1, gap2, len2)   # :137-139
         if not masks_done:
-            O.row_masks(ml, rs2, gap2, len2)                                      # :139 (in FRONT of the fork: the prenet on the side stream reads gap2)
-        side.wait_stream(main)
-        vt = None if self._fused_expand(T1) else ws.raw_plane("vt", B * C, T1, self.align_split)
-        nt, nm = len(self.text_encoder.layers), len(self.mel_encoder.layers)
-        merged = self._on_resconv(rs2) and nt >= 1 and nm >= 1
-        v_ready = torch.cuda.Event()
+            O.row_masks(ml, rs2, gap2, len2)                                   # :139
+        vt = None if self._fused_expand(T1) else ws.raw_plane("vt", B * self.n_channels, T1, self.align_split)
+        return _Pass(ws=ws, pk=pk, text=text, speech=speech, B=B, T1=T1, T2=T2, rs1=rs1, rs2=rs2, gap1=gap1, len1=len1, gap2=gap2, len2=len2,
+                     tl=tl, ml=ml, main=torch.cuda.current_stream(dev), side=self._side_stream(dev), vt=vt, masks_done=masks_done)
 
-        def prenet(max_wgs=0):                                                    # :161
-            pre_f, pre_p, pre_l = self._stream_in(ws, "pre", rs2)
-            wp = pk["prenet"]
-            pre_dp, pre_seed = self._drop(40)                                      # mel_prenet's Dropout (:76-80)
-            if self.act_general is not None:
-                mel_in = ws.plane("mel_in", rs2, self.odim, self.split)
-                O.pack_rows(speech, None, mel_in, rs2)
-                z = ws.f32("pre_z", rs2, C)
-                O.gemm(a=mel_in, b_ptr=wp.ptr, ldb=wp.ld, m=rs2.rows, n=C, bias=self.mel_prenet[0].bias, out_f32_ptr=z.ptr, ldo=C)
-                O.act_apply(self.act_general, z.ptr, None, gap2.data_ptr(), pre_f, pre_p, rs2.rows, C, pre_dp, pre_seed)
-            elif pre_dp == 0.0 and self.fuse_prenet and self.odim % 8 == 0 and self.odim <= 128 and C % 128 == 0:
-                # straight from the caller's fp32 frames: no operand plane of the mel input, one launch (bit-identical on every frame)
-                O.frame_linear(x=speech, w=wp, bias=self.mel_prenet[0].bias, act=L.ACT_LEAKY, slope=self.slope, rs=rs2,
-                               y=pre_p, y_lo=pre_l, y_f32=pre_f, max_workgroups=max_wgs)
-            else:
-                mel_in = ws.plane("mel_in", rs2, self.odim, self.split)
-                O.pack_rows(speech, None, mel_in, rs2)
-                O.gemm(a=mel_in, b_ptr=wp.ptr, ldb=wp.ld, m=rs2.rows, n=C, act=L.ACT_LEAKY, slope=self.slope,
-                       bias=self.mel_prenet[0].bias, rowmask_ptr=gap2.data_ptr(), out_f32_ptr=None if pre_f is None else pre_f.ptr,
-                       ldo=C, out_plane=pre_p, out_plane_lo=pre_l, drop_p=pre_dp, drop_seed=pre_seed)
-            return pre_f, pre_p, pre_l
-
-        def mel_stack(pre_f, pre_p, pre_l, rider=None):                            # :162-164
-            if self.mel_query_fc is None:
-                _, q_p = self._res_stack(ws, "me", "mel_encoder", pk, rs2, pre_f, pre_p, gap2.data_ptr(), self.align_split, False, x_lo=pre_l, rider=rider)
-                return q_p
-            _, mh_p = self._res_stack(ws, "me", "mel_encoder", pk, rs2, pre_f, pre_p, gap2.data_ptr(), self.split, False, x_lo=pre_l, rider=rider)
-            q_p = ws.plane("q_p", rs2, C, self.align_split)
-            wq = pk["qfc"]
-            O.gemm(a=mh_p, b_ptr=wq.ptr, ldb=wq.ld, m=rs2.rows, n=C, bias=self.mel_query_fc.bias, rowmask_ptr=gap2.data_ptr(), out_plane=q_p)
-            return q_p
-
-        if merged:
-            # The last min(nt, nm) text-encoder layers ride in the persistent launches of the mel-encoder layers (one grouped
-            # efts_resconv5_multi launch per pair: the text rows are scheduled behind the mel rows at the long launch's efficiency).
-            # A persistent launch owns every CU's LDS, so a text-length launch of its own beside it would get the 4 spare CUs:
-            # only the first nt - nm text layers run by themselves (efts_resconv5 on the short row space), beside the HBM-bound
-            # prenet on the second stream.
-            nr = min(nt - (1 if self._te0_table() is not None else 0), nm)       # (layer 0 may be table look-ups: it never rides)
-            ns = nt - nr                                                           # text layers that run by themselves first
-            pre_ready, te_done = torch.cuda.Event(), torch.cuda.Event()
-            # The first text layers and the prenet share the chip by halves: both kinds of workgroup take a whole CU (LDS), the
-            # prenet is bound by HBM -- which half the CUs saturate -- and a text-length layer by streaming its weights, so the
-            # prenet's grid is capped at half the CUs and the text layers are scheduled onto the other half.
-            cus = torch.cuda.get_device_properties(dev).multi_processor_count
-            share = ns > (1 if self._te0_table() is not None else 0) and cus >= 64
-            with O.on_stream(side):
-                pre = prenet(cus // 2 if share else 0)                             # (r6: 128 / 144 / 160 / 176 CUs for the prenet measured: no difference)
-                pre_ready.record(side)
-            te_plan = O.resconv5_plan_buf(rs1.rows, C, cus // 2 - 2) if share else None
-            if not masks_done:
-                O.row_masks(tl, rs1, gap1, len1)                                  # :137
-            tab = self._te0_table()
-            if tab is not None:                                                   # :144 + layer 0 of :148 as table look-ups
-                x_f, x_p = self._embed_te0(ws, pk, text, rs1, None, tab)
-                first = 1
-            else:
-                x_f = ws.f32("emb_f", rs1, C)
-                x_p = ws.plane("emb_p", rs1, C, self.split)
-                O.embed(text, self.text_embedding_table.weight.detach(), x_f, x_p, rs1)      # :144
-                first = 0
-            tstate = dict(x_f=x_f, x_p=x_p, x_lo=None)
-
-            def text_layer(i):                                                    # efts_resconv5 keyword set of text layer i (:148)
-                kw, _, y, y_lo = self._res_layer_args(ws, "te", "text_encoder", pk, rs1, i, nt, tstate["x_f"], tstate["x_p"], tstate["x_lo"],
-                                                      gap1.data_ptr(), self.split, False)
-                tstate.update(x_f=None, x_p=y, x_lo=y_lo)
-                return kw
-
-            for i in range(first, ns):
-                O.resconv5(plan=te_plan, **text_layer(i))
-            main.wait_event(pre_ready)
-            q_p = mel_stack(*pre, rider=lambda i: text_layer(ns + i - (nm - nr)) if i >= nm - nr else None)
-            te_done.record(main)
-            key_p = self._key_proj(ws, pk, rs1, tstate["x_p"], gap1, len1)          # :149, :155-156 (q.k^T is next on this stream)
-            side.wait_event(te_done)
-            if not upto_align:
-                with O.on_stream(side):                                           # the value projection beside the key projection, then the
-                    val_f, val_p = self._value_proj(ws, pk, rs1, tstate["x_p"], gap1, len1, vt)   # :150-157   duration predictor (:219;
-                    v_ready.record(side)                                          # needed by the loss only).  (Its k3 convolutions as riders of
-                    dur = self._duration(ws, pk, rs1, val_p, gap1, len1.data_ptr(), 0)    # decoder launches: measured slower, 1.665 vs 1.633 ms, r3.)
+    def _prenet(self, st: _Pass, max_wgs: int = 0) -> _Prenet:
+        """mel_prenet (:161) -> the mel encoder's input buffers.  max_wgs: cap of the fused launch's grid (0: none)"""
+        ws, pk, rs2, speech, gap2, C = st.ws, st.pk, st.rs2, st.speech, st.gap2, self.n_channels
+        pre_f, pre_p, pre_l = self._stream_in(ws, "pre", rs2)
+        wp = pk["prenet"]
+        pre_dp, pre_seed = self._drop(40)                                      # mel_prenet's Dropout (:76-80)
+        if self.act_general is not None:
+            mel_in = ws.plane("mel_in", rs2, self.odim, self.split)
+            O.pack_rows(speech, None, mel_in, rs2)
+            z = ws.f32("pre_z", rs2, C)
+            O.gemm(a=mel_in, b_ptr=wp.ptr, ldb=wp.ld, m=rs2.rows, n=C, bias=self.mel_prenet[0].bias, out_f32_ptr=z.ptr, ldo=C)
+            O.act_apply(self.act_general, z.ptr, None, gap2.data_ptr(), pre_f, pre_p, rs2.rows, C, pre_dp, pre_seed)
+        elif pre_dp == 0.0 and self.fuse_prenet and self.odim % 8 == 0 and self.odim <= 128 and C % 128 == 0:
+            # straight from the caller's fp32 frames: no operand plane of the mel input, one launch (bit-identical on every frame)
+            O.frame_linear(x=speech, w=wp, bias=self.mel_prenet[0].bias, act=L.ACT_LEAKY, slope=self.slope, rs=rs2,
+                           y=pre_p, y_lo=pre_l, y_f32=pre_f, max_workgroups=max_wgs)
         else:
-            # second HIP stream: the text-side launches fill the tail rounds of the mel-length kernels
-            k_ready = torch.cuda.Event()
-            with O.on_stream(side):
-                if not masks_done:
-                    O.row_masks(tl, rs1, gap1, len1)                              # :137
-                key_p, val_f, val_p = self._text_side(ws, pk, text, rs1, gap1, len1, on_key=lambda: k_ready.record(side), vt=vt)  # :144-157
-                v_ready.record(side)
-                if not upto_align:
-                    dur = self._duration(ws, pk, rs1, val_p, gap1, len1.data_ptr(), 0)    # :219
-            q_p = mel_stack(*prenet())
-            main.wait_event(k_ready)
+            mel_in = ws.plane("mel_in", rs2, self.odim, self.split)
+            O.pack_rows(speech, None, mel_in, rs2)
+            O.gemm(a=mel_in, b_ptr=wp.ptr, ldb=wp.ld, m=rs2.rows, n=C, act=L.ACT_LEAKY, slope=self.slope,
+                   bias=self.mel_prenet[0].bias, rowmask_ptr=gap2.data_ptr(), out_f32_ptr=None if pre_f is None else pre_f.ptr,
+                   ldo=C, out_plane=pre_p, out_plane_lo=pre_l, drop_p=pre_dp, drop_seed=pre_seed)
+        return _Prenet(pre_f, pre_p, pre_l)
 
+    def _mel_stack(self, st: _Pass, pre: _Prenet, rider=None) -> Plane:
+        """mel encoder (+ mel_query_fc) (:162-164) -> q as the split-2 operand plane of q.k^T"""
+        ws, pk, rs2, C = st.ws, st.pk, st.rs2, self.n_channels
+        gap_ptr = st.gap2.data_ptr()
+        if self.mel_query_fc is None:
+            return self._res_stack(ws, "me", "mel_encoder", pk, rs2, pre.pre_f, pre.pre_p, gap_ptr, self.align_split, False, x_lo=pre.pre_l, rider=rider)[1]
+        _, mh_p = self._res_stack(ws, "me", "mel_encoder", pk, rs2, pre.pre_f, pre.pre_p, gap_ptr, self.split, False, x_lo=pre.pre_l, rider=rider)
+        q_p = ws.plane("q_p", rs2, C, self.align_split)
+        wq = pk["qfc"]
+        O.gemm(a=mh_p, b_ptr=wq.ptr, ldb=wq.ld, m=rs2.rows, n=C, bias=self.mel_query_fc.bias, rowmask_ptr=gap_ptr, out_plane=q_p)
+        return q_p
+
+    @staticmethod
+    def _text_layers_alone(cur: _TextCursor, upto: int, plan) -> None:
+        """the text-encoder layers in front of layer `upto`, each in an efts_resconv5 launch of its own under `plan` (:148)"""
+        while cur.i < upto:
+            O.resconv5(plan=plan, **cur.next())
+
+    def _soft_index(self, st: _Pass, q_p: Plane, key_p: Plane, keep: bool):
+        """scaled dot-product scores, softmax over the keys, expected key index per frame (:390-398, :168, :312)
+        -> (sidx [B, T2], alpha [B, T1, T2] for keep, else None)"""
+        ws, B, T1, T2, rs1, rs2, tl, ml, C = st.ws, st.B, st.T1, st.T2, st.rs1, st.rs2, st.tl, st.ml, self.n_channels
         sidx = ws.tensor("sidx", (B, T2))
-        imv = torch.empty(B, T2, dtype=torch.float32, device=dev)              # returned to the caller: written in place, no copy
         alpha = ws.tensor("alpha", (B, T1, T2)) if keep else None
         if T1 <= 128 and not keep and self.fuse_soft_index:
-            # :390-398, :168, :312 in one launch: a 128-column tile holds whole score rows, so the softmax over the keys and its
-            # expected index are taken from the staged tile and the 4 B T2 T1 bytes of scores are neither written nor re-read
+            # in one launch: a 128-column tile holds whole score rows, so the softmax over the keys and its expected index are taken
+            # from the staged tile and the 4 B T2 T1 bytes of scores are neither written nor re-read
             O.gemm(a=q_p, b_ptr=key_p.ptr, ldb=key_p.ld, m=T2, n=T1, batch=B, a_batch_stride=rs2.Tp * q_p.ld,
                    b_batch_stride=rs1.Tp * key_p.ld, alpha=O.INV_SQRT(C), soft_index=sidx, key_len=tl, query_len=ml)
         else:
@@ -782,40 +877,37 @@ class EfficientTTSCNN(torch.nn.Module):
                    b_batch_stride=rs1.Tp * key_p.ld, alpha=O.INV_SQRT(C), out_f32_ptr=scores.data_ptr(), ldo=T1,
                    out_batch_stride=T2 * T1)
             O.attn_soft_index(scores, T1, tl, ml, sidx, alpha, B, T1, T2)         # :391-398, :168, :312
+        return sidx, alpha
+
+    def _imv(self, st: _Pass, sidx: torch.Tensor, alpha: Optional[torch.Tensor]) -> _Aligned:
+        """index mapping vector, aligned positions e and the duration target log(delta e) (:314-345, :178-180, :203-216)"""
+        ws, B, T1, T2, tl, ml = st.ws, st.B, st.T1, st.T2, st.tl, st.ml
+        imv = torch.empty(B, T2, dtype=torch.float32, device=sidx.device)       # returned to the caller: written in place, no copy
         e, lde = ws.tensor("e", (B, T1)), ws.tensor("lde", (B, T1))
         if self.fuse_align and O.imv_align_fits(T1, T2):
-            O.imv_align(sidx, tl, ml, float(self.sigma_e), float(self.duration_offset), self.delta_e_method_1, imv, e, lde, B, T1, T2)   # :314-345, :203-216
+            O.imv_align(sidx, tl, ml, float(self.sigma_e), float(self.duration_offset), self.delta_e_method_1, imv, e, lde, B, T1, T2)
         else:
             O.imv_scan(sidx, tl, ml, imv, B, T2)                                  # :314-323
             O.aligned_positions(imv, tl, ml, float(self.sigma_e), float(self.duration_offset), e, lde if self.delta_e_method_1 else None,
                                 B, T1, T2)                                        # :178-180, :203-216
             if not self.delta_e_method_1:
                 O.duration_target(e, tl, ml, float(self.duration_offset), False, lde, B, T1)   # :205-213
-        if upto_align:
-            main.wait_stream(side)
-            return imv, e, tl, ml
-        ralpha = torch.empty(B, T1, T2, dtype=torch.float32, device=dev)
+        return _Aligned(sidx, imv, e, lde, alpha)
 
-        main.wait_event(v_ready)
-        object.__setattr__(self, "_sqerr_parts", None)
-        mel = self._expand_decode(ws, pk, B, T1, rs1, rs2, val_f, e, tl, ml, ralpha, len2.data_ptr(), gap2, vt=vt,
-                                  loss_target=speech)                                                        # :184-200
-        main.wait_stream(side)                                                     # duration predictor done
-
-        out3 = torch.empty(3, dtype=torch.float32, device=dev)                     # :220-227
+    def _losses(self, st: _Pass, head: _Head, dur: torch.Tensor, lde: torch.Tensor) -> torch.Tensor:
+        """(loss, mel_loss, duration_loss) on the device (:220-227), from the squared-error partials of the head's epilogue where it left them"""
+        B, T1, T2, tl, ml = st.B, st.T1, st.T2, st.tl, st.ml
+        out3 = torch.empty(3, dtype=torch.float32, device=ml.device)
         # use_masking=False (fastspeech_loss.py:63-67): plain means over the padded tensors = the masked sums taken with full lengths
         # (mel_pred, dur_pred and log_delta_e are zero beyond each item's length, speech is whatever the caller padded with)
         ml_loss = ml if self.use_masking else torch.full_like(ml, T2)
         tl_loss = tl if self.use_masking else torch.full_like(tl, T1)
-        if self._sqerr_parts is not None:                                          # the mel head left the squared-error partial sums
-            O.losses_from_parts(self._sqerr_parts[0], self._sqerr_parts[1], ml_loss, dur, lde, tl_loss, out3, B, T1, rs1.Tp, T2, self.odim)
+        if head.sqerr_part is not None:
+            O.losses_from_parts(head.sqerr_part, head.n_part, ml_loss, dur, lde, tl_loss, out3, B, T1, st.rs1.Tp, T2, self.odim)
         else:
-            O.masked_losses(mel.data_ptr(), self.odim, speech, ml_loss, dur, lde, tl_loss, out3, ws.tensor("loss_ws", (1024,)), B, T1,
-                            rs1.Tp, T2, T2, self.odim)
-        mel_pred = mel
-        ret = (out3[0], LazyStats(out3), imv, ralpha, mel_pred, speech)
-        extra = dict(e=e, log_delta_e=lde, dur_pred=dur.view(B, rs1.Tp)[:, :T1], ws=ws) if keep else None
-        return ret, extra
+            O.masked_losses(head.mel.data_ptr(), self.odim, st.speech, ml_loss, dur, lde, tl_loss, out3, st.ws.tensor("loss_ws", (1024,)), B, T1,
+                            st.rs1.Tp, T2, T2, self.odim)
+        return out3
 
     # ------------------------------------------------------------------ inference (efficient_tts.py:230-285)
     @torch.no_grad()
@@ -882,7 +974,7 @@ class EfficientTTSCNN(torch.nn.Module):
         gap2 = ws2.tensor("gap2", (rs2.rows,))
         O.row_masks(torch.full((1,), t2, dtype=torch.int32, device=dev), rs2, gap2, None)
         ralpha = torch.empty(1, T1, t2, dtype=torch.float32, device=dev)
-        mel = self._expand_decode(ws2, pk, 1, T1, rs1, rs2, val_f, e, None, None, ralpha, None, gap2)   # :270-284
+        mel = self._expand_decode(ws2, pk, 1, T1, rs1, rs2, val_f, e, None, None, ralpha, None, gap2).mel   # :270-284
         return mel, ralpha
 
     # ------------------------------------------------------------------ batched ragged inference (extension)
@@ -932,31 +1024,13 @@ class EfficientTTSCNN(torch.nn.Module):
         phoneme from efts_duration_control, returned as a third output (mel length -1: a rejected item)."""
         dev = text.device
         B, T1 = text.shape
-        C = self.n_channels
         pk = self.planes.get(self)
         rs1 = Rows(B, T1, self.row_gap)
         gap1, len1 = ws.tensor("gap1", (rs1.rows,)), ws.tensor("len1", (rs1.rows,))
         O.row_masks(tl, rs1, gap1, len1)
         # embedding with padded positions zeroed, then every layer masked by the item length
-        tab = self._te0_table()
-        if tab is not None:                                    # embedding + layer 0 as table look-ups, zero beyond each item's length
-            x_f, x_p = self._embed_te0(ws, pk, text.contiguous(), rs1, tl, tab)
-            start = 1
-        else:
-            e_f = ws.f32("emb_raw", rs1, C)
-            O.embed(text.contiguous(), self.text_embedding_table.weight.detach(), e_f, None, rs1)
-            x_f, x_p = ws.f32("emb_f", rs1, C), ws.plane("emb_p", rs1, C, self.split)
-            O.mask_rows(e_f.ptr, len1.data_ptr(), x_f, x_p, rs1.rows, C)
-            start = 0
-        if start < len(self.text_encoder.layers):
-            _, h_p = self._res_stack(ws, "te", "text_encoder", pk, rs1, x_f, x_p, len1.data_ptr(), self.split, False, start=start)
-        else:
-            h_p = x_p
-        val_f, val_p = ws.f32("val_f", rs1, C), ws.plane("val_p", rs1, C, self.split)
-        shared = self.share_text_encoder_key_value            # (:252-253)
-        wv = pk["key"] if shared else pk["value"]
-        O.gemm(a=h_p, b_ptr=wv.ptr, ldb=wv.ld, m=rs1.rows, n=C, bias=(self.text_encoder_key if shared else self.text_encoder_value).bias,
-               rowmask_ptr=len1.data_ptr(), out_f32_ptr=val_f.ptr, ldo=C, out_plane=val_p, tiling=self._til(rs1.rows))
+        h_p = self._text_stack(ws, pk, rs1, self._embed_text(ws, pk, text.contiguous(), rs1, tl, len1), len1.data_ptr())
+        _, val_p = self._value_proj(ws, pk, rs1, h_p, len1, len1)                       # (:252-253)
         delta = self._duration(ws, pk, rs1, val_p, len1, len1.data_ptr(), 1)          # zero beyond each length
         # durations -> positions e = cumsum, mel lengths round(e[len - 1]) (:260, :270), positions from 0 for method 2 (:261-265)
         e = torch.empty(B, T1, dtype=torch.float32, device=dev)
@@ -981,7 +1055,7 @@ class EfficientTTSCNN(torch.nn.Module):
         gap2, len2 = ws2.tensor("gap2", (rs2.rows,)), ws2.tensor("len2", (rs2.rows,))
         O.row_masks(ml, rs2, gap2, len2)
         ralpha = torch.empty(B, T1, T2, dtype=torch.float32, device=dev)
-        mel = self._expand_decode(ws2, pk, B, T1, rs1, rs2, val_f, e, tl, ml, ralpha, len2.data_ptr(), len2)
+        mel = self._expand_decode(ws2, pk, B, T1, rs1, rs2, val_f, e, tl, ml, ralpha, len2.data_ptr(), len2).mel
         return mel, ralpha
 
     @torch.no_grad()
@@ -1111,8 +1185,9 @@ class EfficientTTSCNN(torch.nn.Module):
         object.__setattr__(self, "_drop_now", None)
         try:
             with O.stream_scope():
-                imv, e, tl, ml = self._forward_body(text, text_lengths, speech, speech_lengths, upto_align=True)
-                e = e.clone()                                  # (the workspace's buffer: the next forward() overwrites it)
+                st, al = self._align_body(text, text_lengths, speech, speech_lengths)
+                imv, tl, ml = al.imv, st.tl, st.ml
+                e = al.e.clone()                               # (the workspace's buffer: the next forward() overwrites it)
                 valid = torch.arange(T1, device=e.device)[None, :] < tl.to(torch.int64)[:, None]
                 if self.delta_e_method_1:                      # :204  delta_e_i = e_i - e_{i-1}, e_{-1} = 0
                     dur = torch.diff(e, dim=1, prepend=torch.zeros(B, 1, device=e.device))

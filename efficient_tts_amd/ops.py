@@ -63,6 +63,16 @@ class on_stream:
         self.ctx.__exit__(*a)
 
 
+def hand_over(src: "torch.cuda.Stream", dst: Optional["torch.cuda.Stream"] = None) -> "torch.cuda.Event":
+    """THE hand-over between streams: what is enqueued on `src` so far is visible to `dst`.  dst None: the wait happens later, on the
+    returned event (`dst.wait_event(ev)`) -- work enqueued on `dst` in between overlaps what `src` runs behind the record"""
+    ev = torch.cuda.Event()
+    ev.record(src)
+    if dst is not None:
+        dst.wait_event(ev)
+    return ev
+
+
 def _stream() -> int:
     return _cached_stream if _cached_stream is not None else torch.cuda.current_stream().cuda_stream
 

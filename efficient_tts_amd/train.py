@@ -16,8 +16,8 @@ import torch
 
 from . import lib as L
 from . import ops as O
-from .ops import F32Rows, PackedWeight, Plane, Rows
-from .model import require_trainable
+from .ops import F32Rows, PackedWeight, Plane, Rows, hand_over
+from .model import lengths_and_masks, require_trainable
 
 # Test hooks and tuning constants of the training pass (module-level: bench.py --train-set NAME=INT, tests).  Round 6 removed the decided A/Bs
 # (_PACK_SPLIT, _NARROW_TN, _EARLY_PACKS: always on) and did not keep its own (_WGRAD_EARLY, _TEXT_RIDERS, _HEAD_ORDER, _PACK_LATE,
@@ -97,16 +97,6 @@ def grad_layout(model) -> List[Tuple[str, torch.nn.Parameter]]:
     order += conv("text_embedding_table.")
     assert sorted(order) == sorted(named), "grad layout must cover every parameter exactly once"
     return [(n, named[n]) for n in order]
-
-
-def _hand_over(src, dst=None):
-    """THE hand-over between streams: what is enqueued on `src` so far is visible to `dst`.  dst None: the wait happens later, on the
-    returned event (`dst.wait_event(ev)`) -- work enqueued on `dst` in between overlaps what `src` runs behind the record"""
-    ev = torch.cuda.Event()
-    ev.record(src)
-    if dst is not None:
-        dst.wait_event(ev)
-    return ev
 
 
 class _Step:
@@ -336,7 +326,7 @@ class TrainEngine:
         if st is None:
             yield
             return
-        _hand_over(torch.cuda.current_stream(self.dev), st)
+        hand_over(torch.cuda.current_stream(self.dev), st)
         with self._on(st, "w"):                 # (scratch of its own: the other streams run weight gradients at the same time)
             yield
 
@@ -459,9 +449,9 @@ class TrainEngine:
         # ============================ forward (efficient_tts.py:144-227), activations kept
         with self._on(side):
             tx = self._fwd_text(st)
-            ev_kv = _hand_over(side)
+            ev_kv = hand_over(side)
             du = self._fwd_duration(st, tx)                          # needs V only
-            ev_dur = _hand_over(side)
+            ev_dur = hand_over(side)
         mf = self._fwd_mel(st)
         self._mark("fwd_mel_encoder_done")
         main.wait_event(ev_kv)                                      # K, V from the side stream, behind the mel encoder
@@ -477,12 +467,12 @@ class TrainEngine:
         # ============================ backward
         self._mark("backward_start")
         lb = self._bwd_loss(st, mel, du, al, lo)
-        _hand_over(main, side)                                      # d(dur) is ready
+        hand_over(main, side)                                       # d(dur) is ready
         with self._on(side):
             dV_dur = self._bwd_duration(st, du, tx, lb)
-            ev_durb = _hand_over(side)
+            ev_durb = hand_over(side)
             pa = self._bwd_operand_packs(st, tx, mf, al)
-            ev_packs = _hand_over(side)
+            ev_packs = hand_over(side)
         dH, dH_p = self._bwd_head_decoder(st, lb, dec, wst2, wst if (_WGRAD_STREAM & 1) else None)
         self._mark("bwd_decoder_done")
         if self.bucket_hook and wst is None:
@@ -493,10 +483,10 @@ class TrainEngine:
         if _GV_ON_SIDE and m.side_stream and not torch.cuda.is_current_stream_capturing():
             # nothing between here and dK reads dV: the branch runs on the text-side stream (idle until dK / dV exist, and the consumer of
             # both) beside the chain d alpha' -> ... -> dQ, dK instead of in front of it; a capturing pass keeps it here (see _GV_ON_SIDE)
-            _hand_over(main, side)                                   # dH
+            hand_over(main, side)                                    # dH
             with self._on(side):
                 self._bwd_dv(st, dH, dHt, pa, dV_dur, dv)            # (dV_dur and alpha' as an operand were produced on this stream)
-                ev_gv = _hand_over(side)
+                ev_gv = hand_over(side)
         else:
             main.wait_event(ev_durb)                                 # dV of the duration predictor (and its gradients: bucket 1)
             self._bwd_dv(st, dH, dHt, pa, dV_dur, dv)
@@ -504,7 +494,7 @@ class TrainEngine:
         if ev_gv is not None:
             main.wait_event(ev_gv)                                   # (shared: dV is the residual of the next launch; else: one join for everything behind)
         GK, GK_p = self._bwd_dk(st, ab, pa, dv)
-        ev_gk = _hand_over(main)
+        ev_gk = hand_over(main)
         self._mark("bwd_alignment_done")
         side.wait_event(ev_gk)                                      # dK, dV are ready
         if wst is not None and self.bucket_hook:
@@ -543,11 +533,8 @@ class TrainEngine:
         rs1, rs2 = Rows(B, T1, m.row_gap), Rows(B, T2, m.row_gap)
         gap1, len1 = ws.tensor("gap1", (rs1.rows,)), ws.tensor("len1", (rs1.rows,))
         gap2, len2 = ws.tensor("gap2", (rs2.rows,)), ws.tensor("len2", (rs2.rows,))
-        tl_, ml_ = text_lengths.to(dev), speech_lengths.to(dev)
-        if tl_.dtype == ml_.dtype and tl_.dtype in (torch.int64, torch.int32) and tl_.is_contiguous() and ml_.is_contiguous():
-            tl, ml = O.row_masks_pair(tl_, ml_, rs1, rs2, gap1, len1, gap2, len2)       # both masks + the int32 lengths in one launch
-        else:
-            tl, ml = tl_.to(torch.int32), ml_.to(torch.int32)
+        tl, ml, masks_done = lengths_and_masks(text_lengths, speech_lengths, dev, rs1, rs2, gap1, len1, gap2, len2)
+        if not masks_done:
             O.row_masks(tl, rs1, gap1, len1)
             O.row_masks(ml, rs2, gap2, len2)
         # Dropout(0.1) of the duration predictor is active in train() mode like the reference's
