@@ -20,6 +20,7 @@ import torch
 
 from . import lib as L
 from . import ops as O
+from .dropout import LAUNCH, NONE, DropoutPlan, dist_rank, rank_base
 from .graphs import GraphCache, PadTo
 from .ops import F32Rows, Plane, Rows, roundup
 from .weights import WeightPlanes
@@ -198,9 +199,9 @@ class _Pass:
     rs1 / rs2: text- and mel-length row spaces; gap* / len*: their row masks (0 on the gap rows / beyond each item's length as well);
     tl / ml: int32 lengths on the device; main / side: the streams of the mel-length and the text-length work (main itself without
     side_stream); vt: the V^T plane of an unfused expand, else None; masks_done: gap1 / len1 are already enqueued (else only
-    gap2 / len2 are, and the schedule launches the text masks behind the fork)"""
+    gap2 / len2 are, and the schedule launches the text masks behind the fork); drop: the pass's Dropout masks (dropout.DropoutPlan)"""
     __slots__ = ("ws", "pk", "text", "speech", "B", "T1", "T2", "rs1", "rs2", "gap1", "len1", "gap2", "len2", "tl", "ml", "main", "side",
-                 "vt", "masks_done")
+                 "vt", "masks_done", "drop")
 
     def __init__(self, **fields):
         for k, v in fields.items():
@@ -320,8 +321,8 @@ class EfficientTTSCNN(torch.nn.Module):
         self._len1 = {}
         self._infer_cache = GraphCache(capacity=64)      # free-running inference: two phases per (bucketed) shape
         self.dropout_seed = 0x5EED          # base seed of the train-mode dropout masks (mixed with the data-parallel rank and the step counter)
-        self._drop_now = None               # set while a train()-mode gradient-free forward enqueues its launches: (conv p, k -> seed, duration p, (seed0, seed1))
         self.dropout_calls = 0              # training steps taken so far: the position in the mask sequence (the trainer restores it from the step count on --resume)
+        self._probed_at, self._probe_calls = 0, 0      # gradient-free train()-mode passes since `dropout_calls` was _probed_at (probe_dropout)
         self.planes = WeightPlanes()        # the packed operand planes of the Conv1d / Linear weights
         self._ws: Dict[Tuple, _Workspace] = {}
         self._ws_infer: Dict[Tuple, _Workspace] = {}
@@ -342,9 +343,9 @@ class EfficientTTSCNN(torch.nn.Module):
         self.planes.invalidate()
 
     # ------------------------------------------------------------------ packed weights (weights.py)
-    def _te0_table(self) -> Optional[torch.Tensor]:
+    def _te0_table(self, drop: DropoutPlan = NONE) -> Optional[torch.Tensor]:
         """tap table of text-encoder layer 0 (WeightPlanes.te0_table) where the look-up form applies, else None"""
-        if not self.embed_conv or len(self.text_encoder.layers) == 0 or self.n_channels % 32 or self._drop(0)[0] > 0.0 or self.k_size > 5 or self.act_general:
+        if not self.embed_conv or len(self.text_encoder.layers) == 0 or self.n_channels % 32 or drop.conv_active or self.k_size > 5 or self.act_general:
             return None                      # (a Dropout mask sits between layer 0's activation and its residual add: no look-up form)
         return self.planes.te0_table(self)
 
@@ -356,33 +357,26 @@ class EfficientTTSCNN(torch.nn.Module):
                      x_f, x_p, rs1)
         return x_f, x_p
 
-    # ------------------------------------------------------------------ train-mode Dropout (counter-based masks)
-    def _dropout_base(self) -> int:
-        """the base seed of this process's mask family: the model's seed mixed with the data-parallel rank (the reference's ranks have
-        their own torch RNG streams)"""
-        rank = 0
-        try:
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized():
-                rank = dist.get_rank()
-        except Exception:                                  # noqa: BLE001
-            rank = 0
-        return (int(self.dropout_seed) + 0x9E3779B1 * rank) & 0xFFFFFFFF
+    # ------------------------------------------------------------------ train-mode Dropout (counter-based masks: dropout.py)
+    def _dropout_plan(self, calls: int, step_word_ptr: Optional[int] = None) -> DropoutPlan:
+        """the masks of step `calls`: in train() mode the duration predictor's Dropout(0.1) always (duration_predictor.py:61), the convs' with dropout_rate"""
+        conv_p = float(self.dropout_rate) if self.training and self.dropout_rate >= 1e-5 else 0.0
+        dur_p = float(self.duration_predictor.conv[0][3].p) if self.training else 0.0
+        return DropoutPlan(conv_p, dur_p, rank_base(self.dropout_seed, dist_rank()), calls, step_word_ptr)
 
-    def _dropout_seeds(self, calls: int):
-        """(conv(k) -> seed of the Dropout behind conv / prenet launch k, seed of duration-predictor layer 0, of layer 1) for the
-        `calls`-th train-mode pass of this process: ONE definition for the fused training pass (train.TrainEngine) and the
-        gradient-free train()-mode forward, which therefore draw the same masks at the same counter"""
-        base = self._dropout_base()
+    def step_dropout(self, step_word_ptr: Optional[int] = None) -> DropoutPlan:
+        """a training step: moves the mask sequence on and returns the step's masks (step_word_ptr: see DropoutPlan)"""
+        self.dropout_calls = int(self.dropout_calls) + 1
+        return self._dropout_plan(self.dropout_calls, step_word_ptr)
 
-        def conv(k: int) -> int:
-            return (base * 2654435761 + calls * 1000003 + k * 7919 + 12345) & 0xFFFFFFFF
-        return conv, (base + 2 * calls) & 0xFFFFFFFF, (base + 2 * calls + 1) & 0xFFFFFFFF
-
-    def _drop(self, k: int):
-        """(p, seed) of the Dropout behind conv / prenet launch k in the pass in progress ((0, 0): none)"""
-        st = getattr(self, "_drop_now", None)
-        return (0.0, 0) if st is None or st[0] <= 0.0 else (st[0], st[1](k))
+    def probe_dropout(self) -> DropoutPlan:
+        """A gradient-free pass in train() mode (a probe, a validation pass that forgot eval()) does NOT advance `dropout_calls`: that counter
+        sequences the masks of the optimisation steps (GraphedStep's step words, the trainer's --resume), and a resumed run must reproduce the
+        uninterrupted one.  Probes draw the step that comes next, then the ones behind it; their counter restarts when a real step has moved on"""
+        if self._probed_at != int(self.dropout_calls):
+            self._probed_at, self._probe_calls = int(self.dropout_calls), 0
+        self._probe_calls += 1
+        return self._dropout_plan(self._probed_at + self._probe_calls)
 
     def _side_stream(self, device) -> "torch.cuda.Stream":
         if not self.side_stream:
@@ -436,17 +430,17 @@ class EfficientTTSCNN(torch.nn.Module):
             return L.TILING_SMALLM
         return None
 
-    def _on_resconv(self, rs: Rows) -> bool:
-        if self._drop(0)[0] > 0.0:           # conv Dropout in the pass in progress: efts_gemm's epilogue carries the masks
+    def _on_resconv(self, rs: Rows, drop: DropoutPlan = NONE) -> bool:
+        if drop.conv_active:                 # conv Dropout in this pass: efts_gemm's epilogue carries the masks
             return False
         return self.resconv and rs.rows >= self.RESCONV_MIN_ROWS and self.n_channels % 256 == 0 and self.k_size in (3, 5) and self.act_general is None
 
-    def _stream_in(self, ws, tag, rs: Rows):
+    def _stream_in(self, ws, tag, rs: Rows, drop: DropoutPlan = NONE):
         """Buffers the producer of a residual stack's input writes: (fp32 stream or None, operand plane, lo plane or None).
         A stack on efts_resconv5 reads its residual from the planes, so no fp32 copy is written at all."""
         C = self.n_channels
         pl = ws.plane(f"{tag}_p", rs, C, self.split)
-        if self._on_resconv(rs):
+        if self._on_resconv(rs, drop):
             return None, pl, (ws.plane(f"{tag}_l", rs, C, 1) if self.split == 1 else None)
         return ws.f32(f"{tag}_f", rs, C), pl, None
 
@@ -465,14 +459,14 @@ class EfficientTTSCNN(torch.nn.Module):
         return kw, o_f32, y, y_lo
 
     def _res_stack(self, ws, tag, blk, pk, rs: Rows, x_f32: Optional[F32Rows], x_pl: Plane, gap_ptr, last_split: int,
-                   last_f32: bool, x_lo: Optional[Plane] = None, rider=None, after=None, start: int = 0):
+                   last_f32: bool, x_lo: Optional[Plane] = None, rider=None, after=None, start: int = 0, drop: DropoutPlan = NONE):
         """n x ( x + LeakyReLU(conv1d_k5(x)) ) on the row space (efts_modules.py:48-51,77-79).
         `rider(i)`: optional, returns the efts_resconv5 keyword set of an independent layer of the same geometry that shares
         layer i's persistent launch (or None); `after(i)`: optional, called when layer i's launch has been enqueued; `start`: first
         layer to run (x is then the output of layer start - 1)."""
         n = len(getattr(self, blk).layers)
         C = self.n_channels
-        if self._on_resconv(rs):
+        if self._on_resconv(rs, drop):
             # The stream between the layers is a pair of bf16 planes (hi = the next layer's MFMA operand, lo = the
             # remainder; split 2 planes carry both): 4 B read + 4 B written per element and layer instead of 4 + 6..8 B.
             o_f32 = None
@@ -488,14 +482,13 @@ class EfficientTTSCNN(torch.nn.Module):
                 x_pl, x_lo = y, y_lo
             return o_f32, x_pl
         assert rider is None and after is None
-        kbase = dict(te=10, me=20, dec=30).get(tag, 50)      # launch index of the Dropout masks (same numbering as the fused training pass)
         for i in range(start, n):
             last = i == n - 1
             w = pk[f"{blk}.{i}"]
             o_split = last_split if last else self.split
             o_f32 = ws.f32(f"{tag}_f{i & 1}", rs, C) if (not last or last_f32) else None
             o_pl = ws.plane(f"{tag}_p{i & 1}", rs, C, o_split)
-            dp_, dseed = self._drop(kbase + i)               # efts_modules.py:38-47: Dropout behind the activation, in front of the residual add
+            dp_, dseed = drop.conv(LAUNCH.get(tag, LAUNCH["other"]) + i)      # efts_modules.py:38-47: Dropout behind the activation, in front of the residual add
             if self.act_general is not None:                 # any other torch.nn activation: pre-activation in fp32, then one elementwise launch
                 z = ws.f32(f"{tag}_z", rs, C)
                 O.gemm(a=x_pl, b_ptr=w.ptr, ldb=w.ld, b_tap_stride=w.tap_stride, taps=self.k_size, m=rs.rows, n=C,
@@ -512,12 +505,12 @@ class EfficientTTSCNN(torch.nn.Module):
             x_f32, x_pl = o_f32, o_pl
         return x_f32, x_pl
 
-    def _embed_text(self, ws, pk, text, rs1: Rows, lens: Optional[torch.Tensor], mask: Optional[torch.Tensor]) -> _Embedded:
+    def _embed_text(self, ws, pk, text, rs1: Rows, lens: Optional[torch.Tensor], mask: Optional[torch.Tensor], drop: DropoutPlan = NONE) -> _Embedded:
         """The embedding (efficient_tts.py:144 / :246), or the embedding + text-encoder layer 0 as table look-ups where that form applies.
         lens (int32 [B]) / mask (the row mask `len1`): zero beyond each item's length (the ragged free-running path); both None: padded
         ids are real symbols (the teacher-forced forward)"""
         C = self.n_channels
-        tab = self._te0_table()
+        tab = self._te0_table(drop)
         if tab is not None:
             return _Embedded(*self._embed_te0(ws, pk, text, rs1, lens, tab), 1)
         table = self.text_embedding_table.weight.detach()
@@ -531,11 +524,11 @@ class EfficientTTSCNN(torch.nn.Module):
             O.mask_rows(e_f.ptr, mask.data_ptr(), x_f, x_p, rs1.rows, C)
         return _Embedded(x_f, x_p, 0)
 
-    def _text_stack(self, ws, pk, rs1: Rows, emb: _Embedded, mask_ptr) -> Plane:
+    def _text_stack(self, ws, pk, rs1: Rows, emb: _Embedded, mask_ptr, drop: DropoutPlan = NONE) -> Plane:
         """the text-encoder layers behind `emb` (efficient_tts.py:148 / :250) -> the operand plane of the last one"""
         if emb.start >= len(self.text_encoder.layers):
             return emb.x_p
-        return self._res_stack(ws, "te", "text_encoder", pk, rs1, emb.x_f, emb.x_p, mask_ptr, self.split, False, start=emb.start)[1]
+        return self._res_stack(ws, "te", "text_encoder", pk, rs1, emb.x_f, emb.x_p, mask_ptr, self.split, False, start=emb.start, drop=drop)[1]
 
     def _text_side(self, ws, pk, text, rs1: Rows, gap1, len1, vt: Optional[Plane] = None) -> _TextSide:
         """embed -> text encoder -> key (split-2 plane, masked), value (fp32 + plane, masked)
@@ -567,9 +560,9 @@ class EfficientTTSCNN(torch.nn.Module):
             O.pack_vt(val_f, vt, rs1.B, rs1.T, rs1.Tp, C)
         return val_f, val_p
 
-    def _duration(self, ws, pk, rs1: Rows, val_p: Plane, gap1, out_mask_ptr, mode: int) -> torch.Tensor:
-        """DurationPredictor._forward (duration_predictor.py:66-88); its Dropout(0.1) behind each LayerNorm (:61) is applied when the
-        pass in progress is a train()-mode one (`_drop_now`), else identity."""
+    def _duration(self, ws, pk, rs1: Rows, val_p: Plane, gap1, out_mask_ptr, mode: int, drop: DropoutPlan = NONE) -> torch.Tensor:
+        """DurationPredictor._forward (duration_predictor.py:66-88); its Dropout(0.1) behind each LayerNorm (:61) is applied with the
+        masks of `drop` (a train()-mode pass), else identity."""
         C = self.n_channels
         dp = self.duration_predictor
         h_f = ws.f32("dur_f", rs1, C)
@@ -578,37 +571,35 @@ class EfficientTTSCNN(torch.nn.Module):
             w = pk[f"dur.{i}"]
             O.gemm(a=x_p, b_ptr=w.ptr, ldb=w.ld, b_tap_stride=w.tap_stride, taps=3, m=rs1.rows, n=C, act=L.ACT_RELU,
                    bias=seq[0].bias, out_f32_ptr=h_f.ptr, ldo=C, tiling=self._til(rs1.rows))
-            x_p = self._duration_norm(ws, rs1, i, gap1, out_mask_ptr, mode)
+            x_p = self._duration_norm(ws, rs1, i, gap1, out_mask_ptr, mode, drop)
         return ws.tensor("dur_out", (rs1.rows,))
 
-    def _duration_norm(self, ws, rs1: Rows, i: int, gap1, out_mask_ptr, mode: int) -> Optional[Plane]:
+    def _duration_norm(self, ws, rs1: Rows, i: int, gap1, out_mask_ptr, mode: int, drop: DropoutPlan = NONE) -> Optional[Plane]:
         """LayerNorm behind conv i (duration_predictor.py:58-61): -> the next conv's operand plane, or (last layer) + Linear(C, 1) ->
         the predicted log-durations in ws "dur_out" """
         C = self.n_channels
         dp = self.duration_predictor
         ln = dp.conv[i][2]
         h_f = ws.f32("dur_f", rs1, C)
-        st = getattr(self, "_drop_now", None)
-        dur_p, dur_seed = (0.0, 0) if st is None else (st[2], st[3][min(i, 1)] if i < 2 else (st[3][1] + i) & 0xFFFFFFFF)
         if i + 1 < len(dp.conv):
             x_p = ws.plane(f"dur_p{i}", rs1, C, self.split)
-            O.layernorm_rows(h_f.ptr, ln.weight.detach(), ln.bias.detach(), ln.eps, gap1.data_ptr(), None, x_p, rs1.rows, C, dur_p, dur_seed)
+            O.layernorm_rows(h_f.ptr, ln.weight.detach(), ln.bias.detach(), ln.eps, gap1.data_ptr(), None, x_p, rs1.rows, C, *drop.dur(i))
             return x_p
         O.layernorm_dot(h_f.ptr, ln.weight.detach(), ln.bias.detach(), ln.eps, dp.linear.weight.detach(), dp.linear.bias.detach(),
-                        out_mask_ptr, mode, float(dp.offset), ws.tensor("dur_out", (rs1.rows,)), rs1.rows, C, dur_p, dur_seed)
+                        out_mask_ptr, mode, float(dp.offset), ws.tensor("dur_out", (rs1.rows,)), rs1.rows, C, *drop.dur(i))
         return None
 
     def _fused_expand(self, T1: int) -> bool:
         return self.fuse_expand and T1 <= 256 and self.n_channels % 128 == 0
 
     def _expand_decode(self, ws, pk, B, T1, rs1: Rows, rs2: Rows, val_f: F32Rows, e, tl, ml, ralpha, len2_ptr, gap2,
-                       vt: Optional[Plane] = None, rider=None, after=None, loss_target: Optional[torch.Tensor] = None):
+                       vt: Optional[Plane] = None, rider=None, after=None, loss_target: Optional[torch.Tensor] = None, drop: DropoutPlan = NONE):
         """Gaussian re-alignment from e, bmm(V^T, alpha') -> decoder -> mel head (efficient_tts.py:184-200 / :270-284).
         `ralpha` [B, T1, T2] receives alpha' (the API tensor); tl / ml: int32 lengths or None (no masks, :270-274);
         `vt`: V^T already packed (unfused path only); `loss_target`: the frames of the loss's mel term, which the head's epilogue takes
         where its launch fills the chip.  -> _Head: the mel and the squared-error partials that epilogue left (or None, 0)."""
         C = self.n_channels
-        h_f, h_p, h_l = self._stream_in(ws, "exp", rs2)
+        h_f, h_p, h_l = self._stream_in(ws, "exp", rs2, drop)
         if self._fused_expand(T1):
             # alpha' is the MFMA A operand, produced in registers; V is read as fp32: no alpha'^T plane, no V^T planes
             O.expand(e=e, tl=tl, ml=ml, sigma=float(self.sigma), v=val_f, rs1=rs1, rs2=rs2, alpha_out=ralpha, y_f32=h_f, y=h_p, y_lo=h_l)
@@ -622,7 +613,7 @@ class EfficientTTSCNN(torch.nn.Module):
                    b_batch_stride=C * vt.ld, rowmask_ptr=len2_ptr, rowmask_batch_stride=rs2.Tp,
                    out_f32_ptr=None if h_f is None else h_f.ptr, ldo=C, out_batch_stride=rs2.Tp * C, out_plane=h_p,
                    outb_batch_stride=rs2.Tp * h_p.ld, out_plane_lo=h_l)
-        _, d_p = self._res_stack(ws, "dec", "decoder", pk, rs2, h_f, h_p, gap2.data_ptr(), self.split, False, x_lo=h_l, rider=rider, after=after)
+        _, d_p = self._res_stack(ws, "dec", "decoder", pk, rs2, h_f, h_p, gap2.data_ptr(), self.split, False, x_lo=h_l, rider=rider, after=after, drop=drop)
         # mel head (:198-200), written straight into the [B, T2, odim] tensor the caller gets (one item per batch entry of the
         # launch: no row-space copy of mel_pred, no clone)
         mel = torch.empty(B, rs2.T, self.odim, dtype=torch.float32, device=h_p.buf.device)
@@ -662,7 +653,7 @@ class EfficientTTSCNN(torch.nn.Module):
             # train() mode without gradients (a validation pass that forgot eval(), a probe): the reference applies its Dropouts here --
             # the duration predictor's 0.1 always (duration_predictor.py:61), ResConv1d's and the prenet's when dropout_rate > 0
             # (efts_modules.py:38-47, efficient_tts.py:76-80).  Same counter-based masks as the fused training pass would draw for the
-            # next step (`_forward_impl`: `dropout_calls` itself is left alone); the seeds are by-value launch arguments, so no graph
+            # next step (`probe_dropout`: `dropout_calls` itself is left alone); the seeds are by-value launch arguments, so no graph
             return self._forward_impl(text, text_lengths, speech, speech_lengths)[0]
         if not self.graphs or torch.cuda.is_current_stream_capturing():
             return self._forward_impl(text, text_lengths, speech, speech_lengths)[0]
@@ -684,38 +675,19 @@ class EfficientTTSCNN(torch.nn.Module):
         return out3[0], LazyStats(out3), imv, ralpha, mel_pred, speech
 
     def _forward_impl(self, text, text_lengths, speech, speech_lengths, keep: bool = False):
-        prev = getattr(self, "_drop_now", None)
-        if self.training:
-            # a gradient-free pass in train() mode (a probe, a validation pass that forgot eval()) does NOT advance `dropout_calls`: that counter
-            # sequences the masks of the optimisation steps (GraphedStep's step words, the trainer's --resume), and a resumed run must
-            # reproduce the uninterrupted one whatever was probed in between.  Probes draw the masks of the step that comes next, then of
-            # the ones behind it, from a counter of their own that restarts whenever a real step has moved the sequence on
-            base = int(self.dropout_calls)
-            if getattr(self, "_probe_base", None) != base:
-                object.__setattr__(self, "_probe_base", base)
-                object.__setattr__(self, "_probe_calls", 0)
-            conv, s0, s1 = self._dropout_seeds(base + 1 + self._probe_calls)
-            object.__setattr__(self, "_probe_calls", self._probe_calls + 1)
-            conv_p = float(self.dropout_rate) if self.dropout_rate >= 1e-5 else 0.0
-            object.__setattr__(self, "_drop_now", (conv_p, conv, float(self.duration_predictor.conv[0][3].p), (s0, s1)))
-        else:
-            object.__setattr__(self, "_drop_now", None)
-        try:
-            with O.stream_scope():
-                return self._forward_body(text, text_lengths, speech, speech_lengths, keep)
-        finally:
-            object.__setattr__(self, "_drop_now", prev)
+        with O.stream_scope():
+            return self._forward_body(text, text_lengths, speech, speech_lengths, keep, self.probe_dropout() if self.training else NONE)
 
     # ------------------------------------------------------------------ the schedule of the forward: every stage call, fork, hand-over and join
-    def _forward_body(self, text, text_lengths, speech, speech_lengths, keep: bool = False):
+    def _forward_body(self, text, text_lengths, speech, speech_lengths, keep: bool = False, drop: DropoutPlan = NONE):
         """The whole teacher-forced forward.  Two HIP streams: the text side (masks, embed, 5 convs, K/V) and the duration predictor do
         not depend on the mel side (prenet, 3 convs) and run on `side` beside the mel-length kernels on `main`."""
-        st = self._begin_forward(text, text_lengths, speech, speech_lengths)    # masks on main
+        st = self._begin_forward(text, text_lengths, speech, speech_lengths, drop)      # masks on main
         fr, al = self._to_alignment(st, keep, full=True)
         ralpha = torch.empty(st.B, st.T1, st.T2, dtype=torch.float32, device=st.text.device)
         st.main.wait_event(fr.v_ready)                                          # V from the side stream
         head = self._expand_decode(st.ws, st.pk, st.B, st.T1, st.rs1, st.rs2, fr.val_f, al.e, st.tl, st.ml, ralpha, st.len2.data_ptr(), st.gap2,
-                                   vt=st.vt, loss_target=st.speech)             # :184-200
+                                   vt=st.vt, loss_target=st.speech, drop=st.drop)       # :184-200
         st.main.wait_stream(st.side)                                            # duration predictor done
         out3 = self._losses(st, head, fr.dur, al.lde)                           # :220-227
         # (for inspection only -- tests look whether the head's epilogue took the loss's mel term; nothing reads it back)
@@ -736,7 +708,7 @@ class EfficientTTSCNN(torch.nn.Module):
         """fork, both encoders on their streams, K behind the mel encoder, then the alignment block on main.  full False: without what
         only the decoder and the losses read (_front_merged, _front_split)"""
         st.side.wait_stream(st.main)
-        merged = self._on_resconv(st.rs2) and len(self.text_encoder.layers) >= 1 and len(self.mel_encoder.layers) >= 1
+        merged = self._on_resconv(st.rs2, st.drop) and len(self.text_encoder.layers) >= 1 and len(self.mel_encoder.layers) >= 1
         fr = self._front_merged(st, full) if merged else self._front_split(st, full)
         sidx, alpha = self._soft_index(st, fr.q_p, fr.key_p, keep)
         return fr, self._imv(st, sidx, alpha)
@@ -749,7 +721,7 @@ class EfficientTTSCNN(torch.nn.Module):
         stream.  full False skips the value projection and the duration predictor."""
         main, side = st.main, st.side
         nt, nm = len(self.text_encoder.layers), len(self.mel_encoder.layers)
-        first = 0 if self._te0_table() is None else 1                          # (layer 0 may be table look-ups: it never rides)
+        first = 0 if self._te0_table(st.drop) is None else 1                   # (layer 0 may be table look-ups: it never rides)
         nr = min(nt - first, nm)
         ns = nt - nr                                                           # text layers that run by themselves first
         # The first text layers and the prenet share the chip by halves: both kinds of workgroup take a whole CU (LDS), the
@@ -763,7 +735,7 @@ class EfficientTTSCNN(torch.nn.Module):
         te_plan = O.resconv5_plan_buf(st.rs1.rows, self.n_channels, cus // 2 - 2) if share else None      # (a host-side table: no launch)
         if not st.masks_done:
             O.row_masks(st.tl, st.rs1, st.gap1, st.len1)                       # :137 (behind the fork, on main: beside the prenet)
-        cur = _TextCursor(self, st, self._embed_text(st.ws, st.pk, st.text, st.rs1, None, None), ride_from=nm - nr)    # :144
+        cur = _TextCursor(self, st, self._embed_text(st.ws, st.pk, st.text, st.rs1, None, None, st.drop), ride_from=nm - nr)    # :144
         self._text_layers_alone(cur, ns, te_plan)                              # :148
         main.wait_event(pre_ready)
         q_p = self._mel_stack(st, pre, rider=cur.ride)
@@ -777,7 +749,7 @@ class EfficientTTSCNN(torch.nn.Module):
             with O.on_stream(side):
                 val_f, val_p = self._value_proj(st.ws, st.pk, st.rs1, cur.x_p, st.gap1, st.len1, st.vt)      # :150-157
                 v_ready = O.hand_over(side)
-                dur = self._duration(st.ws, st.pk, st.rs1, val_p, st.gap1, st.len1.data_ptr(), 0)            # :219
+                dur = self._duration(st.ws, st.pk, st.rs1, val_p, st.gap1, st.len1.data_ptr(), 0, st.drop)   # :219
         return _Front(q_p, key_p, val_f, dur, v_ready)
 
     def _front_split(self, st: _Pass, full: bool) -> _Front:
@@ -787,18 +759,18 @@ class EfficientTTSCNN(torch.nn.Module):
         with O.on_stream(side):
             if not st.masks_done:
                 O.row_masks(st.tl, rs1, gap1, len1)                            # :137 (behind the fork, on side)
-            h_p = self._text_stack(ws, pk, rs1, self._embed_text(ws, pk, st.text, rs1, None, None), gap1.data_ptr())    # :144-148
+            h_p = self._text_stack(ws, pk, rs1, self._embed_text(ws, pk, st.text, rs1, None, None, st.drop), gap1.data_ptr(), st.drop)    # :144-148
             key_p = self._key_proj(ws, pk, rs1, h_p, gap1, len1)               # :149, :155-156
             k_ready = O.hand_over(side)
             val_f, val_p = self._value_proj(ws, pk, rs1, h_p, gap1, len1, st.vt)      # :150-157
             v_ready = O.hand_over(side)
-            dur = self._duration(ws, pk, rs1, val_p, gap1, len1.data_ptr(), 0) if full else None     # :219
+            dur = self._duration(ws, pk, rs1, val_p, gap1, len1.data_ptr(), 0, st.drop) if full else None     # :219
         q_p = self._mel_stack(st, self._prenet(st))
         st.main.wait_event(k_ready)
         return _Front(q_p, key_p, val_f, dur, v_ready)
 
     # ------------------------------------------------------------------ the stages of the forward (launches on the current stream; no fork, no join)
-    def _begin_forward(self, text, text_lengths, speech, speech_lengths) -> _Pass:
+    def _begin_forward(self, text, text_lengths, speech, speech_lengths, drop: DropoutPlan = NONE) -> _Pass:
         """workspace, row spaces, streams and the masks that go in front of the fork: both row spaces' in one launch, else (lengths of
         two dtypes) the mel mask only -- the prenet on the side stream reads gap2"""
         dev = text.device
@@ -816,14 +788,14 @@ class EfficientTTSCNN(torch.nn.Module):
             O.row_masks(ml, rs2, gap2, len2)                                   # :139
         vt = None if self._fused_expand(T1) else ws.raw_plane("vt", B * self.n_channels, T1, self.align_split)
         return _Pass(ws=ws, pk=pk, text=text, speech=speech, B=B, T1=T1, T2=T2, rs1=rs1, rs2=rs2, gap1=gap1, len1=len1, gap2=gap2, len2=len2,
-                     tl=tl, ml=ml, main=torch.cuda.current_stream(dev), side=self._side_stream(dev), vt=vt, masks_done=masks_done)
+                     tl=tl, ml=ml, main=torch.cuda.current_stream(dev), side=self._side_stream(dev), vt=vt, masks_done=masks_done, drop=drop)
 
     def _prenet(self, st: _Pass, max_wgs: int = 0) -> _Prenet:
         """mel_prenet (:161) -> the mel encoder's input buffers.  max_wgs: cap of the fused launch's grid (0: none)"""
         ws, pk, rs2, speech, gap2, C = st.ws, st.pk, st.rs2, st.speech, st.gap2, self.n_channels
-        pre_f, pre_p, pre_l = self._stream_in(ws, "pre", rs2)
+        pre_f, pre_p, pre_l = self._stream_in(ws, "pre", rs2, st.drop)
         wp = pk["prenet"]
-        pre_dp, pre_seed = self._drop(40)                                      # mel_prenet's Dropout (:76-80)
+        pre_dp, pre_seed = st.drop.conv(LAUNCH["prenet"])                      # mel_prenet's Dropout (:76-80)
         if self.act_general is not None:
             mel_in = ws.plane("mel_in", rs2, self.odim, self.split)
             O.pack_rows(speech, None, mel_in, rs2)
@@ -847,8 +819,8 @@ class EfficientTTSCNN(torch.nn.Module):
         ws, pk, rs2, C = st.ws, st.pk, st.rs2, self.n_channels
         gap_ptr = st.gap2.data_ptr()
         if self.mel_query_fc is None:
-            return self._res_stack(ws, "me", "mel_encoder", pk, rs2, pre.pre_f, pre.pre_p, gap_ptr, self.align_split, False, x_lo=pre.pre_l, rider=rider)[1]
-        _, mh_p = self._res_stack(ws, "me", "mel_encoder", pk, rs2, pre.pre_f, pre.pre_p, gap_ptr, self.split, False, x_lo=pre.pre_l, rider=rider)
+            return self._res_stack(ws, "me", "mel_encoder", pk, rs2, pre.pre_f, pre.pre_p, gap_ptr, self.align_split, False, x_lo=pre.pre_l, rider=rider, drop=st.drop)[1]
+        _, mh_p = self._res_stack(ws, "me", "mel_encoder", pk, rs2, pre.pre_f, pre.pre_p, gap_ptr, self.split, False, x_lo=pre.pre_l, rider=rider, drop=st.drop)
         q_p = ws.plane("q_p", rs2, C, self.align_split)
         wq = pk["qfc"]
         O.gemm(a=mh_p, b_ptr=wq.ptr, ldb=wq.ld, m=rs2.rows, n=C, bias=self.mel_query_fc.bias, rowmask_ptr=gap_ptr, out_plane=q_p)
@@ -1181,25 +1153,20 @@ class EfficientTTSCNN(torch.nn.Module):
         `inference(text, durations=align(...)["durations"])` re-synthesises with the recorded timing."""
         self._require(text)
         B, T1 = text.shape
-        prev = getattr(self, "_drop_now", None)
-        object.__setattr__(self, "_drop_now", None)
-        try:
-            with O.stream_scope():
-                st, al = self._align_body(text, text_lengths, speech, speech_lengths)
-                imv, tl, ml = al.imv, st.tl, st.ml
-                e = al.e.clone()                               # (the workspace's buffer: the next forward() overwrites it)
-                valid = torch.arange(T1, device=e.device)[None, :] < tl.to(torch.int64)[:, None]
-                if self.delta_e_method_1:                      # :204  delta_e_i = e_i - e_{i-1}, e_{-1} = 0
-                    dur = torch.diff(e, dim=1, prepend=torch.zeros(B, 1, device=e.device))
-                else:                                          # :205-213  delta_e_i = e_{i+1} - e_i with e_{len} = mel length
-                    ee = torch.cat([e, torch.zeros(B, 1, device=e.device)], dim=1)
-                    ee.scatter_(1, tl.to(torch.int64)[:, None], ml.to(torch.float32)[:, None])
-                    dur = ee[:, 1:] - ee[:, :-1]
-                dur = torch.where(valid, dur, torch.zeros((), device=e.device))
-                frames = torch.empty(B, T1, dtype=torch.int32, device=e.device)
-                O.duration_control(dur, T1, tl, None, None, None, True, torch.empty_like(e), torch.empty_like(tl), frames, B, T1)
-        finally:
-            object.__setattr__(self, "_drop_now", prev)
+        with O.stream_scope():
+            st, al = self._align_body(text, text_lengths, speech, speech_lengths)
+            imv, tl, ml = al.imv, st.tl, st.ml
+            e = al.e.clone()                               # (the workspace's buffer: the next forward() overwrites it)
+            valid = torch.arange(T1, device=e.device)[None, :] < tl.to(torch.int64)[:, None]
+            if self.delta_e_method_1:                      # :204  delta_e_i = e_i - e_{i-1}, e_{-1} = 0
+                dur = torch.diff(e, dim=1, prepend=torch.zeros(B, 1, device=e.device))
+            else:                                          # :205-213  delta_e_i = e_{i+1} - e_i with e_{len} = mel length
+                ee = torch.cat([e, torch.zeros(B, 1, device=e.device)], dim=1)
+                ee.scatter_(1, tl.to(torch.int64)[:, None], ml.to(torch.float32)[:, None])
+                dur = ee[:, 1:] - ee[:, :-1]
+            dur = torch.where(valid, dur, torch.zeros((), device=e.device))
+            frames = torch.empty(B, T1, dtype=torch.int32, device=e.device)
+            O.duration_control(dur, T1, tl, None, None, None, True, torch.empty_like(e), torch.empty_like(tl), frames, B, T1)
         return dict(e=e, durations=dur, frames=frames.to(torch.int64), imv=imv)
 
 

@@ -5,7 +5,7 @@ Why: the step is ~190 launches.  Issued eagerly the host needs 1.9 ms for them o
 4.5-5.7 ms on a loaded host (observed on the measurement pool), where the HOST then sets the step time.  A replay costs the host a
 few tens of microseconds.  What changes from step to step lives in device memory, refreshed by one tiny stream-ordered launch in
 front of every replay (efts_store_words): the learning rate and Adam's two bias corrections (efts_adam_amsgrad_dev; words 0-2), the step
-word of the duration predictor's Dropout seeds (`drop_seed_add` of efts_layernorm_rows / _dot / _bwd; word 3), and the four words of
+word of the duration predictor's Dropout seeds (dropout.DropoutPlan.step_word, the `drop_seed_add` of efts_layernorm_rows / _dot / _bwd; word 3), and the four words of
 the other fused optimizers (efts_optim_step `hyper`: Adam without amsgrad, AdamW, RAdam; words 4-7, 16-byte aligned).  Parameters, optimizer
 state and every result are bit-identical to the eager loop's (tests/test_gpu_train.py).
 
@@ -27,6 +27,7 @@ import torch
 from . import ops as O
 from . import train as T
 from .autograd import engine_of
+from .dropout import DropoutPlan
 from .model import LazyStats
 from .optim import FlatOptimizer
 
@@ -78,7 +79,7 @@ class GraphedStep:
         m = self.model
         words, hw, w0 = [0] * 8, self.opt.hyper_words(self.opt.t + 1), self.opt.hyper_word0
         words[w0:w0 + len(hw)] = hw
-        words[3] = 2 * (int(getattr(m, "dropout_calls", 0)) + 1)
+        words[3] = DropoutPlan.step_word(int(m.dropout_calls) + 1)
         O.store_words(self.words, words)
 
     def __call__(self, text, text_lengths, speech, speech_lengths):
@@ -111,7 +112,7 @@ class GraphedStep:
                 # replay holds no conversion launches of its own)
                 ent["static"] = [text.clone(), text_lengths.to(device=dev, dtype=torch.int32).clone(), speech.clone(),
                                  speech_lengths.to(device=dev, dtype=torch.int32).clone()]
-                calls0 = int(getattr(m, "dropout_calls", 0))
+                calls0 = int(m.dropout_calls)
                 m.planes.invalidate()                                 # the weight planes are (re)packed INSIDE the graph, every step
                 g = torch.cuda.CUDAGraph()
                 torch.cuda.synchronize()
@@ -152,7 +153,7 @@ class GraphedStep:
         ent["graph"].replay()
         self.replays += 1
         # what the eager loop's Python does around its launches
-        m.dropout_calls = int(getattr(m, "dropout_calls", 0)) + 1
+        m.dropout_calls = int(m.dropout_calls) + 1
         self.opt.t += 1
         m.planes.invalidate()
         for n, p in eng.named:

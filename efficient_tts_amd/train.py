@@ -16,6 +16,7 @@ import torch
 
 from . import lib as L
 from . import ops as O
+from .dropout import LAUNCH, DropoutPlan
 from .ops import F32Rows, PackedWeight, Plane, Rows, hand_over
 from .model import lengths_and_masks, require_trainable
 
@@ -104,10 +105,9 @@ class _Step:
     gap* / len*: their row masks (0 on the gap rows / beyond each item's length as well); tl / ml: int32 lengths on the device;
     pk: packed forward planes by layer name (set by the repack); main / side / wst: the streams of the mel-length work, the
     text-length work (main itself without model.side_stream) and the mel-length weight gradients (None without _WGRAD_STREAM);
-    drop_p, seed0, seed1, sadd: the duration predictor's Dropout -- p, the seeds of its two layers, and the address of the device
-    word added to both in a captured step (else None)"""
+    drop: the step's Dropout masks (dropout.DropoutPlan: one mask per launch and step, regenerated by the backward from the same seed)"""
     __slots__ = ("ws", "text", "speech", "gscale", "B", "T1", "T2", "rs1", "rs2", "gap1", "len1", "gap2", "len2", "tl", "ml", "pk",
-                 "main", "side", "wst", "drop_p", "seed0", "seed1", "sadd")
+                 "main", "side", "wst", "drop")
 
     def __init__(self, **fields):
         self.pk = None
@@ -194,18 +194,6 @@ class TrainEngine:
         return m.planes.schedule(m, self.folded, self.wt, self.step_params, self._pack_phase)
 
     # ------------------------------------------------------------------ small wrappers
-    def _conv_drop(self, k: int):
-        """(p, seed) of the train-mode Dropout behind the activation of conv / prenet launch k (efts_modules.py:38-47,
-        efficient_tts.py:76-80): one mask per launch and step, regenerated by the backward from the same seed"""
-        m = self.m
-        if not m.training or m.dropout_rate < 1e-5:
-            return 0.0, 0
-        return float(m.dropout_rate), m._dropout_seeds(self.drop_calls)[0](k)
-
-    def _seed_base(self) -> int:
-        """the model's base seed mixed with the data-parallel rank"""
-        return self.m._dropout_base()
-
     def _wgrad_any(self, ws, dz_f_ptr, dz_p: Optional[Plane], x_f_ptr, x_p: Optional[Plane], cout, cin, taps, rows, out_dw, defer: Optional[list] = None):
         """un-normed weights: the direct kernel when both operand planes exist in one format and the shape fits its tiles.
         defer: a list that collects the direct items of equally shaped layers for ONE grouped launch (the caller passes it to
@@ -273,11 +261,11 @@ class TrainEngine:
         return True
 
     # ------------------------------------------------------------------ forward with saved activations
-    def _stack_fwd(self, ws, tag, blk, pk, rs, x_f, x_p, gap_ptr, last_split):
+    def _stack_fwd(self, ws, tag, blk, pk, rs, x_f, x_p, gap_ptr, last_split, drop: DropoutPlan):
         m, C = self.m, self.m.n_channels
         saved = []
         layers = getattr(m, blk).layers
-        if (_RESCONV_FWD & dict(dec=1, me=2, te=0)[tag]) and m._on_resconv(rs) and self._conv_drop(0)[0] == 0.0 and _WGRAD_TN_SPLITS > 0 and C % 128 == 0:
+        if (_RESCONV_FWD & dict(dec=1, me=2, te=0)[tag]) and m._on_resconv(rs, drop) and _WGRAD_TN_SPLITS > 0 and C % 128 == 0:
             # mel-length stack on efts_resconv5 (the inference kernel): the stream between the layers is hi + lo bf16 planes (every
             # hi plane is kept: it is the layer's operand in the wgrad), the activation's sign leaves the epilogue as bit rows
             # (efts_act_bwd mode 5); fp32 only into the first layer (the producer's stream) and out of the last one
@@ -301,7 +289,7 @@ class TrainEngine:
             w = pk[f"{blk}.{i}"]
             o_f = ws.f32(f"T{tag}_f{i}", rs, C)
             o_p = ws.plane(f"T{tag}_p{i}", rs, C, last_split if last else m.split)
-            dp, dseed = self._conv_drop(dict(te=10, me=20, dec=30)[tag] + i)
+            dp, dseed = drop.conv(LAUNCH[tag] + i)
             if m.act_general is not None:
                 # a torch.nn activation outside the contraction epilogues (csrc/efts_act.hip): the pre-activation is kept in fp32 for f'(z)
                 z = ws.f32(f"T{tag}_z{i}", rs, C)
@@ -537,33 +525,18 @@ class TrainEngine:
         if not masks_done:
             O.row_masks(tl, rs1, gap1, len1)
             O.row_masks(ml, rs2, gap2, len2)
-        # Dropout(0.1) of the duration predictor is active in train() mode like the reference's
-        # (duration_predictor.py:61; the model never forwards its own dropout_rate to it)
-        drop_p = float(m.duration_predictor.conv[0][3].p) if m.training else 0.0
-        # one mask family per (base seed, data-parallel rank, step counter): replicas draw different masks (the reference's ranks
-        # have their own torch RNG streams); the trainer sets the counter to the step count when it loads a checkpoint, so that
-        # --resume continues the sequence instead of replaying it
-        m.dropout_calls = int(getattr(m, "dropout_calls", 0)) + 1
-        self.drop_calls = m.dropout_calls
-        self.seed_base = self._seed_base()
-        if self.step_words is not None:
-            # a step that is being captured (step_graph.GraphedStep): the counter's contribution comes from device word 3 of
-            # `step_words` (= 2 * dropout_calls, refreshed in front of every replay), the by-value seeds stay constant
-            sadd = self.step_words.data_ptr() + 12
-            seed0, seed1 = self.seed_base & 0xFFFFFFFF, (self.seed_base + 1) & 0xFFFFFFFF
-        else:
-            sadd = None
-            seed0, seed1 = (self.seed_base + 2 * self.drop_calls) & 0xFFFFFFFF, (self.seed_base + 2 * self.drop_calls + 1) & 0xFFFFFFFF
+        # the next step of the mask sequence; one that is being captured (step_graph.GraphedStep) adds device word 3 of `step_words` to its duration seeds
+        drop = m.step_dropout(None if self.step_words is None else self.step_words.data_ptr() + 12)
         return _Step(ws=ws, text=text, speech=speech, gscale=gscale, B=B, T1=T1, T2=T2, rs1=rs1, rs2=rs2,
                      gap1=gap1, len1=len1, gap2=gap2, len2=len2, tl=tl, ml=ml, main=torch.cuda.current_stream(dev), side=m._side_stream(dev),
-                     wst=m._aux_stream(dev) if (_WGRAD_STREAM and m.side_stream) else None, drop_p=drop_p, seed0=seed0, seed1=seed1, sadd=sadd)
+                     wst=m._aux_stream(dev) if (_WGRAD_STREAM and m.side_stream) else None, drop=drop)
 
     def _fwd_text(self, st: _Step) -> _TextFwd:
         """embedding, text encoder, key / value Linears"""
         m, ws, rs1, C, split = self.m, st.ws, st.rs1, self.m.n_channels, self.m.split
         emb_f, emb_p = ws.f32("Temb_f", rs1, C), ws.plane("Temb_p", rs1, C, split)
         O.embed(st.text, m.text_embedding_table.weight.detach(), emb_f, emb_p, rs1)
-        te_f, te_p, te_saved = self._stack_fwd(ws, "te", "text_encoder", st.pk, rs1, emb_f, emb_p, st.gap1.data_ptr(), split)
+        te_f, te_p, te_saved = self._stack_fwd(ws, "te", "text_encoder", st.pk, rs1, emb_f, emb_p, st.gap1.data_ptr(), split, st.drop)
         key_f, key_p = ws.f32("Tkey_f", rs1, C), ws.plane("Tkey_p", rs1, C, 2)
         val_f, val_p = ws.f32("Tval_f", rs1, C), ws.plane("Tval_p", rs1, C, split)
         shared = m.share_text_encoder_key_value                 # efficient_tts.py:150-153: the value is the key projection
@@ -586,11 +559,11 @@ class TrainEngine:
         O.gemm(a=tx.val_p, b_ptr=w0.ptr, ldb=w0.ld, b_tap_stride=w0.tap_stride, taps=3, m=rs1.rows, n=C, act=L.ACT_RELU,
                bias=dp.conv[0][0].bias, out_f32_ptr=h1_f.ptr, ldo=C)
         O.layernorm_rows(h1_f.ptr, ln0.weight.detach(), ln0.bias.detach(), ln0.eps, st.gap1.data_ptr(), l1_f.ptr, l1_p, rs1.rows, C,
-                         st.drop_p, st.seed0, st.sadd)
+                         *st.drop.dur(0))
         O.gemm(a=l1_p, b_ptr=w1.ptr, ldb=w1.ld, b_tap_stride=w1.tap_stride, taps=3, m=rs1.rows, n=C, act=L.ACT_RELU,
                bias=dp.conv[1][0].bias, out_f32_ptr=h2_f.ptr, ldo=C)
         O.layernorm_dot(h2_f.ptr, ln1.weight.detach(), ln1.bias.detach(), ln1.eps, dp.linear.weight.detach(),
-                        dp.linear.bias.detach(), st.len1.data_ptr(), 0, float(dp.offset), dur, rs1.rows, C, st.drop_p, st.seed1, st.sadd)
+                        dp.linear.bias.detach(), st.len1.data_ptr(), 0, float(dp.offset), dur, rs1.rows, C, *st.drop.dur(1))
         return _DurFwd(h1_f, l1_f, l1_p, h2_f, dur)
 
     def _fwd_mel(self, st: _Step) -> _MelFwd:
@@ -601,7 +574,7 @@ class TrainEngine:
         O.pack_rows(st.speech, mel_in_f, mel_in, rs2)               # (the backward's wgrad of the prenet reads both)
         pre_f, pre_p = ws.f32("Tpre_f", rs2, C), ws.plane("Tpre_p", rs2, C, split)
         wp = st.pk["prenet"]
-        pre_dp, pre_seed = self._conv_drop(40)                       # mel_prenet's Dropout (efficient_tts.py:76-80)
+        pre_dp, pre_seed = st.drop.conv(LAUNCH["prenet"])            # mel_prenet's Dropout (efficient_tts.py:76-80)
         pre_z = None
         if m.act_general is not None:
             pre_z = ws.f32("Tpre_z", rs2, C)
@@ -616,9 +589,9 @@ class TrainEngine:
                    rowmask_ptr=gap2, out_f32_ptr=pre_f.ptr, ldo=C, out_plane=pre_p, drop_p=pre_dp, drop_seed=pre_seed)
         if m.mel_query_fc is None:
             mh_f = mh_p = None
-            q_f, q_p, me_saved = self._stack_fwd(ws, "me", "mel_encoder", st.pk, rs2, pre_f, pre_p, gap2, 2)
+            q_f, q_p, me_saved = self._stack_fwd(ws, "me", "mel_encoder", st.pk, rs2, pre_f, pre_p, gap2, 2, st.drop)
         else:                                                       # efficient_tts.py:163-164: Linear(C, C) in front of the attention
-            mh_f, mh_p, me_saved = self._stack_fwd(ws, "me", "mel_encoder", st.pk, rs2, pre_f, pre_p, gap2, split)
+            mh_f, mh_p, me_saved = self._stack_fwd(ws, "me", "mel_encoder", st.pk, rs2, pre_f, pre_p, gap2, split, st.drop)
             q_f, q_p = ws.f32("Tq_f", rs2, C), ws.plane("Tq_p", rs2, C, 2)
             wq = st.pk["qfc"]
             O.gemm(a=mh_p, b_ptr=wq.ptr, ldb=wq.ld, m=rs2.rows, n=C, bias=m.mel_query_fc.bias, rowmask_ptr=gap2,
@@ -663,7 +636,7 @@ class TrainEngine:
             O.gemm(a=al.ra_p, b_ptr=vt.ptr, ldb=vt.ld, m=T2, n=C, batch=B, a_batch_stride=rs2.Tp * al.ra_p.ld, b_batch_stride=C * vt.ld,
                    rowmask_ptr=st.len2.data_ptr(), rowmask_batch_stride=rs2.Tp, out_f32_ptr=h_f.ptr, ldo=C, out_batch_stride=rs2.Tp * C,
                    out_plane=h_p, outb_batch_stride=rs2.Tp * h_p.ld)
-        return _DecFwd(*self._stack_fwd(ws, "dec", "decoder", st.pk, rs2, h_f, h_p, st.gap2.data_ptr(), m.split))
+        return _DecFwd(*self._stack_fwd(ws, "dec", "decoder", st.pk, rs2, h_f, h_p, st.gap2.data_ptr(), m.split, st.drop))
 
     def _fwd_head(self, st: _Step, dec: _DecFwd) -> F32Rows:
         m, rs2 = self.m, st.rs2
@@ -702,7 +675,7 @@ class TrainEngine:
         dz2_f, dz2_p = ws.f32("Bdur_dz2", rs1, C), ws.plane("Bdur_dz2p", rs1, C, split)
         O.layernorm_bwd(du.h2_f.ptr, ln1.weight, ln1.bias, ln1.eps, None, lb.ddur, dp.linear.weight, None, dz2_f.ptr, dz2_p,
                         gname(1, "2.weight"), gname(1, "2.bias"), gname(1, "0.bias"), g["duration_predictor.linear.weight"],
-                        g["duration_predictor.linear.bias"], rs1.rows, C, st.drop_p, st.seed1, st.sadd)
+                        g["duration_predictor.linear.bias"], rs1.rows, C, *st.drop.dur(1))
         dur_items = []                                           # both k3 weight gradients in one grouped launch, below
         self._wgrad_any(ws, dz2_f.ptr, dz2_p, du.l1_f.ptr, du.l1_p, C, C, 3, rs1.rows, gname(1, "0.weight"), defer=dur_items)
         G1 = ws.f32("Bdur_G1", rs1, C)
@@ -710,7 +683,7 @@ class TrainEngine:
         O.gemm(a=dz2_p, b_ptr=wt.ptr, ldb=wt.ld, b_tap_stride=wt.tap_stride, taps=3, m=rs1.rows, n=C, out_f32_ptr=G1.ptr, ldo=C)
         dz1_f, dz1_p = ws.f32("Bdur_dz1", rs1, C), ws.plane("Bdur_dz1p", rs1, C, split)
         O.layernorm_bwd(du.h1_f.ptr, ln0.weight, ln0.bias, ln0.eps, G1.ptr, None, None, st.gap1.data_ptr(), dz1_f.ptr, dz1_p,
-                        gname(0, "2.weight"), gname(0, "2.bias"), gname(0, "0.bias"), None, None, rs1.rows, C, st.drop_p, st.seed0, st.sadd)
+                        gname(0, "2.weight"), gname(0, "2.bias"), gname(0, "0.bias"), None, None, rs1.rows, C, *st.drop.dur(0))
         self._wgrad_any(ws, dz1_f.ptr, dz1_p, tx.val_f.ptr, tx.val_p, C, C, 3, rs1.rows, gname(0, "0.weight"), defer=dur_items)
         if dur_items:
             self._wgrad_group(ws, dur_items, C, C, rs1.rows, 3, split)

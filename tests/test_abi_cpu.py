@@ -105,10 +105,18 @@ def test_train_mode_forward_without_gradients_reaches_the_device_path():
             with torch.no_grad(), pytest.raises(Exception) as ei:
                 m(t, torch.tensor([8]), torch.zeros(1, 16, 80), torch.tensor([16]))
             assert not isinstance(ei.value, NotImplementedError)
-    conv, s0, s1 = m._dropout_seeds(7)
-    conv2, t0, t1 = m._dropout_seeds(8)
-    assert conv(30) != conv(31) and conv(30) != conv2(30) and (s0, s1) != (t0, t1) and s1 == (s0 + 1) & 0xFFFFFFFF
-    assert m._drop(30) == (0.0, 0)                                       # no pass in progress: no masks
+    import inspect
+    from efficient_tts_amd import dropout as D
+    m.train()
+    m.dropout_calls = 6
+    p7, p8 = m.step_dropout(), m.step_dropout()                          # the plans of steps 7 and 8 (dropout.DropoutPlan)
+    (s0, s1), (t0, t1) = [(p.dur(0)[1], p.dur(1)[1]) for p in (p7, p8)]
+    assert (p7.calls, p8.calls, m.dropout_calls) == (7, 8, 8) and p7.conv_active and p7.conv(30)[0] == p7.conv_p == 0.1
+    assert p7.conv(30) != p7.conv(31) and p7.conv(30) != p8.conv(30) and (s0, s1) != (t0, t1) and s1 == (s0 + 1) & 0xFFFFFFFF
+    # no train-mode pass: every helper that takes a plan defaults to NONE, which has no masks
+    for f in (m._on_resconv, m._stream_in, m._te0_table, m._embed_text, m._res_stack, m._duration, m._duration_norm, m._begin_forward):
+        assert inspect.signature(f).parameters["drop"].default is D.NONE
+    assert D.NONE.conv(30) == (0.0, 0) and not D.NONE.conv_active and D.NONE.dur(1) == (0.0, 0, None)
 
 
 def test_lazy_stats_behaves_like_a_dict():
