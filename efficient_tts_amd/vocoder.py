@@ -17,10 +17,14 @@ Every Conv1d / ConvTranspose1d is one `efts_gemm` launch on channel-last rows (o
   * the multi-receptive-field mean and the LeakyReLU of the next layer's input: `efts_mean_act_rows`;
   * conv_post + tanh: the kernel's tanh epilogue.
 Batches: the B utterances share one row space per stage, item b at rows b * P .. b * P + T_b * up with a pitch of
-P = (T + 4) * up rows (the 4 spare mel frames become >= 32 zero rows from the first stage on: more than the largest
-halo, (11 - 1) / 2 * 5 = 25).  Every launch carries the per-row validity mask of its stage, so rows past an item's own
+P = (T + gap) * up rows.  `gap` spare mel frames (`gap_frames`) come from the configuration: at the first upsampled
+stage they are gap * upsample_rates[0] zero rows, and that must be no less than the largest halo of a residual
+convolution, max (k - 1) / 2 * d; never fewer than 4 frames, which cover conv_pre (3 rows at mel rate) and the extra
+input row of the transposed convolutions.  V1: max(4, ceil(25 / 8)) = 4 frames, 32 rows against a halo of
+(11 - 1) / 2 * 5 = 25.  Every launch carries the per-row validity mask of its stage, so rows past an item's own
 length stay zero exactly as the zero padding of a single-utterance run does; `forward(mel, lengths)` therefore equals
 B separate calls on the unpadded items.
+Configurations the launches below cannot compute are refused in the constructor (`_refusal`), never at a launch.
 There is no CPU path.
 """
 from __future__ import annotations
@@ -38,11 +42,50 @@ from .ops import PackedWeight, Plane
 
 LRELU_SLOPE = 0.1
 _GUARD = 64            # zero rows in front of every row space: (taps - 1) / 2 * dilation <= 25
-_GAP_FRAMES = 4        # spare mel frames between the items of a batch: >= 32 zero rows at every upsampled stage
+_MIN_GAP_FRAMES = 4    # spare mel frames between the items of a batch, at least: conv_pre's halo (3) and the transposed convolutions' extra row
+_MAX_RES_KERNELS = 3   # efts_mean_act_rows adds up to three streams
+_GEMM_TAPS = (1, 3, 5, 7, 9, 11)       # what efts_gemm takes as `taps`
+_GEMM_MAX_SPAN = 64    # efts_gemm: (taps - 1) * dilation rows of window at the most
 
 
 def _cfg(h, key, default=None):
     return h[key] if isinstance(h, dict) and key in h else getattr(h, key, default)
+
+
+def gap_frames(upsample_rates, res_kernels, res_dilations) -> int:
+    """spare mel frames between the items of a batch: their rows at the first upsampled stage hold the largest halo of a
+    residual convolution (the later stages only have more rows per frame)"""
+    halo = max((k - 1) // 2 * d for k, ds in zip(res_kernels, res_dilations) for d in ds)
+    return max(_MIN_GAP_FRAMES, -(-halo // upsample_rates[0]))
+
+
+def _refusal(rates, kernels, res_kernels, res_dilations, c0, num_mels) -> Optional[str]:
+    """why the launches of `_run` cannot compute this configuration (None: they can)"""
+    if not rates or len(rates) != len(kernels):
+        return "upsample_rates and upsample_kernel_sizes must be non-empty lists of one length"
+    for u, k in zip(rates, kernels):
+        if u <= 0 or k != 2 * u or u % 2:
+            return "transposed convolutions are implemented for kernel = 2 * stride, even stride"
+    if not 1 <= len(res_kernels) <= _MAX_RES_KERNELS:
+        return (f"{len(res_kernels)} resblock_kernel_sizes: the multi-receptive-field mean (efts_mean_act_rows) adds one to "
+                f"{_MAX_RES_KERNELS} residual chains")
+    if len(res_dilations) != len(res_kernels):
+        return "resblock_dilation_sizes must hold one list per entry of resblock_kernel_sizes"
+    for k, ds in zip(res_kernels, res_dilations):
+        if k not in _GEMM_TAPS:
+            return f"residual kernel size {k}: efts_gemm takes {', '.join(map(str, _GEMM_TAPS))} taps"
+        if not ds:
+            return "an empty dilation list (a residual block without convolutions) is not implemented"
+        for d in ds:
+            if d < 1 or (k - 1) * d > _GEMM_MAX_SPAN:
+                return f"residual kernel size {k} with dilation {d}: efts_gemm takes (k - 1) * d <= {_GEMM_MAX_SPAN} rows, d >= 1"
+    c_last = c0 // 2 ** len(rates)
+    if c0 <= 0 or c0 % 2 ** len(rates) or c_last % 4:
+        return (f"upsample_initial_channel {c0} over {len(rates)} stages: every stage needs a whole channel count that is a multiple "
+                "of 4 (the 4-column accesses of the elementwise kernels)")
+    if not 1 <= num_mels <= 4096:
+        return "num_mels must be in 1 .. 4096 (efts_pack_rows)"
+    return None
 
 
 class _ResBlock1(nn.Module):
@@ -87,9 +130,10 @@ class HiFiGANGenerator(nn.Module):
         self.res_dilations = tuple(tuple(d) for d in _cfg(h, "resblock_dilation_sizes"))
         c0 = int(_cfg(h, "upsample_initial_channel"))
         self.num_mels = int(_cfg(h, "num_mels", 80))
-        for u, k in zip(self.upsample_rates, self.upsample_kernel_sizes):
-            if k != 2 * u or u % 2:
-                raise NotImplementedError("transposed convolutions are implemented for kernel = 2 * stride, even stride")
+        why = _refusal(self.upsample_rates, self.upsample_kernel_sizes, self.res_kernels, self.res_dilations, c0, self.num_mels)
+        if why is not None:
+            raise NotImplementedError(why)
+        self.gap_frames = gap_frames(self.upsample_rates, self.res_kernels, self.res_dilations)
         self.conv_pre = weight_norm(nn.Conv1d(self.num_mels, c0, 7, 1, padding=3))
         self.ups = nn.ModuleList([weight_norm(nn.ConvTranspose1d(c0 // 2 ** i, c0 // 2 ** (i + 1), k, u, padding=(k - u) // 2))
                                   for i, (u, k) in enumerate(zip(self.upsample_rates, self.upsample_kernel_sizes))])
@@ -174,7 +218,7 @@ class HiFiGANGenerator(nn.Module):
         if len(self._bufs) > 2:
             self._bufs.pop(next(iter(self._bufs)))
         sp = self.split
-        pitch = T + _GAP_FRAMES                                                # rows per item at mel rate
+        pitch = T + self.gap_frames                                            # rows per item at mel rate
         rows = B * pitch
         b = {"pitch": pitch, "mel": _Rows(rows, self.num_mels, sp, dev, f32=False),
              "pre": _Rows(rows, self.conv_pre.out_channels, sp, dev, f32=False), "mask": []}
@@ -202,9 +246,11 @@ class HiFiGANGenerator(nn.Module):
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
-    def forward(self, x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, lengths: Optional[torch.Tensor] = None, keep: Optional[dict] = None) -> torch.Tensor:
         """mel [B, num_mels, T] -> audio [B, 1, T * hop].  `lengths` (frames per item, optional): every item is
-        synthesised exactly as if it had been passed alone without its padding; samples past lengths[b] * hop are 0."""
+        synthesised exactly as if it had been passed alone without its padding; samples past lengths[b] * hop are 0.
+        `keep` (a dict, for the tests; like `_forward_impl(..., keep=True)` of the acoustic model): every step's output buffer is
+        cloned into it (`_run`), which works with eagerly issued launches only: `graphs = False`, never under capture."""
         if x.dim() != 3 or x.shape[1] != self.num_mels:
             raise ValueError(f"expected mel [B, {self.num_mels}, T]")
         if not x.is_cuda:
@@ -229,9 +275,11 @@ class HiFiGANGenerator(nn.Module):
         def body(mel_btc, lens_i32):
             audio = torch.zeros(B, 1, T * hop, dtype=torch.float32, device=dev)
             with O.stream_scope():
-                self._run(pk, mel_btc, lens_i32, audio, B, T, hop, dev)
+                self._run(pk, mel_btc, lens_i32, audio, B, T, hop, dev, keep)
             return (audio,)
 
+        if keep is not None and (self.graphs or torch.cuda.is_current_stream_capturing()):
+            raise RuntimeError("keep: the stages are observed on eagerly issued launches only (graphs = False, no capture)")
         if not self.graphs or torch.cuda.is_current_stream_capturing():
             return body(mel, lens)[0]
         ws = self._workspace_for(B, T, dev)
@@ -246,7 +294,12 @@ class HiFiGANGenerator(nn.Module):
                resid_ptr=resid, ldr=ldr, rowmask_ptr=None if mask is None else mask.data_ptr(), out_f32_ptr=out_f, ldo=ldo,
                out_plane=out_p, dilation=dil, plane_act=plane_slope is not None, plane_slope=0.0 if plane_slope is None else plane_slope)
 
-    def _run(self, pk, mel_btc: torch.Tensor, lens: torch.Tensor, audio: torch.Tensor, B: int, T: int, hop: int, dev) -> None:
+    def _run(self, pk, mel_btc: torch.Tensor, lens: torch.Tensor, audio: torch.Tensor, B: int, T: int, hop: int, dev,
+             keep: Optional[dict] = None) -> None:
+        """keep (None: nothing happens): after each step a clone of what it wrote, made on the stream of the step's launch and complete
+        when `_run` returns (it ends with a device synchronisation then).  Whole buffers, guard rows included: "pre", "x{i}", "s{i}"
+        operand planes (uint8 [alloc][ld], row 0 at _GUARD); "r{i}.{j}.{d}" fp32 [alloc][c] of residual block j after pair d;
+        "up{i}" fp32 [rows][c] behind the u / 2-row offset; "out" fp32 [rows + 256][1]; "pitch": rows per item at mel rate."""
         b = self._workspace_for(B, T, dev)
         lib = L.load()
         sp = self.split
@@ -263,6 +316,8 @@ class HiFiGANGenerator(nn.Module):
         # conv_pre (:118); its only consumer applies leaky first (:120) -> the plane of leaky(x), no fp32 copy
         rows = B * pitch
         self._conv(pk, "conv_pre", mel_p, rows, 7, 1, mask=b["mask_mel"], out_p=b["pre"].p, plane_slope=LRELU_SLOPE)
+        if keep is not None:
+            keep["pitch"], keep["pre"] = pitch, b["pre"].p.buf.clone()
         cur_p, n, up_total = b["pre"].p, 0, 1
         for i, u in enumerate(self.upsample_rates):
             cout = self.ups[i].out_channels
@@ -279,6 +334,9 @@ class HiFiGANGenerator(nn.Module):
             # the transposed convolution's cropped border samples, which land in the zero rows between items
             L.check(lib.efts_act_bwd(x_f, x_f, None, mask.data_ptr(), LRELU_SLOPE, 3, None, x_p.ptr, x_p.ld, sp, None, n_i, cout, st),
                     "efts_act_bwd")
+            if keep is not None:
+                lo = (_GUARD + u // 2) * cout
+                keep[f"up{i}"], keep[f"x{i}"] = up.f.view(-1)[lo:lo + n_i * cout].view(n_i, cout).clone(), x_p.buf.clone()
             # The residual blocks of a stage (kernel sizes 3 / 7 / 11) are independent until their mean (:123-128): each runs as a chain of its own
             # on its own stream (round 6).  At one utterance a launch is 50-200 workgroups for 15-30 us: eighteen of them in a row per stage were
             # latency, not work (profiles/rocprofv3_r06_vocoder_summary.txt); two chains' workgroups fit a CU's LDS side by side.
@@ -304,6 +362,8 @@ class HiFiGANGenerator(nn.Module):
                         self._conv(pk, f"rb{n + j}.c2.{d_i}", tp, n_i, k, 1, mask=mask, out_f=nxt.fptr, ldo=cout, out_p=nxt.p,
                                    plane_slope=LRELU_SLOPE, resid=r_f, ldr=cout)                                        # :50-51
                         r_f, r_p = nxt.fptr, nxt.p
+                        if keep is not None:            # (on this chain's stream: the next pair but one writes this buffer again)
+                            keep[f"r{i}.{j}.{d_i}"] = nxt.f.clone()
                     finals[j] = r_f
                     if own is not None:
                         ev = torch.cuda.Event()
@@ -317,9 +377,14 @@ class HiFiGANGenerator(nn.Module):
             L.check(lib.efts_mean_act_rows(finals[0], finals[1] if len(finals) > 1 else None, finals[2] if len(finals) > 2 else None,
                                            cout, 1.0 / len(finals), 0.01 if last else LRELU_SLOPE, None, 0, s_p.ptr, s_p.ld, sp, n_i, cout,
                                            st), "efts_mean_act_rows")                                              # :128 (+ :120 / :129)
+            if keep is not None:
+                keep[f"s{i}"] = s_p.buf.clone()
             cur_p, rows = s_p, n_i
         self._conv(pk, "conv_post", cur_p, rows, 7, 1, mask=b["mask"][-1], out_f=b["out"].data_ptr(), ldo=1, act=L.ACT_TANH)   # :130-131
         audio[:, 0].copy_(b["out"][:rows, 0].view(B, pitch * hop)[:, :T * hop])
+        if keep is not None:
+            keep["out"] = b["out"].clone()
+            torch.cuda.synchronize(dev)                 # the side streams' clones included
 
 
 def load_hifigan_generator(device, config_path: str, checkpoint_path: str, precision: str = "bf16x3") -> HiFiGANGenerator:
