@@ -3,6 +3,7 @@
     python -m efficient_tts_amd.bin.score --checkpoint exp/efts/checkpoint-100000steps.pkl --test_fid_scp test.txt --outdir exp/efts/score \\
         [--config exp/efts/config.yml] [--batch_size 16] [--precision bf16x3] [--length_scale 1.0]
         [--f0 --vocoder griffinlim|hifigan [--vocoder_config c.json --vocoder_checkpoint g.pt] [--gl_iters 32] [--f0_min 60] [--f0_max 600] [--f0_threshold 0.15]]
+        [--trim_silence [--trim_top_db 40]] [--normalize_peak 0.95]
 
 Reads the `wav_path|phonemes` list of `efficient_tts_amd.bin.inference` (16-bit wav files at the front-end's rate; a path that does not
 exist is looked up by its file name under dataset_params.wav_path).  Per batch, on the device: the recordings' log-mels (`LogMelFrontend`
@@ -15,6 +16,11 @@ tracker (`efficient_tts_amd.pitch`) runs on the synthesis and on the recording, 
 `F0Error` gives the F0 error in cents over the cells voiced on both sides and the share of cells whose voicing differs.  mcd.tsv gets three more
 columns behind its own -- f0_rmse_cents, vuv_error, voiced_pairs -- and the last line their means over the utterances that have a value.
 Without `--f0` nothing changes.
+
+`--trim_silence` and `--normalize_peak` treat the RECORDINGS as a training run with `trim_silence` / `normalize_peak` in its recipe treats them
+(`efficient_tts_amd.trim.SilenceTrimmer` on the front-end's hop), before their log-mel and F0: the synthesis of a model trained on trimmed
+recordings carries no silence at its ends, and the recordings it is scored against should not either.  mcd.tsv then ends every line with two
+more columns, ref_trim_start and ref_trim_len (samples), and "-" in them on the line of the means.  Without the flags nothing changes.
 
 The numbers compare checkpoints of this project with each other (natural-log mels of this front-end); they are not comparable to MCDs
 computed from SPTK cepstra of waveforms.
@@ -32,6 +38,7 @@ from efficient_tts_amd.bin.inference import SAMPLING_RATE, _read_list, build_voc
 from efficient_tts_amd.frontend import LogMelFrontend
 from efficient_tts_amd.pitch import PitchTracker, lag_range
 from efficient_tts_amd.score import F0Error, MelCepstralDistortion
+from efficient_tts_amd.trim import SilenceTrimmer
 
 
 def get_parser() -> argparse.ArgumentParser:
@@ -52,7 +59,17 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--f0_min", type=float, default=60.0, help="--f0: lowest fundamental searched, Hz (default 60)")
     p.add_argument("--f0_max", type=float, default=600.0, help="--f0: highest fundamental searched, Hz (default 600)")
     p.add_argument("--f0_threshold", type=float, default=0.15, help="--f0: YIN threshold on the normalised difference function (default 0.15)")
+    p.add_argument("--trim_silence", action="store_true", help="cut the silence at both ends of every recording before it is scored against")
+    p.add_argument("--trim_top_db", type=float, default=40.0, help="--trim_silence: a frame this far under the loudest one is silence (default 40)")
+    p.add_argument("--normalize_peak", type=float, default=None, help="bring every recording to this peak, in (0, 1], before it is scored against")
     return p
+
+
+def build_trimmer(args, hop: int, max_wav_value: float, device=None):
+    """the SilenceTrimmer for the recordings, or None without --trim_silence / --normalize_peak"""
+    if not args.trim_silence and args.normalize_peak is None:
+        return None
+    return SilenceTrimmer(device, hop_size=hop, top_db=args.trim_top_db, peak=args.normalize_peak, max_wav_value=max_wav_value, trim=args.trim_silence)
 
 
 def check_f0_args(args, front=None) -> None:
@@ -94,6 +111,7 @@ def run_score(args) -> float:
     rate = int(front.get("sampling_rate", 22050))
     scorer = MelCepstralDistortion(device, num_mels=frontend.n_mels)
     check_f0_args(args, front)
+    trimmer = build_trimmer(args, frontend.hop, frontend.max_wav_value, device)
     if args.f0:
         vocoder = build_vocoder(args, device)
         tracker = PitchTracker(device, sampling_rate=rate, n_fft=frontend.n_fft, hop_size=frontend.hop, fmin=args.f0_min, fmax=args.f0_max,
@@ -102,21 +120,25 @@ def run_score(args) -> float:
     wav_dir = (config.get("dataset_params") or {}).get("wav_path")
     items = _read_list(args.test_fid_scp, phn2idx, with_paths=True)
     bs = max(1, int(args.batch_size))
-    rows, extra = [], []
+    rows, extra, cuts = [], [], []
     for lo in range(0, len(items), bs):
         chunk = items[lo:lo + bs]
         wavs = [_read_wav(path, wav_dir, rate) for _, _, path in chunk]
         audio = torch.nn.utils.rnn.pad_sequence(wavs, batch_first=True)
         ids = torch.nn.utils.rnn.pad_sequence([t for _, t, _ in chunk], batch_first=True)
+        wav_len = torch.tensor([w.shape[0] for w in wavs])
         with torch.no_grad():
-            rec, rec_len = frontend(audio, torch.tensor([w.shape[0] for w in wavs]))
+            if trimmer is not None:                # the recordings as a run with these options trains on them: fp32 on the device, new lengths
+                audio, wav_len, cut_start, _ = trimmer(audio.to(device), wav_len, return_bounds=True)
+                cuts.extend(zip(cut_start.tolist(), wav_len.tolist()))
+            rec, rec_len = frontend(audio, wav_len)
             syn, syn_len = model.inference_batch(ids.to(device), torch.tensor([len(t) for _, t, _ in chunk], device=device),
                                                  length_scale=args.length_scale)[:2]
             out = scorer(syn, syn_len, rec, rec_len, return_path=True) if args.f0 else scorer(syn, syn_len, rec, rec_len)
             if args.f0:
                 wav = vocoder(syn.transpose(1, 2).contiguous(), syn_len)[:, 0].float()
                 f0_syn = tracker(wav, syn_len * frontend.hop, max_frames=syn.shape[1], short_ok=True)[0]
-                f0_rec = tracker(audio, torch.tensor([w.shape[0] for w in wavs]), max_frames=rec.shape[1])[0]
+                f0_rec = tracker(audio, wav_len, max_frames=rec.shape[1])[0]
                 pitch = f0_error(f0_syn, f0_rec, out["path"], out["path_len"])
                 extra.extend(zip(pitch["f0_rmse_cents"].tolist(), pitch["vuv_error"].tolist(), pitch["voiced_pairs"].tolist()))
         for (utt, _, _), m, a, b, n in zip(chunk, out["mcd"].tolist(), syn_len.tolist(), rec_len.tolist(), out["path_len"].tolist()):
@@ -127,8 +149,12 @@ def run_score(args) -> float:
     with open(os.path.join(args.outdir, "mcd.tsv"), "w") as handle:
         for i, (utt, m, a, b, n) in enumerate(rows):
             tail = f"\t{extra[i][0]:.4f}\t{extra[i][1]:.6f}\t{extra[i][2]}" if args.f0 else ""
+            if trimmer is not None:
+                tail += f"\t{cuts[i][0]}\t{cuts[i][1]}"
             handle.write(f"{utt}\t{m:.6f}\t{a}\t{b}\t{n}{tail}\n")
         tail = f"\t{mean_of(0):.4f}\t{mean_of(1):.6f}\t{mean_of(2):.1f}" if args.f0 else ""
+        if trimmer is not None:
+            tail += "\t-\t-"
         handle.write(f"mean\t{mean:.6f}{tail}\n")
     print(f"mean MCD over {len(scored)} of {len(rows)} utterances: {mean:.4f} dB")
     if args.f0:

@@ -32,6 +32,7 @@ from efficient_tts_amd import datasets, models, optimizers, schedulers, trainers
 from efficient_tts_amd.dist import DistributedEFTS
 from efficient_tts_amd.frontend import LogMelFrontend
 from efficient_tts_amd.resample import Resampler
+from efficient_tts_amd.trim import SilenceTrimmer
 
 # (flags, kwargs) of the reference command line, kept as data so the parser and the docs cannot drift apart
 _CLI = (
@@ -117,6 +118,21 @@ def _build_data(config: Dict[str, Any], args: argparse.Namespace, proc: _Process
     return loaders, samplers
 
 
+def build_trimmer(config: Dict[str, Any], device=None) -> Optional[SilenceTrimmer]:
+    """the SilenceTrimmer that the recipe asks for, on the front-end's hop; None when neither `trim_silence` nor `normalize_peak` is set.
+    `trim_silence: true` (with `trim_top_db`, `trim_keep_frames`, `trim_frame_length`) cuts the quiet ends off every recording;
+    `normalize_peak: 0.95` brings what is kept to that peak, with or without trimming."""
+    trim, peak = bool(config.get("trim_silence", False)), config.get("normalize_peak")
+    if isinstance(peak, bool):
+        peak = 0.95 if peak else None
+    if not trim and peak is None:
+        return None
+    front = config.get("frontend_params") or {}
+    return SilenceTrimmer(device, frame_length=int(config.get("trim_frame_length", 1024)), hop_size=int(front.get("hop_size", 256)),
+                          top_db=float(config.get("trim_top_db", 40.0)), keep_frames=int(config.get("trim_keep_frames", 2)),
+                          peak=None if peak is None else float(peak), max_wav_value=float(front.get("max_wav_value", 32768.0)), trim=trim)
+
+
 def _build_trainer(config: Dict[str, Any], loaders, samplers, proc: _Process):
     device = proc.device
     net = getattr(models, config["model_name"])(**config["model_params"]).to(device)
@@ -140,6 +156,11 @@ def _build_trainer(config: Dict[str, Any], loaders, samplers, proc: _Process):
         trainer.resampler = Resampler(device, int(source_rate), front_rate, quality=config.get("resample_quality", "best"),
                                       max_wav_value=float(front.get("max_wav_value", 32768.0)))
         logging.info(f"resampling {source_rate} -> {front_rate} Hz on the device ({trainer.resampler.quality})")
+    trainer.trimmer = build_trimmer(config, device)
+    if trainer.trimmer is not None:
+        t = trainer.trimmer
+        logging.info(f"on the device, per recording: " + (f"silence trimmed at {t.top_db} dB under the loudest frame, {t.keep_frames} frames kept" if t.trim
+                                                           else "no trimming") + (f", peak set to {t.peak}" if t.peak is not None else ""))
     return trainer
 
 

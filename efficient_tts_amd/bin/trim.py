@@ -1,0 +1,93 @@
+"""`python -m efficient_tts_amd.bin.trim` -- what silence trimming and peak normalisation would do to a corpus, before training on it.
+
+    python -m efficient_tts_amd.bin.trim --filelist train.txt --wav_path wavs --outdir exp/trim \\
+        [--top_db 40] [--keep_frames 2] [--frame_length 1024] [--hop_size 256] [--normalize_peak 0.95] [--batch_size 16] [--write_wavs]
+
+Reads a training file list (`audiopath|...`, one recording per line; the file name is looked up under --wav_path, 16-bit mono wav files),
+runs the recordings through `efficient_tts_amd.trim.SilenceTrimmer` in batches -- the object that `trim_silence: true` / `normalize_peak`
+in the training recipe put in front of the log-mel front-end, so --top_db, --keep_frames and --frame_length mean what `trim_top_db`,
+`trim_keep_frames` and `trim_frame_length` mean there -- and writes outdir/trim.tsv:
+
+    id  samples  start  new_samples  gain  seconds_removed
+
+one line per recording under a header line (gain: what every kept sample was multiplied by, 1 / 32768 included; seconds at the file's own
+rate), and prints the totals.  `--write_wavs` also writes the results to outdir/<id>.wav as 16-bit PCM (rounded to nearest, clipped),
+to listen to a threshold before training on it.  There is no CPU mode.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+from efficient_tts_amd.trim import SilenceTrimmer
+
+
+def get_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="efficient_tts_amd.bin.trim", description=__doc__.splitlines()[0])
+    p.add_argument("--filelist", type=str, required=True, help="file list: audiopath|..., one recording per line")
+    p.add_argument("--wav_path", type=str, required=True, help="directory of the wav files (looked up by file name)")
+    p.add_argument("--outdir", type=str, required=True, help="where trim.tsv (and with --write_wavs the wav files) go")
+    p.add_argument("--top_db", type=float, default=40.0, help="a frame this far under the loudest one is silence (default 40)")
+    p.add_argument("--keep_frames", type=int, default=2, help="frames kept around the first and last sound frame (default 2)")
+    p.add_argument("--frame_length", type=int, default=1024, help="512, 1024 or 2048 samples (default 1024)")
+    p.add_argument("--hop_size", type=int, default=256, help="the front-end's hop (default 256)")
+    p.add_argument("--normalize_peak", type=float, default=None, help="bring every recording to this peak, in (0, 1] (default: leave the level)")
+    p.add_argument("--batch_size", type=int, default=16, help="recordings per call (default 16; every item is treated as if alone)")
+    p.add_argument("--write_wavs", action="store_true", help="also write the trimmed recordings as 16-bit wav files")
+    return p
+
+
+def _read_list(path: str):
+    with open(path, encoding="utf-8") as handle:
+        return [line.split("|")[0].strip() for line in handle if line.strip()]
+
+
+def run_trim(args) -> float:
+    from scipy.io.wavfile import read, write
+    trimmer = SilenceTrimmer(None, frame_length=args.frame_length, hop_size=args.hop_size, top_db=args.top_db, keep_frames=args.keep_frames,
+                             peak=args.normalize_peak)
+    if not torch.cuda.is_available():
+        raise RuntimeError("no MI355X (gfx950) device visible: efficient_tts_amd has no CPU path")
+    device = torch.device("cuda")
+    os.makedirs(args.outdir, exist_ok=True)
+    names = _read_list(args.filelist)
+    bs = max(1, int(args.batch_size))
+    removed = kept = 0.0
+    with open(os.path.join(args.outdir, "trim.tsv"), "w") as handle:
+        handle.write("id\tsamples\tstart\tnew_samples\tgain\tseconds_removed\n")
+        for lo in range(0, len(names), bs):
+            chunk = names[lo:lo + bs]
+            wavs, rates = [], []
+            for name in chunk:
+                sr, data = read(os.path.join(args.wav_path, os.path.basename(name)))
+                if data.dtype != np.int16 or data.ndim != 1:
+                    raise ValueError(f"{name}: expected mono 16-bit PCM")
+                wavs.append(torch.from_numpy(np.ascontiguousarray(data)))
+                rates.append(int(sr))
+            audio = torch.nn.utils.rnn.pad_sequence(wavs, batch_first=True).to(device)
+            out, new_len, start, gain = trimmer(audio, torch.tensor([w.shape[0] for w in wavs]), return_bounds=True)
+            new_len, start, gain = new_len.tolist(), start.tolist(), gain.tolist()
+            pcm = torch.round(out * 32768.0).clamp(-32768, 32767).to(torch.int16).cpu().numpy() if args.write_wavs else None
+            for i, name in enumerate(chunk):
+                utt = os.path.splitext(os.path.basename(name))[0]
+                n = int(wavs[i].shape[0])
+                seconds = (n - new_len[i]) / rates[i]
+                removed, kept = removed + seconds, kept + new_len[i] / rates[i]
+                handle.write(f"{utt}\t{n}\t{start[i]}\t{new_len[i]}\t{gain[i]:.9g}\t{seconds:.4f}\n")
+                if pcm is not None:
+                    write(os.path.join(args.outdir, utt + ".wav"), rates[i], pcm[i, :new_len[i]])
+    print(f"{len(names)} recordings: {removed:.2f} s removed, {kept:.2f} s kept")
+    return removed
+
+
+def main(argv=None) -> int:
+    run_trim(get_parser().parse_args(argv))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -84,7 +84,9 @@ extern "C" {
  *        + efts_resample, efts_resample_pcm16 (sample-rate conversion): exports added, the revision stays by the same rule
  *        + efts_mel_cepstrum, efts_dtw (scoring synthesis against a recording): exports added, the revision stays by the same rule
  *        + efts_yin, efts_yin_pcm16 (pitch tracking), efts_dtw_path, efts_dtw_path_workspace_bytes, efts_f0_path_error (the warping path and
- *          the F0 error along it): exports added, the revision stays by the same rule */
+ *          the F0 error along it): exports added, the revision stays by the same rule
+ *        + efts_trim, efts_trim_pcm16, efts_trim_workspace_bytes (silence trimming and peak normalisation): exports added, the revision stays
+ *          by the same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -892,6 +894,46 @@ int efts_yin(const float* audio, int64_t ld, const int32_t* lengths, float* f0, 
              int32_t n_fft, int32_t hop, int32_t sampling_rate, float fmin, float fmax, float threshold, void* stream);
 int efts_yin_pcm16(const int16_t* audio, int64_t ld, float pcm_scale, const int32_t* lengths, float* f0, float* aperiodicity, float* cmnd, int32_t B,
                    int32_t T, int32_t n_fft, int32_t hop, int32_t sampling_rate, float fmin, float fmax, float threshold, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Silence trimming and peak normalisation of a padded batch: the quiet ends of every item are cut off and what is left is scaled.
+ * Parameters: frame length W (512, 1024 or 2048), hop H (1 <= H <= W, W - H even), pad = (W - H) / 2, the threshold ratio
+ * r = 10^(top_db / 10) > 1 (computed by the caller in double), keep_frames, peak (<= 0: no normalisation), and on the int16 entry pcm_scale
+ * (1 / max_wav_value).  For item b with len = lengths[b] (clamped to 0 .. ld_in) samples x, x = 0 outside [0, len):
+ *   frames    : T = ceil(len / H); frame t covers samples t H - pad .. t H - pad + W - 1; its energy E_t is the sum of x^2 over the frame.
+ *               int16: the exact integer sum of the raw sample values in an unsigned 64-bit accumulator (at most 2048 * 2^30 = 2^41: every
+ *               order gives the same value).
+ *               fp32, ONE fixed order: a frame is R segments of S samples, segment j of the item starting at sample j H - pad; S = H and
+ *               R = W / H when H divides W and H >= 64, else S = W and R = 1.  Segment sum P_j: lane l = 0 .. 63 starts from 0 and takes
+ *               acc = fma(x_i, x_i, acc) over the segment's samples i = l, l + 64, l + 128, ... in ascending order; the 64 lane sums are
+ *               then combined by v = v + (the v of the lane 32 across), then 16, 8, 4, 2, 1 across (every lane ends with the same bits).
+ *               E_t = (..((P_t + P_{t+1}) + P_{t+2}) ..) + P_{t+R-1}.  Samples are addressed by their index in the item, never by their
+ *               address, so the order does not depend on where the row lies.
+ *   threshold : E_max = max over t of E_t.  Frame t is SOUND iff (double) E_t * r > (double) E_max: one correctly rounded fp64 multiply and
+ *               one compare.  E_max == 0 (an empty or all-zero item): no frame is sound.
+ *   bounds    : t_first / t_last the first / last sound frame: start = max(0, (t_first - keep_frames) H),
+ *               end = min(len, (t_last + 1 + keep_frames) H).  No sound frame: start = 0, end = len and the gain is 1.  new_len = end - start.
+ *               keep_frames < 0 switches the trimming off: every item keeps 0 .. len (normalisation alone).
+ *   gain      : p = max |x_i| over start <= i < end (exact; int16: of the raw integers).  With peak > 0 and p > 0: g = (float) peak / (float) p,
+ *               one correctly rounded fp32 division.  Otherwise g = pcm_scale on the int16 entry and 1 on the fp32 entry.
+ *   out[b * ld_out + i] = (float) x[start + i] * g for i < new_len, exactly 0.0f for new_len <= i < ld_out.
+ *   new_len, start (int32 [B]) and gain (fp32 [B]) are written by the kernels.
+ * No sample at or beyond len and no other row is read or influences anything; an item gives the same bits alone, at any batch position and
+ * in any run (no atomics).  lengths[b] == 0 is legal: zeros, new_len 0, gain 1.
+ * workspace : device memory, 16-byte aligned, of the size that the workspace-size entry returns for (B, max_len = ld_in, H, pcm16 = 0 for
+ *             the fp32 entry and 1 for the int16 entry): the frame energies [B][T_max] (uint64 or fp32) and, behind them, the peak of every
+ *             hop chunk c H .. c H + H - 1 [B][T_max] (int32 or fp32), T_max = ceil(ld_in / H).  Contents afterwards: unspecified.  The
+ *             size entry returns 0 for a non-positive argument.
+ * Three launches: energies and chunk peaks (the samples are read once, 16 bytes at a time where the row's address allows), the per-item
+ * decision on the workspace alone, and the compacting, scaling copy.  No host synchronisation, no allocation.
+ * EFTS_ESHAPE, nothing launched: B outside 1 .. 65535, ld_in < 1, ld_out < ld_in, either near 2^31, W other than 512, 1024, 2048, H outside
+ * 1 .. W or W - H odd.  EFTS_EINVAL: null pointer, a pointer not aligned to its element (the workspace: to 16 bytes), r <= 1.
+ * ---------------------------------------------------------------------------------- */
+int64_t efts_trim_workspace_bytes(int32_t B, int64_t max_len, int32_t H, int32_t pcm16);
+int efts_trim(const float* in, int64_t ld_in, const int32_t* lengths, int32_t W, int32_t H, double r, int32_t keep_frames, float peak, float* out,
+              int64_t ld_out, int32_t* new_len, int32_t* start, float* gain, void* workspace, int32_t B, void* stream);
+int efts_trim_pcm16(const int16_t* in, int64_t ld_in, const int32_t* lengths, int32_t W, int32_t H, double r, int32_t keep_frames, float peak,
+                    float pcm_scale, float* out, int64_t ld_out, int32_t* new_len, int32_t* start, float* gain, void* workspace, int32_t B, void* stream);
 
 #ifdef __cplusplus
 }
