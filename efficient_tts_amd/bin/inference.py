@@ -20,7 +20,8 @@ HiFi-GAN V1 generator (efficient_tts_amd.vocoder).  Differences from the referen
   * `--sampling_rate R [--resample_quality best|fast]` writes the wav files at R Hz instead of the vocoder's 22 050 Hz: the vocoder's
     output is converted on the device (efficient_tts_amd.resample) in front of the 16-bit quantisation;
   * `--write_f0` writes the pitch contour of every utterance next to its wav (<id>_<step>.f0.txt: frame index, time in seconds, f0 in Hz with 0 for an
-    unvoiced frame), tracked on the device from the vocoder's output (efficient_tts_amd.pitch) on the mel frames' grid.
+    unvoiced frame), tracked on the device from the vocoder's output (efficient_tts_amd.pitch) on the mel frames' grid;
+    `--f0_smooth` decides the frames of an utterance together (the tracker's Viterbi path over all lags) instead of one by one.
 """
 from __future__ import annotations
 
@@ -69,6 +70,7 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--resample_quality", type=str, default="best", choices=sorted(QUALITIES), help="filter of --sampling_rate (default best)")
     p.add_argument("--write_f0", action="store_true",
                    help="also write <id>_<step>.f0.txt: frame index, time in seconds, f0 in Hz (0: unvoiced) of the vocoder's output")
+    p.add_argument("--f0_smooth", action="store_true", help="--write_f0: smooth the contour across frames (the cheapest path over the lags of all frames)")
     p.add_argument("--verbose", type=int, default=1)
     return p
 
@@ -140,7 +142,14 @@ def _write_durations(path: str, phonemes: List[str], frames, hop: int, sampling_
             start += int(n)
 
 
+def check_f0_smooth(args) -> None:
+    """--f0_smooth changes how --write_f0 tracks: alone it would do nothing, so it is refused (on the host, before anything is loaded)"""
+    if args.f0_smooth and not args.write_f0:
+        raise ValueError("--f0_smooth smooths the contour that --write_f0 writes: give --write_f0 as well")
+
+
 def run_tts(args) -> float:
+    check_f0_smooth(args)
     level = {0: logging.WARNING, 1: logging.INFO}.get(args.verbose, logging.DEBUG)
     logging.basicConfig(level=level, stream=sys.stdout, force=True, format="%(asctime)s %(levelname)s %(name)s:%(lineno)d  %(message)s")
     if not torch.cuda.is_available():
@@ -164,7 +173,7 @@ def run_tts(args) -> float:
     if args.write_f0 and args.no_vocoder:
         raise ValueError("--write_f0 tracks the vocoder's output: it cannot be combined with --no_vocoder")
     vocoder = None if args.no_vocoder else build_vocoder(args, device)
-    tracker = PitchTracker(device, sampling_rate=SAMPLING_RATE, n_fft=1024, hop_size=256) if args.write_f0 else None
+    tracker = PitchTracker(device, sampling_rate=SAMPLING_RATE, n_fft=1024, hop_size=256, smooth=args.f0_smooth) if args.write_f0 else None
     resampler = None
     if vocoder is not None and out_rate != SAMPLING_RATE:
         resampler = Resampler(device, SAMPLING_RATE, out_rate, quality=args.resample_quality)

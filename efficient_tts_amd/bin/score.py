@@ -2,7 +2,7 @@
 
     python -m efficient_tts_amd.bin.score --checkpoint exp/efts/checkpoint-100000steps.pkl --test_fid_scp test.txt --outdir exp/efts/score \\
         [--config exp/efts/config.yml] [--batch_size 16] [--precision bf16x3] [--length_scale 1.0]
-        [--f0 --vocoder griffinlim|hifigan [--vocoder_config c.json --vocoder_checkpoint g.pt] [--gl_iters 32] [--f0_min 60] [--f0_max 600] [--f0_threshold 0.15]]
+        [--f0 --vocoder griffinlim|hifigan [--vocoder_config c.json --vocoder_checkpoint g.pt] [--gl_iters 32] [--f0_min 60] [--f0_max 600] [--f0_threshold 0.15] [--f0_smooth]]
         [--trim_silence [--trim_top_db 40]] [--normalize_peak 0.95]
 
 Reads the `wav_path|phonemes` list of `efficient_tts_amd.bin.inference` (16-bit wav files at the front-end's rate; a path that does not
@@ -15,7 +15,8 @@ mean -- and prints the mean.  An utterance whose synthesis has no frames has no 
 tracker (`efficient_tts_amd.pitch`) runs on the synthesis and on the recording, the MCD's own warping path is kept, and along it
 `F0Error` gives the F0 error in cents over the cells voiced on both sides and the share of cells whose voicing differs.  mcd.tsv gets three more
 columns behind its own -- f0_rmse_cents, vuv_error, voiced_pairs -- and the last line their means over the utterances that have a value.
-Without `--f0` nothing changes.
+`--f0_smooth` smooths both contours, synthesis and recording, across frames before the error is read (the tracker's Viterbi path over all lags
+instead of YIN's frame-by-frame rule, whose octave errors of 1200 cents each otherwise dominate f0_rmse_cents).  Without `--f0` nothing changes.
 
 `--trim_silence` and `--normalize_peak` treat the RECORDINGS as a training run with `trim_silence` / `normalize_peak` in its recipe treats them
 (`efficient_tts_amd.trim.SilenceTrimmer` on the front-end's hop), before their log-mel and F0: the synthesis of a model trained on trimmed
@@ -59,6 +60,7 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--f0_min", type=float, default=60.0, help="--f0: lowest fundamental searched, Hz (default 60)")
     p.add_argument("--f0_max", type=float, default=600.0, help="--f0: highest fundamental searched, Hz (default 600)")
     p.add_argument("--f0_threshold", type=float, default=0.15, help="--f0: YIN threshold on the normalised difference function (default 0.15)")
+    p.add_argument("--f0_smooth", action="store_true", help="--f0: smooth both contours across frames (the cheapest path over the lags of all frames)")
     p.add_argument("--trim_silence", action="store_true", help="cut the silence at both ends of every recording before it is scored against")
     p.add_argument("--trim_top_db", type=float, default=40.0, help="--trim_silence: a frame this far under the loudest one is silence (default 40)")
     p.add_argument("--normalize_peak", type=float, default=None, help="bring every recording to this peak, in (0, 1], before it is scored against")
@@ -74,6 +76,8 @@ def build_trimmer(args, hop: int, max_wav_value: float, device=None):
 
 def check_f0_args(args, front=None) -> None:
     """--f0 needs audio of the synthesis that means something: refused on the host, before anything is loaded"""
+    if args.f0_smooth and not args.f0:
+        raise ValueError("--f0_smooth smooths the contours that --f0 scores: give --f0 as well")
     if not args.f0:
         return
     if args.vocoder == "hifigan" and not (args.vocoder_checkpoint and args.vocoder_config):
@@ -115,7 +119,7 @@ def run_score(args) -> float:
     if args.f0:
         vocoder = build_vocoder(args, device)
         tracker = PitchTracker(device, sampling_rate=rate, n_fft=frontend.n_fft, hop_size=frontend.hop, fmin=args.f0_min, fmax=args.f0_max,
-                               threshold=args.f0_threshold, max_wav_value=frontend.max_wav_value)
+                               threshold=args.f0_threshold, max_wav_value=frontend.max_wav_value, smooth=args.f0_smooth)
         f0_error = F0Error(device)
     wav_dir = (config.get("dataset_params") or {}).get("wav_path")
     items = _read_list(args.test_fid_scp, phn2idx, with_paths=True)

@@ -205,6 +205,9 @@ _SIGS = {
     # pitch tracking
     "efts_yin": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp]),
     "efts_yin_pcm16": (i32, [vp, i64, f32, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp]),
+    # pitch smoothing across frames: the integer Viterbi path over d'
+    "efts_f0_viterbi_workspace_bytes": (i64, [i32, i32, i32]),
+    "efts_f0_viterbi": (i32, [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     # silence trimming and peak normalisation
     "efts_trim_workspace_bytes": (i64, [i32, i64, i32, i32]),
     "efts_trim": (i32, [vp, i64, vp, i32, i32, C.c_double, i32, f32, vp, i64, vp, vp, vp, vp, i32, vp]),

@@ -86,7 +86,9 @@ extern "C" {
  *        + efts_yin, efts_yin_pcm16 (pitch tracking), efts_dtw_path, efts_dtw_path_workspace_bytes, efts_f0_path_error (the warping path and
  *          the F0 error along it): exports added, the revision stays by the same rule
  *        + efts_trim, efts_trim_pcm16, efts_trim_workspace_bytes (silence trimming and peak normalisation): exports added, the revision stays
- *          by the same rule */
+ *          by the same rule
+ *        + efts_f0_viterbi, efts_f0_viterbi_workspace_bytes (pitch smoothing across frames): exports added, the revision stays by the same
+ *          rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -894,6 +896,50 @@ int efts_yin(const float* audio, int64_t ld, const int32_t* lengths, float* f0, 
              int32_t n_fft, int32_t hop, int32_t sampling_rate, float fmin, float fmax, float threshold, void* stream);
 int efts_yin_pcm16(const int16_t* audio, int64_t ld, float pcm_scale, const int32_t* lengths, float* f0, float* aperiodicity, float* cmnd, int32_t B,
                    int32_t T, int32_t n_fft, int32_t hop, int32_t sampling_rate, float fmin, float fmax, float threshold, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Smoothing the pitch across frames: the cheapest path (Viterbi) over the lags of every frame, on the d' that efts_yin writes.  All costs
+ * are integers in Q16 and the recurrence is integer-only, so the path has exactly one right answer: a restatement in 64-bit integers
+ * reproduces it bit for bit (tests/viterbi_reference.py does), and no tolerance applies to it.
+ *   cmnd    : fp32, d'(tau) of item b, frame t at cmnd[b * item_stride + t * frame_stride + tau], tau = 0 .. tau_max (strides in floats, the
+ *             lag is the unit-stride axis); only frames below the item's count are read
+ *   frames  : [B]; item b has n = frames[b] clamped to 0 .. T frames.  n = 0 is legal.
+ *   ranges  : 2 <= tau_min < tau_max - 1, tau_max <= EFTS_VITERBI_MAX_LAG
+ *   states  : S = tau_max - tau_min voiced states, state s is the lag k = tau_min + s (lags tau_min .. tau_max - 1); state S is unvoiced
+ * Fixed point, Q = 65536:
+ *   lg      : int32 [tau_max + 1], lg[k] = rint(log2(k) Q) for k = 1 .. tau_max, built by the caller in float64 (entry 0 is not read); the
+ *             library computes no logarithm
+ *   costs   : unvoiced_q, octave_q, jump_q, vuv_q: int32, rint((double) value * Q), each in 0 .. 16 Q
+ *   q(x)    = x < 4.0f ? (int) rintf(x * 65536.f) : 4 Q, so NaN and +inf land on 4 Q.  d' is never negative; an x at or below -4 -- outside
+ *             what efts_yin writes -- counts as -4 Q.
+ *   obs(t, s) = q(cmnd[t][k]) + (((int64) octave_q * (lg[k] - lg[tau_min])) >> 16) for a voiced state;  obs(t, S) = unvoiced_q
+ *   trans   : voiced k' -> voiced k: ((int64) jump_q * |lg[k] - lg[k']|) >> 16;  voiced <-> unvoiced: vuv_q;  unvoiced -> unvoiced: 0
+ * Recurrence:
+ *   C(0, s) = obs(0, s);   C(t, s) = obs(t, s) + min over p of (C(t - 1, p) + trans(p, s))
+ *   ties: the predecessor with the lowest state index wins; the final state is the lowest index among the minima of C(n - 1, .); the path
+ *   is traced back from there.  The path is exact for every T the call admits: each frame is stored less the minimum of the frame before,
+ *   which moves no argmin, so 32 bits never overflow.
+ * Outputs, [B][T] each, for t < n with k the lag of the path's state at t:
+ *   lag          : int32, k, or 0 for the unvoiced state
+ *   f0           : voiced: sampling_rate / (k + shift) with efts_yin's parabola AT k (no walk to a local minimum): fp32, s0, s1, s2 =
+ *                  d'(k - 1), d'(k), d'(k + 1), den = (s0 - s1) + (s2 - s1), shift = 0.5 (s0 - s2) / den clamped to [-1, 1], 0 when den == 0.
+ *                  Unvoiced: 0.
+ *   aperiodicity : voiced: d'(k).  Unvoiced: the smallest d' over the lags tau_min .. tau_max - 1 (fminf: a NaN is passed over).
+ *   All three are 0 for n <= t < T.
+ * workspace : device memory, 16-byte aligned, B times what the workspace-size entry returns for the same (T, tau_min, tau_max): one uint16
+ *   back-pointer per (frame, state), T (S + 1) 2 bytes per item rounded up to 16.  workspace_bytes is what the caller holds.  Contents
+ *   afterwards: unspecified.  The size entry returns 0 for arguments that the call would refuse; it is monotone in T and in S.
+ * One launch, one workgroup per item, no atomics: an item gives the same bits alone, in any batch position and in any run.
+ * EFTS_EINVAL: null pointer.  EFTS_ESHAPE, nothing launched: a lag range outside the above, B outside 1 .. 65535, T outside
+ * 1 .. EFTS_VITERBI_MAX_FRAMES, sampling_rate < 1, frame_stride < tau_max + 1, item_stride < 0, a cost outside 0 .. 16 Q, a workspace smaller
+ * than B items need.  EFTS_EALIGN: workspace misaligned.
+ * ---------------------------------------------------------------------------------- */
+#define EFTS_VITERBI_MAX_LAG 1024
+#define EFTS_VITERBI_MAX_FRAMES 1048576
+int64_t efts_f0_viterbi_workspace_bytes(int32_t T, int32_t tau_min, int32_t tau_max);
+int efts_f0_viterbi(const float* cmnd, int64_t item_stride, int64_t frame_stride, const int32_t* frames, const int32_t* lg, float* f0,
+                    float* aperiodicity, int32_t* lag, void* workspace, int64_t workspace_bytes, int32_t B, int32_t T, int32_t tau_min,
+                    int32_t tau_max, int32_t sampling_rate, int32_t unvoiced_q, int32_t octave_q, int32_t jump_q, int32_t vuv_q, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Silence trimming and peak normalisation of a padded batch: the quiet ends of every item are cut off and what is left is scaled.

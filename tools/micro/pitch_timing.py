@@ -1,4 +1,5 @@
-"""Time the pitch tracker and the path-returning DTW on the GPU; writes profiles/pitch_timing.json.
+"""Time the pitch tracker, its smoother and the path-returning DTW on the GPU; writes profiles/pitch_timing.json and
+profiles/pitch_viterbi_timing.json.
 
 Three measurements, every arm warmed up first and the arms of one measurement interleaved round by round inside one process:
   yin      : efts_yin_pcm16 on 64 items x 800 frames of int16 PCM (n_fft 1024, hop 256, 60 .. 600 Hz: lags 36 .. 367), against the same YIN on
@@ -7,10 +8,13 @@ Three measurements, every arm warmed up first and the arms of one measurement in
              walks the batch in slices of `--stock_items` items and 32 lags, as a user of stock ops would have to.
   dtw_path : efts_dtw_path against efts_dtw on the 64 ragged pairs of tools/micro/score_timing.py: what the move record and the back-trace cost.
   f0_error : efts_f0_path_error on those paths (one small launch).
+  viterbi  : (its own file) efts_f0_viterbi on the 64 x 800 frames of d' that the yin measurement's kernel wrote, lags 36 .. 367, against the same
+             integer recurrence on stock torch ops on the same GPU -- per frame one broadcast add [B, S + 1, S + 1] and one min over the
+             predecessors, then the back-trace by `gather` -- and the tracker's call with and without `smooth=True`: what smoothing adds to it.
 Reported per arm: ms per call (median and min over the rounds); for yin also the fused multiply-adds of the difference function per second,
 counted from the shapes (frames x lags x W), which is what bounds the kernel.  Not a gate: nothing asserts on the times.
 
-    python tools/micro/pitch_timing.py [--items 64] [--frames 800] [--rounds 5]
+    python tools/micro/pitch_timing.py [--items 64] [--frames 800] [--rounds 5] [--measure all|viterbi]
 """
 import argparse
 import json
@@ -22,7 +26,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from efficient_tts_amd.pitch import PitchTracker  # noqa: E402
+from efficient_tts_amd.pitch import Q16, PitchTracker, ViterbiSmoother, log2_table  # noqa: E402
 from efficient_tts_amd.score import F0Error, dtw, dtw_path  # noqa: E402
 
 SR, N_FFT, HOP = 22050, 1024, 256
@@ -62,6 +66,32 @@ def stock_yin(audio, lengths, tau_min, tau_max, threshold, items_per_slice):
     return out
 
 
+def stock_viterbi(cmnd, tau_min, tau_max, costs_q):
+    """lag [B, T] of full-length items by stock ops: the recurrence of include/efts_abi.h in int64, one broadcast add and one min per frame"""
+    B, T, _ = cmnd.shape
+    S = tau_max - tau_min
+    uq, oq, jq, vq = costs_q
+    lg = log2_table(tau_max).to(cmnd.device).long()[tau_min:tau_max]
+    x = cmnd[:, :, tau_min:tau_max]
+    obs = torch.where(x < 4.0, torch.round(x.clamp(-4.0, 4.0) * 65536.0), torch.full_like(x, 4.0 * Q16)).long() + ((oq * (lg - lg[0])) >> 16)
+    obs = torch.cat([obs, torch.full((B, T, 1), uq, dtype=torch.long, device=cmnd.device)], dim=2)
+    trans = torch.full((S + 1, S + 1), vq, dtype=torch.long, device=cmnd.device)
+    trans[:S, :S] = (jq * (lg[None, :] - lg[:, None]).abs()) >> 16
+    trans[S, S] = 0
+    C = obs[:, 0]
+    back = torch.empty(B, T, S + 1, dtype=torch.long, device=cmnd.device)
+    for t in range(1, T):
+        best, back[:, t] = (C[:, :, None] + trans[None]).min(dim=1)             # the first, i.e. lowest, index among equal minima is not promised by
+        C = obs[:, t] + best                                                    # torch.min: the arm is a yardstick for time
+    state = C.argmin(dim=1, keepdim=True)
+    states = [state]
+    for t in range(T - 1, 0, -1):
+        state = back[:, t].gather(1, state)
+        states.append(state)
+    states = torch.cat(states[::-1], dim=1)
+    return torch.where(states < S, states + tau_min, torch.zeros_like(states))
+
+
 def timed(arms, calls, rounds):
     times = {name: [] for name in arms}
     for _ in range(rounds):
@@ -76,6 +106,39 @@ def timed(arms, calls, rounds):
     return times
 
 
+def viterbi(args, dev, tracker, pcm, lengths):
+    B, T = args.items, args.frames
+    cmnd, frames = tracker(pcm, lengths, return_cmnd=True)[3], torch.full((B,), T, dtype=torch.int32, device=dev)
+    smoother = ViterbiSmoother(dev, SR, tracker.tau_min, tracker.tau_max)
+    smooth_tracker = PitchTracker(dev, sampling_rate=SR, n_fft=N_FFT, hop_size=HOP, smooth=True)
+    arms = {"hip": lambda: smoother(cmnd, frames), "stock": lambda: stock_viterbi(cmnd, tracker.tau_min, tracker.tau_max, smoother.costs_q),
+            "tracker": lambda: tracker(pcm, lengths), "tracker_smooth": lambda: smooth_tracker(pcm, lengths)}
+    outs = {}
+    for name, fn in arms.items():
+        for _ in range(args.warmup):
+            outs[name] = fn()
+    torch.cuda.synchronize()
+    hip_lag, stock_lag = outs["hip"][2].long(), outs["stock"]
+    agree = float((hip_lag == stock_lag).float().mean())
+    calls = {"hip": args.hip_calls, "stock": args.stock_calls, "tracker": args.hip_calls, "tracker_smooth": args.hip_calls}
+    times = timed(arms, calls, args.rounds)
+    lines = [dict(measurement="viterbi", leg=name, ms_median=round(statistics.median(times[name]), 4), ms_min=round(min(times[name]), 4),
+                  ms_rounds=[round(v, 4) for v in times[name]], calls=calls[name], warmup=args.warmup, items=B, frames=T) for name in arms]
+    med = {name: statistics.median(times[name]) for name in arms}
+    S = tracker.tau_max - tracker.tau_min
+    lines.append(dict(summary="viterbi", hip_ms=round(med["hip"], 4), stock_torch_ms=round(med["stock"], 4), stock_over_hip=round(med["stock"] / med["hip"], 2),
+                      tracker_ms=round(med["tracker"], 4), tracker_smooth_ms=round(med["tracker_smooth"], 4),
+                      smooth_over_plain_tracker=round(med["tracker_smooth"] / med["tracker"], 3),
+                      us_per_frame_of_the_chain=round(med["hip"] * 1e3 / T, 3), state_pairs_unpruned=B * (T - 1) * (S + 1) * (S + 1),
+                      lags=[tracker.tau_min, tracker.tau_max], voiced_share=round(float((hip_lag > 0).float().mean()), 4),
+                      lag_agreement_with_stock=round(agree, 5), device=torch.cuda.get_device_name(0)))
+    os.makedirs(os.path.dirname(args.viterbi_out), exist_ok=True)
+    with open(args.viterbi_out, "w") as fh:
+        for line in lines:
+            fh.write(json.dumps(line) + "\n")
+            print(json.dumps(line), flush=True)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--items", type=int, default=64)
@@ -86,6 +149,8 @@ def main() -> int:
     ap.add_argument("--stock_items", type=int, default=4, help="items per slice of the stock-torch YIN")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "pitch_timing.json"))
+    ap.add_argument("--viterbi_out", type=str, default=os.path.join(ROOT, "profiles", "pitch_viterbi_timing.json"))
+    ap.add_argument("--measure", type=str, default="all", choices=["all", "viterbi"], help="viterbi: only the smoother's measurement and its file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError("no MI355X (gfx950) device visible: nothing to time")
@@ -101,6 +166,9 @@ def main() -> int:
     pcm = (wave * 20000.0 + 300.0 * torch.randn(B, n, generator=g, dtype=torch.float64)).round().clamp(-32768, 32767).to(torch.int16).to(dev)
     lengths = torch.full((B,), n)
     tracker = PitchTracker(dev, sampling_rate=SR, n_fft=N_FFT, hop_size=HOP)
+    viterbi(args, dev, tracker, pcm, lengths)
+    if args.measure == "viterbi":
+        return 0
     lines = []
 
     arms = {"hip": lambda: tracker(pcm, lengths), "stock": lambda: stock_yin(pcm, lengths, tracker.tau_min, tracker.tau_max, 0.15, args.stock_items)}
