@@ -1,0 +1,126 @@
+"""`python -m efficient_tts_amd.bin.vocoder_score` -- multi-resolution STFT distance of a vocoder's copy-synthesis against the recordings.
+
+    python -m efficient_tts_amd.bin.vocoder_score --test_fid_scp test.txt --outdir exp/vocoder/score \\
+        --vocoder griffinlim|hifigan [--vocoder_config c.json --vocoder_checkpoint g.pt] [--gl_iters 32] [--precision bf16x3]
+        [--batch_size 16] [--wav_path wavs/]
+
+Copy-synthesis: recording -> log-mel (`LogMelFrontend`) -> vocoder (the `--vocoder` switches of `efficient_tts_amd.bin.inference`) -> audio,
+compared with the recording over min(len) samples by `MultiResolutionSTFTDistance` at the reference's three resolutions.  No acoustic
+checkpoint is involved.  Reads the `wav_path|...` list of `efficient_tts_amd.bin.inference` (only the path is used; 16-bit wav files at
+22 050 Hz; a path that does not exist is looked up by its file name under --wav_path).  Writes outdir/mrstft.tsv -- utterance id, samples
+compared, then sc and log_mag per resolution, then their means over the resolutions; the last line holds the means over the utterances that
+have a value -- and prints those means.  An utterance too short for a resolution has nan there and in its own means.
+
+sc is the spectral convergence ||mag_rec - mag_syn||_F / ||mag_rec||_F, log_mag the mean |ln mag_rec - ln mag_syn|; both are 0 for a perfect
+copy.  The numbers judge `--precision`, `--gl_iters` and vocoder checkpoints against each other on the same recordings.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+from efficient_tts_amd.stft import DEFAULT_RESOLUTIONS
+
+SAMPLING_RATE = 22050
+
+
+def get_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="efficient_tts_amd.bin.vocoder_score", description=__doc__.splitlines()[0])
+    p.add_argument("--test_fid_scp", type=str, required=True, help="utterance list: wav_path, optionally followed by |anything")
+    p.add_argument("--outdir", type=str, required=True, help="where mrstft.tsv goes")
+    p.add_argument("--vocoder", type=str, default="hifigan", choices=["hifigan", "griffinlim"], help="what turns the recordings' log-mels back into audio")
+    p.add_argument("--vocoder_config", type=str, default=None, help="HiFi-GAN config.json")
+    p.add_argument("--vocoder_checkpoint", type=str, default=None, help='HiFi-GAN checkpoint with a "generator" state_dict')
+    p.add_argument("--gl_iters", type=int, default=32, help="Griffin-Lim iterations (--vocoder griffinlim; default 32)")
+    p.add_argument("--precision", type=str, default="bf16x3", choices=["bf16x3", "bf16", "fp32"], help="MFMA operand mode of the vocoder")
+    p.add_argument("--batch_size", type=int, default=16, help="utterances per call (default 16; every item is scored as if alone)")
+    p.add_argument("--wav_path", type=str, default=None, help="directory searched, by file name, for a wav path that does not exist")
+    return p
+
+
+def check_args(args) -> None:
+    """a generator with random weights has nothing to score: refused on the host, before anything is loaded"""
+    if args.vocoder == "hifigan" and not (args.vocoder_checkpoint and args.vocoder_config):
+        raise ValueError("--vocoder hifigan needs --vocoder_checkpoint and --vocoder_config (a generator with random weights has no copy-synthesis "
+                         "to score); --vocoder griffinlim needs no weights")
+    if args.batch_size < 1:
+        raise ValueError("--batch_size must be >= 1")
+
+
+def columns(resolutions=DEFAULT_RESOLUTIONS):
+    """the columns of mrstft.tsv"""
+    names = ["utt", "samples"]
+    for n, h, w in resolutions:
+        names += [f"sc_{n}_{h}_{w}", f"log_mag_{n}_{h}_{w}"]
+    return names + ["sc_mean", "log_mag_mean"]
+
+
+def format_rows(rows, resolutions=DEFAULT_RESOLUTIONS):
+    """the lines of mrstft.tsv from (utt, samples, sc [R], log_mag [R]) per utterance, and the two means that the last line ends with"""
+    lines, table = [], []
+    for utt, n, sc, lm in rows:
+        vals = [v for pair in zip(sc, lm) for v in pair] + [float(np.mean(sc)), float(np.mean(lm))]       # (nan in a resolution: nan in the mean)
+        table.append(vals)
+        lines.append("\t".join([utt, str(int(n))] + [f"{v:.6f}" for v in vals]))
+    table = np.asarray(table, dtype=np.float64).reshape(len(rows), 2 * len(resolutions) + 2)
+    means = [float(np.mean(col[np.isfinite(col)])) if np.isfinite(col).any() else float("nan") for col in table.T]
+    lines.append("\t".join(["mean", "-"] + [f"{v:.6f}" for v in means]))
+    return lines, means[-2], means[-1]
+
+
+def _read_paths(path: str):
+    items = []
+    with open(path) as handle:
+        for line in handle:
+            line = line.strip()
+            if line:
+                wav = line.split("|")[0]
+                items.append((os.path.splitext(os.path.basename(wav))[0], wav))
+    return items
+
+
+def run_score(args):
+    check_args(args)
+    if not torch.cuda.is_available():
+        raise RuntimeError("no MI355X (gfx950) device visible: efficient_tts_amd has no CPU path")
+    from efficient_tts_amd.bin.inference import build_vocoder
+    from efficient_tts_amd.bin.score import _read_wav
+    from efficient_tts_amd.frontend import LogMelFrontend
+    from efficient_tts_amd.stft import MultiResolutionSTFTDistance
+    device = torch.device("cuda")
+    os.makedirs(args.outdir, exist_ok=True)
+    frontend = LogMelFrontend(device)
+    vocoder = build_vocoder(args, device)
+    scorer = MultiResolutionSTFTDistance(device, max_wav_value=frontend.max_wav_value)
+    items = _read_paths(args.test_fid_scp)
+    rows = []
+    for lo in range(0, len(items), args.batch_size):
+        chunk = items[lo:lo + args.batch_size]
+        wavs = [_read_wav(path, args.wav_path, SAMPLING_RATE) for _, path in chunk]
+        audio = torch.nn.utils.rnn.pad_sequence(wavs, batch_first=True).to(device)
+        wav_len = torch.tensor([w.shape[0] for w in wavs], device=device)
+        with torch.no_grad():
+            mel, mel_len = frontend(audio, wav_len)
+            syn = vocoder(mel.transpose(1, 2).contiguous(), mel_len)[:, 0].float()
+            n = torch.minimum(wav_len, mel_len.to(wav_len.dtype) * frontend.hop).clamp(max=min(syn.shape[1], audio.shape[1]))
+            out = scorer(syn, audio, n)
+        for (utt, _), k, sc, lm in zip(chunk, n.tolist(), out["sc"].tolist(), out["log_mag"].tolist()):
+            rows.append((utt, k, sc, lm))
+    lines, sc_mean, lm_mean = format_rows(rows)
+    with open(os.path.join(args.outdir, "mrstft.tsv"), "w") as handle:
+        handle.write("\n".join(lines) + "\n")
+    print(f"copy-synthesis of {len(rows)} utterances with {args.vocoder}: mean spectral convergence {sc_mean:.4f}, mean log-magnitude distance {lm_mean:.4f}")
+    return sc_mean, lm_mean
+
+
+def main(argv=None) -> int:
+    run_score(get_parser().parse_args(argv))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -88,7 +88,9 @@ extern "C" {
  *        + efts_trim, efts_trim_pcm16, efts_trim_workspace_bytes (silence trimming and peak normalisation): exports added, the revision stays
  *          by the same rule
  *        + efts_f0_viterbi, efts_f0_viterbi_workspace_bytes (pitch smoothing across frames): exports added, the revision stays by the same
- *          rule */
+ *          rule
+ *        + efts_stft_mag, efts_stft_dist, efts_stft_dist_workspace_bytes (STFT magnitudes at four sizes and the multi-resolution STFT
+ *          distance): exports added, the revision stays by the same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -980,6 +982,41 @@ int efts_trim(const float* in, int64_t ld_in, const int32_t* lengths, int32_t W,
               int64_t ld_out, int32_t* new_len, int32_t* start, float* gain, void* workspace, int32_t B, void* stream);
 int efts_trim_pcm16(const int16_t* in, int64_t ld_in, const int32_t* lengths, int32_t W, int32_t H, double r, int32_t keep_frames, float peak,
                     float pcm_scale, float* out, int64_t ld_out, int32_t* new_len, int32_t* start, float* gain, void* workspace, int32_t B, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * STFT magnitudes and the STFT distance between two signals at one resolution (N, H, W): FFT size N (256, 512, 1024 or 2048), hop
+ * 1 <= H <= N, window length 2 <= W <= N.  Replaces nntts/losses/stft_loss.py: stft (:12-32), SpectralConvergenceLoss (:53),
+ * LogSTFTMagnitudeLoss (:74); MultiResolutionSTFTLoss (:110) is one call per resolution.
+ *   samples : fp32, or int16 PCM (pcm16 != 0) multiplied by pcm_scale (1 / max_wav_value) at the load; an fp32 signal is not scaled.
+ *             Item b is row b of its [B][ld] array and has len = lengths[b], clamped to 0 .. max_len, samples; nothing behind them is read.
+ *   window  : [W] fp32, DEVICE memory: the periodic Hann window w[i] = 0.5 - 0.5 cos(2 pi i / W), computed by the caller in float64 and
+ *             rounded once.  It sits in the N-sample frame with (N - W) / 2 (integer division) zeros in front, as torch.stft places it.
+ *   frames  : an item has T = 1 + len / H frames when len > N / 2, and none otherwise (it cannot be reflect-padded).  Sample n of frame t is
+ *             index i = t H - N / 2 + n of the signal, reflected without edge repeat: i < 0 -> -i, i >= len -> 2 (len - 1) - i.
+ *   spectrum: the fp32 N-point DFT of the windowed frame; mag[t][f] = sqrt(max(re^2 + im^2, 1e-7)) for f = 0 .. N / 2.  Frames 2 p and
+ *             2 p + 1 of a signal share one complex transform; both signals of efts_stft_dist pass through the same instructions, so equal
+ *             samples give equal magnitudes.
+ * efts_stft_mag: mag [B][T_max][N / 2 + 1], T_max = 1 + max_len / H; rows at and beyond an item's T are 0.  frames [B] int32: T.
+ * efts_stft_dist: x is the candidate, y the reference signal.  Per item, over its own T (N / 2 + 1) cells:
+ *   sums [B][3] float64: num = sum (mag_y - mag_x)^2, den = sum mag_y^2, l1 = sum |ln mag_y - ln mag_x|;  cells [B] int64: T (N / 2 + 1).
+ *   An item without frames has cells = 0 and sums 0: the device decides, nothing is read back.  From these,
+ *   spectral convergence = sqrt(num) / sqrt(den) and log-magnitude distance = l1 / cells.
+ *   ONE fixed order.  Inside a frame, fp32: with G = 16, 32, 64, 64 lanes for N = 256, 512, 1024, 2048, lane l starts from 0 and takes its
+ *   bins f = l, l + G, l + 2 G, ... in ascending order -- num = fma(d, d, num) with d = mag_y - mag_x, den = fma(mag_y, mag_y, den),
+ *   l1 = l1 + |ln mag_y - ln mag_x| -- and the G lane sums are combined by v = v + (the v of the lane G / 2 across), then G / 4, .., 1
+ *   across.  Across an item's frames: float64, frame 0 first, one addition per frame, by a second launch.  No atomics: an item gives the
+ *   same bits alone, at any batch position, in any run and whatever lies behind its samples.
+ *   workspace: device memory, 16-byte aligned, of the size the workspace-size entry returns (three fp32 per frame: [B][T_max][3]);
+ *   contents afterwards unspecified.  The size entry returns 0 for arguments the call would refuse.
+ * EFTS_EINVAL, nothing launched, the entry's name in efts_last_error(): N other than the four sizes, H or W out of range, B outside
+ * 1 .. 65535, max_len outside 1 .. 2^31 - 8193, a leading dimension below max_len, a workspace too small, a null or misaligned pointer.
+ * ---------------------------------------------------------------------------------- */
+int efts_stft_mag(const void* audio, int32_t pcm16, float pcm_scale, int64_t ld, const int32_t* lengths, int32_t max_len, const float* window,
+                  float* mag, int32_t* frames, int32_t B, int32_t N, int32_t H, int32_t W, void* stream);
+int64_t efts_stft_dist_workspace_bytes(int32_t B, int32_t max_len, int32_t N, int32_t H);
+int efts_stft_dist(const void* x, int32_t x_pcm16, int64_t ldx, const void* y, int32_t y_pcm16, int64_t ldy, float pcm_scale, const int32_t* lengths,
+                   int32_t max_len, const float* window, double* sums, int64_t* cells, void* workspace, int64_t workspace_bytes, int32_t B, int32_t N,
+                   int32_t H, int32_t W, void* stream);
 
 #ifdef __cplusplus
 }
