@@ -35,6 +35,7 @@ import sys
 import numpy as np
 import torch
 
+from efficient_tts_amd.bin._io import read_wav
 from efficient_tts_amd.bin.inference import SAMPLING_RATE, _read_list, build_vocoder, load_acoustic_model
 from efficient_tts_amd.frontend import LogMelFrontend
 from efficient_tts_amd.pitch import PitchTracker, lag_range
@@ -91,16 +92,6 @@ def check_f0_args(args, front=None) -> None:
         lag_range(rate, n_fft, args.f0_min, args.f0_max)
 
 
-def _read_wav(path: str, wav_dir, rate: int) -> torch.Tensor:
-    from scipy.io.wavfile import read
-    if not os.path.exists(path) and wav_dir:
-        path = os.path.join(wav_dir, os.path.basename(path))
-    sr, data = read(path)
-    if sr != rate or data.dtype != np.int16 or data.ndim != 1:
-        raise ValueError(f"{path}: expected mono 16-bit PCM at {rate} Hz")
-    return torch.from_numpy(np.ascontiguousarray(data))
-
-
 def run_score(args) -> float:
     check_f0_args(args)
     if not torch.cuda.is_available():
@@ -127,7 +118,7 @@ def run_score(args) -> float:
     rows, extra, cuts = [], [], []
     for lo in range(0, len(items), bs):
         chunk = items[lo:lo + bs]
-        wavs = [_read_wav(path, wav_dir, rate) for _, _, path in chunk]
+        wavs = [read_wav(path, wav_dir, rate)[0] for _, _, path in chunk]
         audio = torch.nn.utils.rnn.pad_sequence(wavs, batch_first=True)
         ids = torch.nn.utils.rnn.pad_sequence([t for _, t, _ in chunk], batch_first=True)
         wav_len = torch.tensor([w.shape[0] for w in wavs])

@@ -20,9 +20,9 @@ import argparse
 import os
 import sys
 
-import numpy as np
 import torch
 
+from efficient_tts_amd.bin._io import read_wav
 from efficient_tts_amd.trim import SilenceTrimmer
 
 
@@ -47,7 +47,7 @@ def _read_list(path: str):
 
 
 def run_trim(args) -> float:
-    from scipy.io.wavfile import read, write
+    from scipy.io.wavfile import write
     trimmer = SilenceTrimmer(None, frame_length=args.frame_length, hop_size=args.hop_size, top_db=args.top_db, keep_frames=args.keep_frames,
                              peak=args.normalize_peak)
     if not torch.cuda.is_available():
@@ -61,14 +61,8 @@ def run_trim(args) -> float:
         handle.write("id\tsamples\tstart\tnew_samples\tgain\tseconds_removed\n")
         for lo in range(0, len(names), bs):
             chunk = names[lo:lo + bs]
-            wavs, rates = [], []
-            for name in chunk:
-                sr, data = read(os.path.join(args.wav_path, os.path.basename(name)))
-                if data.dtype != np.int16 or data.ndim != 1:
-                    raise ValueError(f"{name}: expected mono 16-bit PCM")
-                wavs.append(torch.from_numpy(np.ascontiguousarray(data)))
-                rates.append(int(sr))
-            audio = torch.nn.utils.rnn.pad_sequence(wavs, batch_first=True).to(device)
+            wavs, rates = zip(*(read_wav(os.path.join(args.wav_path, os.path.basename(name))) for name in chunk))
+            audio = torch.nn.utils.rnn.pad_sequence(list(wavs), batch_first=True).to(device)
             out, new_len, start, gain = trimmer(audio, torch.tensor([w.shape[0] for w in wavs]), return_bounds=True)
             new_len, start, gain = new_len.tolist(), start.tolist(), gain.tolist()
             pcm = torch.round(out * 32768.0).clamp(-32768, 32767).to(torch.int16).cpu().numpy() if args.write_wavs else None

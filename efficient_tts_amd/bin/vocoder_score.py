@@ -88,7 +88,7 @@ def run_score(args):
     if not torch.cuda.is_available():
         raise RuntimeError("no MI355X (gfx950) device visible: efficient_tts_amd has no CPU path")
     from efficient_tts_amd.bin.inference import build_vocoder
-    from efficient_tts_amd.bin.score import _read_wav
+    from efficient_tts_amd.bin._io import read_wav
     from efficient_tts_amd.frontend import LogMelFrontend
     from efficient_tts_amd.stft import MultiResolutionSTFTDistance
     device = torch.device("cuda")
@@ -100,7 +100,7 @@ def run_score(args):
     rows = []
     for lo in range(0, len(items), args.batch_size):
         chunk = items[lo:lo + args.batch_size]
-        wavs = [_read_wav(path, args.wav_path, SAMPLING_RATE) for _, path in chunk]
+        wavs = [read_wav(path, args.wav_path, SAMPLING_RATE)[0] for _, path in chunk]
         audio = torch.nn.utils.rnn.pad_sequence(wavs, batch_first=True).to(device)
         wav_len = torch.tensor([w.shape[0] for w in wavs], device=device)
         with torch.no_grad():

@@ -20,6 +20,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
+from . import audio_args as A
 from . import lib as L
 from . import ops as O
 from .ops import F32Rows, PackedWeight, Plane, Rows
@@ -114,7 +115,7 @@ class LogMelFrontend:
             with O.stream_scope():
                 self.dft = PackedWeight(M, M, 1, 2, self.dev)
                 self.dft.pack(torch.from_numpy(dft).to(self.dev).contiguous())
-        self._ws = {}
+        self._ws = A.Cache(capacity=5)
         self._pins = {}
 
     _RING = 8
@@ -159,35 +160,19 @@ class LogMelFrontend:
             audio = audio.to(self.dev, torch.float32).contiguous()
         # host side of a call: the checks on plain ints, ONE small host-to-device copy (lengths and frame counts together), one output allocation
         # (three CPU-tensor reductions and three copies took 60 us per call -- as long as the fused launch itself)
-        lh = lengths.detach().to("cpu", torch.int64).tolist()
-        if min(lh) <= (self.n_fft - self.hop) // 2:
-            raise ValueError("every item must be longer than the reflect padding (n_fft - hop) / 2")
-        if max(lh) > audio.shape[1]:
-            raise ValueError("lengths exceed the audio buffer")
-        fh = [l // self.hop for l in lh]
-        T = max(fh) if max_frames is None else int(max_frames)
+        lh, fh, T = A.frame_counts(lengths, audio.shape[1], self.hop, (self.n_fft - self.hop) // 2, max_frames=max_frames)
         both = self._to_device_async(lh, fh)
         li, fi = both[0], both[1]
         frames_d = fi.to(torch.int64)
         if self.radix == 0:
             out = torch.empty(B, T, self.n_mels, dtype=torch.float32, device=self.dev)
+            fn, name, scale = A.pcm_entry(L.load(), "efts_logmel_fft", audio, self.max_wav_value)
             with O.stream_scope():
-                if pcm16:
-                    L.check(L.load().efts_logmel_fft_pcm16(audio.data_ptr(), audio.shape[1], 1.0 / self.max_wav_value, li.data_ptr(), self.window.data_ptr(),
-                                                           self.basis.data_ptr(), self.ranges.data_ptr(), out.data_ptr(), B, T, self.n_fft, self.hop, self.n_mels,
-                                                           O._stream()), "efts_logmel_fft_pcm16")
-                else:
-                    L.check(L.load().efts_logmel_fft(audio.data_ptr(), audio.shape[1], li.data_ptr(), self.window.data_ptr(), self.basis.data_ptr(),
-                                                     self.ranges.data_ptr(), out.data_ptr(), B, T, self.n_fft, self.hop, self.n_mels, O._stream()),
-                            "efts_logmel_fft")
+                L.check(fn(audio.data_ptr(), audio.shape[1], *scale, li.data_ptr(), self.window.data_ptr(), self.basis.data_ptr(), self.ranges.data_ptr(),
+                           out.data_ptr(), B, T, self.n_fft, self.hop, self.n_mels, O._stream()), name)
             return out, frames_d
         rs = Rows(B, T)
-        key = (B, T)
-        if key not in self._ws:
-            if len(self._ws) > 4:
-                self._ws.pop(next(iter(self._ws)))
-            self._ws[key] = (Plane.for_rows(rs, self.n_fft, 2, self.dev), F32Rows(rs, self.ld_spec, self.dev))
-        fr, spec = self._ws[key]
+        fr, spec = self._ws.get((B, T), lambda: (Plane.for_rows(rs, self.n_fft, 2, self.dev), F32Rows(rs, self.ld_spec, self.dev)))
         out = torch.empty(B, T, self.n_mels, dtype=torch.float32, device=self.dev)
         lib = L.load()
         with O.stream_scope():

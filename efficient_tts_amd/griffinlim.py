@@ -29,6 +29,7 @@ import torch
 
 from . import lib as L
 from . import ops as O
+from .audio_args import Cache
 from .frontend import slaney_mel_filterbank
 from .graphs import GraphCache
 from .ops import F32Rows, PackedWeight, Plane, Rows
@@ -72,7 +73,7 @@ class GriffinLimVocoder(torch.nn.Module):
         self.graphs = graphs
         self._pinv_host = torch.from_numpy(mel_pseudo_inverse(sampling_rate, n_fft, num_mels, fmin, fmax).astype(np.float32)).contiguous()
         self._state = {}                 # device -> (packed pinv, window)
-        self._ws = {}                    # (device, B, T) -> buffers
+        self._ws = Cache(capacity=5)     # (device, B, T) -> buffers
         self._graph_cache = GraphCache(capacity=8)
 
     # ------------------------------------------------------------------ device state
@@ -86,17 +87,14 @@ class GriffinLimVocoder(torch.nn.Module):
         return self._state[dev]
 
     def _workspace_for(self, B: int, T: int, dev) -> dict:
-        key = (dev, B, T)
-        if key not in self._ws:
-            if len(self._ws) > 4:
-                self._ws.pop(next(iter(self._ws)))
+        def make():
             rs = Rows(B, T)
-            self._ws[key] = dict(
+            return dict(
                 rs=rs, mel=Plane.for_rows(rs, self.num_mels, self.split, dev), lin=F32Rows(rs, O.roundup(self.n_bins, 4), dev),
                 spec=torch.zeros(B, T, self.n_bins, 2, dtype=torch.float32, device=dev),
                 prev=torch.zeros(B, T, self.n_bins, 2, dtype=torch.float32, device=dev),
                 wframes=torch.zeros(B, T, self.n_fft, dtype=torch.float32, device=dev))
-        return self._ws[key]
+        return self._ws.get((dev, B, T), make)
 
     def _check_input(self, x: torch.Tensor) -> None:
         if x.dim() != 3 or x.shape[1] != self.num_mels:

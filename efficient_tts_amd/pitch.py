@@ -31,6 +31,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from . import audio_args as A
 from . import lib as L
 from . import ops as O
 
@@ -53,7 +54,7 @@ MAX_COST = 16.0                                                # efts_f0_viterbi
 MAX_LAG = 1024                                                 # EFTS_VITERBI_MAX_LAG
 
 _lg_tables: Dict[tuple, torch.Tensor] = {}
-_workspaces: Dict[tuple, torch.Tensor] = {}                    # the back-pointers of the smoother, per (device, B, T, tau_min, tau_max)
+_workspaces = A.Cache(capacity=5)                              # the back-pointers of the smoother, per (device, B, T, tau_min, tau_max)
 
 
 def log2_table(tau_max: int) -> torch.Tensor:
@@ -93,14 +94,6 @@ class ViterbiSmoother:
             _lg_tables[key] = log2_table(self.tau_max).to(self.dev)
         self.lg = _lg_tables[key]
 
-    def _workspace(self, B: int, T: int) -> torch.Tensor:
-        key = (self.dev, B, T, self.tau_min, self.tau_max)
-        if key not in _workspaces:
-            if len(_workspaces) > 4:
-                _workspaces.pop(next(iter(_workspaces)))
-            _workspaces[key] = torch.empty(B * int(L.load().efts_f0_viterbi_workspace_bytes(T, self.tau_min, self.tau_max)), dtype=torch.uint8, device=self.dev)
-        return _workspaces[key]
-
     @torch.no_grad()
     def __call__(self, cmnd: torch.Tensor, frames: torch.Tensor):
         if cmnd.dim() != 3 or cmnd.dtype != torch.float32 or cmnd.shape[0] < 1 or cmnd.shape[1] < 1 or cmnd.shape[2] != self.tau_max + 1:
@@ -114,9 +107,10 @@ class ViterbiSmoother:
             cmnd = cmnd.contiguous()
         fr = frames.to(device=cmnd.device, dtype=torch.int32)
         lib = L.load()
-        if lib.efts_f0_viterbi_workspace_bytes(T, self.tau_min, self.tau_max) <= 0:
+        need = int(lib.efts_f0_viterbi_workspace_bytes(T, self.tau_min, self.tau_max))
+        if need <= 0:
             raise ValueError(f"ViterbiSmoother: {T} frames are more than one call takes")
-        ws = self._workspace(B, T)
+        ws = _workspaces.get((self.dev, B, T, self.tau_min, self.tau_max), lambda: torch.empty(B * need, dtype=torch.uint8, device=self.dev))
         f0 = torch.empty(B, T, dtype=torch.float32, device=cmnd.device)
         ap = torch.empty(B, T, dtype=torch.float32, device=cmnd.device)
         lag = torch.empty(B, T, dtype=torch.int32, device=cmnd.device)
@@ -147,12 +141,13 @@ class PitchTracker:
             raise ValueError(f"n_fft must be one of {N_FFTS}")
         if not 1 <= hop_size <= n_fft or (n_fft - hop_size) % 2:
             raise ValueError("hop_size must lie in 1 .. n_fft with n_fft - hop_size even")
-        if not threshold > 0 or not max_wav_value > 0:
-            raise ValueError("threshold and max_wav_value must be > 0")
+        if not threshold > 0:
+            raise ValueError("threshold must be > 0")
+        self.max_wav_value = A.max_wav(max_wav_value)
         self.tau_min, self.tau_max = lag_range(int(sampling_rate), n_fft, fmin, fmax)
         self.dev = torch.device(device)
         self.sr, self.n_fft, self.hop, self.pad = int(sampling_rate), int(n_fft), int(hop_size), (n_fft - hop_size) // 2
-        self.fmin, self.fmax, self.threshold, self.max_wav_value = float(fmin), float(fmax), float(threshold), float(max_wav_value)
+        self.fmin, self.fmax, self.threshold = float(fmin), float(fmax), float(threshold)
         L.load()
         L.require_device()
         self.smoother = ViterbiSmoother(self.dev, self.sr, self.tau_min, self.tau_max, unvoiced_cost, octave_cost, jump_cost, vuv_cost) if smooth else None
@@ -162,32 +157,19 @@ class PitchTracker:
 
     @torch.no_grad()
     def __call__(self, audio: torch.Tensor, lengths: torch.Tensor, max_frames: Optional[int] = None, return_cmnd: bool = False, short_ok: bool = False):
-        if audio.dim() != 2 or audio.dtype not in (torch.float32, torch.int16):
-            raise ValueError("audio must be [B, L], float32 or int16")
+        audio = A.signal(audio.to(self.dev), "audio", "efficient_tts_amd.pitch")
         B = audio.shape[0]
         if lengths.shape != (B,):
             raise ValueError("lengths must be [B]")
-        audio = audio.to(self.dev).contiguous()
-        lh = lengths.detach().to("cpu", torch.int64).tolist()                       # the one host copy: the checks run on plain ints
-        if max(lh) > audio.shape[1]:
-            raise ValueError("lengths exceed the audio buffer")
-        if min(lh) <= self.pad and not short_ok:
-            raise ValueError("every item must be longer than the reflect padding (n_fft - hop) / 2")
-        fh = [l // self.hop if l > self.pad else 0 for l in lh]
-        T = max(max(fh), 1) if max_frames is None else int(max_frames)
-        if T < 1:
-            raise ValueError("max_frames must be >= 1")
+        lh, fh, T = A.frame_counts(lengths, audio.shape[1], self.hop, self.pad, short_ok, max_frames)   # the one host copy: the checks run on plain ints
         both = torch.tensor([lh, fh], dtype=torch.int32).to(self.dev, non_blocking=True)
         f0 = torch.empty(B, T, dtype=torch.float32, device=self.dev)
         ap = torch.empty(B, T, dtype=torch.float32, device=self.dev)
         cmnd = torch.empty(B, T, self.tau_max + 1, dtype=torch.float32, device=self.dev) if return_cmnd or self.smoother else None
-        lib = L.load()
-        tail = (f0.data_ptr(), ap.data_ptr(), O._p(cmnd), B, T, self.n_fft, self.hop, self.sr, self.fmin, self.fmax, self.threshold)
+        fn, name, scale = A.pcm_entry(L.load(), "efts_yin", audio, self.max_wav_value)
         with O.stream_scope():
-            if audio.dtype == torch.int16:
-                L.check(lib.efts_yin_pcm16(audio.data_ptr(), audio.shape[1], 1.0 / self.max_wav_value, both[0].data_ptr(), *tail, O._stream()), "efts_yin_pcm16")
-            else:
-                L.check(lib.efts_yin(audio.data_ptr(), audio.shape[1], both[0].data_ptr(), *tail, O._stream()), "efts_yin")
+            L.check(fn(audio.data_ptr(), audio.shape[1], *scale, both[0].data_ptr(), f0.data_ptr(), ap.data_ptr(), O._p(cmnd), B, T, self.n_fft, self.hop,
+                       self.sr, self.fmin, self.fmax, self.threshold, O._stream()), name)
         if self.smoother is not None:
             f0, ap, _ = self.smoother(cmnd, both[1])
         frames = both[1].to(torch.int64)

@@ -21,6 +21,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
+from . import audio_args as A
 from . import lib as L_
 from . import ops as O
 
@@ -29,7 +30,7 @@ TABLE_MAX_BYTES = 4 << 20
 
 
 def _rate(value, name: str) -> int:
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value <= 0:
+    if A.as_int(value, name) <= 0:
         raise ValueError(f"{name} must be a positive integer (Hz), got {value!r}")
     return int(value)
 
@@ -100,35 +101,20 @@ class Resampler(torch.nn.Module):
 
     @torch.no_grad()
     def forward(self, audio: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        if audio.dim() != 2 or audio.dtype not in (torch.float32, torch.int16):
-            raise ValueError("expected audio [B, n], float32 or int16")
+        audio = A.signal(audio, "audio", None if self.identity else "Resampler")         # (the identity has no launch and takes host tensors too)
         B, n = audio.shape
-        if B < 1 or n < 1:
-            raise ValueError("empty batch or no samples")
-        if lengths is None:
-            lens = torch.full((B,), n, dtype=torch.int64, device=audio.device)
-        else:
-            if lengths.shape != (B,):
-                raise ValueError("lengths must be [B]")
-            lens = lengths.to(device=audio.device, dtype=torch.int64).clamp(0, n)
+        dev = audio.device
+        li = A.device_lengths(lengths, B, n, dev)
         if self.identity:
-            return (audio if audio.dtype == torch.float32 else audio.to(torch.float32) * (1.0 / self.max_wav_value)), lens
-        if not audio.is_cuda:
-            raise RuntimeError("Resampler runs on an MI355X device only (no CPU path)")
+            return (audio if audio.dtype == torch.float32 else audio.to(torch.float32) * (1.0 / self.max_wav_value)), li.to(torch.int64)
         lib = L_.load()
         L_.require_device()
-        dev = audio.device
-        audio = audio.contiguous()
         n_out = self.out_length(n)
         out = torch.empty(B, n_out, dtype=torch.float32, device=dev)
         out_lens = torch.empty(B, dtype=torch.int32, device=dev)
-        li = lens.to(torch.int32)
         table = self._table(dev)
+        fn, name, scale = A.pcm_entry(lib, "efts_resample", audio, self.max_wav_value)
         with O.stream_scope():
-            if audio.dtype == torch.int16:
-                L_.check(lib.efts_resample_pcm16(audio.data_ptr(), n, 1.0 / self.max_wav_value, li.data_ptr(), table.data_ptr(), self.L, self.M, self.W,
-                                                 out.data_ptr(), n_out, out_lens.data_ptr(), B, O._stream()), "efts_resample_pcm16")
-            else:
-                L_.check(lib.efts_resample(audio.data_ptr(), n, li.data_ptr(), table.data_ptr(), self.L, self.M, self.W, out.data_ptr(), n_out,
-                                           out_lens.data_ptr(), B, O._stream()), "efts_resample")
+            L_.check(fn(audio.data_ptr(), n, *scale, li.data_ptr(), table.data_ptr(), self.L, self.M, self.W, out.data_ptr(), n_out,
+                        out_lens.data_ptr(), B, O._stream()), name)
         return out, out_lens.to(torch.int64)

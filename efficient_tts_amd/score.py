@@ -29,12 +29,13 @@ import torch
 
 from . import lib as L_
 from . import ops as O
+from .audio_args import Cache
 
 MCD_DB = 10.0 * math.sqrt(2.0) / math.log(10.0)
 MAX_MELS, MAX_COEF = 128, 32                                      # limits of efts_mel_cepstrum (include/efts_abi.h)
 
 _tables: Dict[tuple, torch.Tensor] = {}
-_workspaces: Dict[tuple, torch.Tensor] = {}                        # the move record of dtw_path, per (device, B, Tx, Ty)
+_workspaces = Cache(capacity=5)                                    # the move record of dtw_path, per (device, B, Tx, Ty)
 
 
 def dct_table(n_mels: int, n_coef: int) -> torch.Tensor:
@@ -110,15 +111,6 @@ def dtw(x: torch.Tensor, x_lengths: torch.Tensor, y: torch.Tensor, y_lengths: to
     return cost, path_len
 
 
-def _workspace(dev: torch.device, B: int, Tx: int, Ty: int) -> torch.Tensor:
-    key = (dev, B, Tx, Ty)
-    if key not in _workspaces:
-        if len(_workspaces) > 4:
-            _workspaces.pop(next(iter(_workspaces)))
-        _workspaces[key] = torch.empty(B * int(L_.load().efts_dtw_path_workspace_bytes(Tx, Ty)), dtype=torch.uint8, device=dev)
-    return _workspaces[key]
-
-
 @torch.no_grad()
 def dtw_path(x: torch.Tensor, x_lengths: torch.Tensor, y: torch.Tensor, y_lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(cost [B] fp32, path_len [B] int32, path [B, Tx + Ty - 1, 2] int32): `dtw`'s cost and path_len, bit for bit, and the path itself.
@@ -133,9 +125,10 @@ def dtw_path(x: torch.Tensor, x_lengths: torch.Tensor, y: torch.Tensor, y_length
     Ty = y.shape[1]
     lib = L_.load()
     L_.require_device()
-    if lib.efts_dtw_path_workspace_bytes(Tx, Ty) <= 0:
+    need = int(lib.efts_dtw_path_workspace_bytes(Tx, Ty))
+    if need <= 0:
         raise ValueError(f"dtw_path: Tx and Ty must be 1 .. 8192 frames (got {Tx}, {Ty})")
-    ws = _workspace(x.device, B, Tx, Ty)
+    ws = _workspaces.get((x.device, B, Tx, Ty), lambda: torch.empty(B * need, dtype=torch.uint8, device=x.device))
     cost = torch.empty(B, dtype=torch.float32, device=x.device)
     path_len = torch.empty(B, dtype=torch.int32, device=x.device)
     path = torch.empty(B, Tx + Ty - 1, 2, dtype=torch.int32, device=x.device)

@@ -22,6 +22,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import audio_args as A
 from . import lib as L_
 from . import ops as O
 
@@ -29,14 +30,8 @@ FFT_SIZES = (256, 512, 1024, 2048)
 DEFAULT_RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))      # stft_loss.py:113-116
 
 
-def _int(value, name: str) -> int:
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
-        raise ValueError(f"{name} must be an integer, got {value!r}")
-    return int(value)
-
-
 def check_resolution(n_fft, hop_size, win_length) -> Tuple[int, int, int]:
-    n, h, w = _int(n_fft, "n_fft"), _int(hop_size, "hop_size"), _int(win_length, "win_length")
+    n, h, w = A.as_int(n_fft, "n_fft"), A.as_int(hop_size, "hop_size"), A.as_int(win_length, "win_length")
     if n not in FFT_SIZES:
         raise ValueError(f"n_fft must be one of {FFT_SIZES}, got {n_fft!r}")
     if not 1 <= h <= n:
@@ -57,24 +52,6 @@ def frame_count(length: int, n_fft: int, hop_size: int) -> int:
     return 1 + length // hop_size if length > n_fft // 2 else 0
 
 
-def _signal(t: torch.Tensor, name: str) -> torch.Tensor:
-    if t.dim() != 2 or t.dtype not in (torch.float32, torch.int16):
-        raise ValueError(f"expected {name} [B, n], float32 or int16")
-    if t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{name}: empty batch or no samples")
-    if not t.is_cuda:
-        raise RuntimeError("the STFT ops run on an MI355X device only (no CPU path)")
-    return t.contiguous()
-
-
-def _lengths(lengths: Optional[torch.Tensor], B: int, n: int, dev) -> torch.Tensor:
-    if lengths is None:
-        return torch.full((B,), n, dtype=torch.int32, device=dev)
-    if lengths.shape != (B,):
-        raise ValueError("lengths must be [B]")
-    return lengths.to(device=dev, dtype=torch.int64).clamp(0, n).to(torch.int32)
-
-
 class STFTMagnitude(torch.nn.Module):
     """mag, frames = STFTMagnitude(device, n_fft, hop_size, win_length)(audio [B, n] float32 | int16, lengths=None)
 
@@ -85,9 +62,7 @@ class STFTMagnitude(torch.nn.Module):
         super().__init__()
         self.dev = None if device is None else torch.device(device)
         self.n_fft, self.hop, self.win_length = check_resolution(n_fft, hop_size, win_length)
-        self.max_wav_value = float(max_wav_value)
-        if not self.max_wav_value > 0.0:
-            raise ValueError(f"max_wav_value must be > 0, got {max_wav_value!r}")
+        self.max_wav_value = A.max_wav(max_wav_value)
         self._window = {}                # device -> window
 
     def _win(self, dev) -> torch.Tensor:
@@ -97,12 +72,12 @@ class STFTMagnitude(torch.nn.Module):
 
     @torch.no_grad()
     def forward(self, audio: torch.Tensor, lengths: Optional[torch.Tensor] = None):
-        audio = _signal(audio, "audio")
+        audio = A.signal(audio, "audio", "efficient_tts_amd.stft")
         B, n = audio.shape
         lib = L_.load()
         L_.require_device()
         dev = audio.device
-        li = _lengths(lengths, B, n, dev)
+        li = A.device_lengths(lengths, B, n, dev)
         T = 1 + n // self.hop
         mag = torch.empty(B, T, self.n_fft // 2 + 1, dtype=torch.float32, device=dev)
         frames = torch.empty(B, dtype=torch.int32, device=dev)
@@ -127,40 +102,30 @@ class MultiResolutionSTFTDistance(torch.nn.Module):
         self.resolutions = tuple(check_resolution(*r) for r in resolutions)
         if not self.resolutions:
             raise ValueError("at least one resolution")
-        self.max_wav_value = float(max_wav_value)
-        if not self.max_wav_value > 0.0:
-            raise ValueError(f"max_wav_value must be > 0, got {max_wav_value!r}")
+        self.max_wav_value = A.max_wav(max_wav_value)
         self._window = {}                # (device, W) -> window
-        self._ws = {}                    # (device, B, n) -> one workspace, large enough for every resolution
+        self._ws = A.Cache(capacity=5)   # (device, B, n) -> one workspace, large enough for every resolution
 
     def _win(self, dev, w: int) -> torch.Tensor:
         if (dev, w) not in self._window:
             self._window[(dev, w)] = torch.from_numpy(hann_window(w)).to(dev)
         return self._window[(dev, w)]
 
-    def _workspace(self, lib, dev, B: int, n: int) -> torch.Tensor:
-        key = (dev, B, n)
-        if key not in self._ws:
-            if len(self._ws) > 4:
-                self._ws.pop(next(iter(self._ws)))
-            need = max(int(lib.efts_stft_dist_workspace_bytes(B, n, N, H)) for N, H, _ in self.resolutions)
-            self._ws[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-        return self._ws[key]
-
     @torch.no_grad()
     def forward(self, x: torch.Tensor, y: torch.Tensor, lengths: Optional[torch.Tensor] = None):
-        x, y = _signal(x, "x"), _signal(y, "y")
+        x, y = A.signal(x, "x", "efficient_tts_amd.stft"), A.signal(y, "y", "efficient_tts_amd.stft")
         if x.shape[0] != y.shape[0] or x.device != y.device:
             raise ValueError("x and y must hold the same number of items on the same device")
         B, n = x.shape[0], min(x.shape[1], y.shape[1])
         lib = L_.load()
         L_.require_device()
         dev = x.device
-        li = _lengths(lengths, B, n, dev)
+        li = A.device_lengths(lengths, B, n, dev)
         R = len(self.resolutions)
         sums = torch.empty(R, B, 3, dtype=torch.float64, device=dev)
         cells = torch.empty(R, B, dtype=torch.int64, device=dev)
-        ws = self._workspace(lib, dev, B, n)
+        ws = self._ws.get((dev, B, n), lambda: torch.empty(max(int(lib.efts_stft_dist_workspace_bytes(B, n, N, H)) for N, H, _ in self.resolutions),
+                                                           dtype=torch.uint8, device=dev))
         with O.stream_scope():
             for r, (N, H, W) in enumerate(self.resolutions):
                 L_.check(lib.efts_stft_dist(x.data_ptr(), int(x.dtype == torch.int16), x.shape[1], y.data_ptr(), int(y.dtype == torch.int16), y.shape[1],

@@ -20,16 +20,11 @@ from typing import Optional
 import numpy as np
 import torch
 
+from . import audio_args as A
 from . import lib as L_
 from . import ops as O
 
 FRAME_LENGTHS = (512, 1024, 2048)
-
-
-def _int(value, name: str) -> int:
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
-        raise ValueError(f"{name} must be an integer, got {value!r}")
-    return int(value)
 
 
 class SilenceTrimmer(torch.nn.Module):
@@ -45,7 +40,7 @@ class SilenceTrimmer(torch.nn.Module):
                  peak: Optional[float] = None, max_wav_value: float = 32768.0, trim: bool = True):
         super().__init__()
         self.dev = None if device is None else torch.device(device)
-        self.frame_length, self.hop = _int(frame_length, "frame_length"), _int(hop_size, "hop_size")
+        self.frame_length, self.hop = A.as_int(frame_length, "frame_length"), A.as_int(hop_size, "hop_size")
         if self.frame_length not in FRAME_LENGTHS:
             raise ValueError(f"frame_length must be one of {FRAME_LENGTHS}, got {frame_length!r}")
         if not 1 <= self.hop <= self.frame_length or (self.frame_length - self.hop) % 2:
@@ -53,63 +48,39 @@ class SilenceTrimmer(torch.nn.Module):
         self.top_db = float(top_db)
         if not self.top_db > 0.0 or not np.isfinite(self.top_db):
             raise ValueError(f"top_db must be > 0, got {top_db!r}")
-        self.keep_frames = _int(keep_frames, "keep_frames")
+        self.keep_frames = A.as_int(keep_frames, "keep_frames")
         if self.keep_frames < 0:
             raise ValueError(f"keep_frames must be >= 0, got {keep_frames!r}")
         if peak is not None and not 0.0 < float(peak) <= 1.0:
             raise ValueError(f"peak must be None or lie in (0, 1], got {peak!r}")
         self.peak = None if peak is None else float(peak)
-        self.max_wav_value = float(max_wav_value)
-        if not self.max_wav_value > 0.0:
-            raise ValueError(f"max_wav_value must be > 0, got {max_wav_value!r}")
+        self.max_wav_value = A.max_wav(max_wav_value)
         self.trim = bool(trim)
         self.ratio = float(10.0 ** (np.float64(self.top_db) / 10.0))        # r, float64, once
         if not self.ratio > 1.0 or not np.isfinite(self.ratio):
             raise ValueError(f"top_db {top_db!r} gives no usable threshold ratio")
-        self._ws = {}                    # (device, B, n, int16?) -> workspace
-
-    def _workspace(self, lib, dev, B: int, n: int, pcm16: bool) -> torch.Tensor:
-        key = (dev, B, n, pcm16)
-        if key not in self._ws:
-            if len(self._ws) > 4:
-                self._ws.pop(next(iter(self._ws)))
-            self._ws[key] = torch.empty(int(lib.efts_trim_workspace_bytes(B, n, self.hop, int(pcm16))), dtype=torch.uint8, device=dev)
-        return self._ws[key]
+        self._ws = A.Cache(capacity=5)   # (device, B, n, int16?) -> workspace
 
     @torch.no_grad()
     def forward(self, audio: torch.Tensor, lengths: Optional[torch.Tensor] = None, return_bounds: bool = False):
-        if audio.dim() != 2 or audio.dtype not in (torch.float32, torch.int16):
-            raise ValueError("expected audio [B, n], float32 or int16")
+        audio = A.signal(audio, "audio", "SilenceTrimmer")
         B, n = audio.shape
-        if B < 1 or n < 1:
-            raise ValueError("empty batch or no samples")
-        if lengths is not None and lengths.shape != (B,):
-            raise ValueError("lengths must be [B]")
-        if not audio.is_cuda:
-            raise RuntimeError("SilenceTrimmer runs on an MI355X device only (no CPU path)")
         lib = L_.load()
         L_.require_device()
         dev = audio.device
-        audio = audio.contiguous()
-        if lengths is None:
-            li = torch.full((B,), n, dtype=torch.int32, device=dev)
-        else:
-            li = lengths.to(device=dev, dtype=torch.int64).clamp(0, n).to(torch.int32)
+        li = A.device_lengths(lengths, B, n, dev)
         pcm16 = audio.dtype == torch.int16
         out = torch.empty(B, n, dtype=torch.float32, device=dev)
         res = torch.empty(2, B, dtype=torch.int32, device=dev)           # new_len, start
         gains = torch.empty(B, dtype=torch.float32, device=dev)
-        ws = self._workspace(lib, dev, B, n, pcm16)
+        ws = self._ws.get((dev, B, n, pcm16),
+                          lambda: torch.empty(int(lib.efts_trim_workspace_bytes(B, n, self.hop, int(pcm16))), dtype=torch.uint8, device=dev))
         keep = self.keep_frames if self.trim else -1
         peak = self.peak if self.peak is not None else 0.0
+        fn, name, scale = A.pcm_entry(lib, "efts_trim", audio, self.max_wav_value)
         with O.stream_scope():
-            if pcm16:
-                L_.check(lib.efts_trim_pcm16(audio.data_ptr(), n, li.data_ptr(), self.frame_length, self.hop, self.ratio, keep, peak,
-                                             1.0 / self.max_wav_value, out.data_ptr(), n, res[0].data_ptr(), res[1].data_ptr(), gains.data_ptr(),
-                                             ws.data_ptr(), B, O._stream()), "efts_trim_pcm16")
-            else:
-                L_.check(lib.efts_trim(audio.data_ptr(), n, li.data_ptr(), self.frame_length, self.hop, self.ratio, keep, peak, out.data_ptr(), n,
-                                       res[0].data_ptr(), res[1].data_ptr(), gains.data_ptr(), ws.data_ptr(), B, O._stream()), "efts_trim")
+            L_.check(fn(audio.data_ptr(), n, li.data_ptr(), self.frame_length, self.hop, self.ratio, keep, peak, *scale, out.data_ptr(), n,
+                        res[0].data_ptr(), res[1].data_ptr(), gains.data_ptr(), ws.data_ptr(), B, O._stream()), name)
         out_lengths = res[0].to(torch.int64)
         if return_bounds:
             return out, out_lengths, res[1].to(torch.int64), gains

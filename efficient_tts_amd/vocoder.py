@@ -38,6 +38,7 @@ from torch.nn.utils import remove_weight_norm, weight_norm
 
 from . import lib as L
 from . import ops as O
+from .audio_args import Cache
 from .ops import PackedWeight, Plane
 
 LRELU_SLOPE = 0.1
@@ -147,7 +148,7 @@ class HiFiGANGenerator(nn.Module):
         self._packed: Optional[Dict[str, PackedWeight]] = None
         self._packed_dev = None
         self._bias: Dict[str, torch.Tensor] = {}
-        self._bufs: Dict[int, dict] = {}
+        self._bufs = Cache(capacity=3)          # (B, T) -> workspace
         # per-shape hipGraph of the ~85 launches of a call (round 6; efficient_tts_amd/graphs.py, the acoustic model's cache): one utterance is
         # 2 ms of device work issued by a host that needs about as long for the launches; `graphs = False`: every launch issued eagerly
         self.graphs = True
@@ -212,11 +213,9 @@ class HiFiGANGenerator(nn.Module):
 
     # ------------------------------------------------------------------ buffers per mel length
     def _workspace_for(self, B: int, T: int, dev) -> dict:
-        key = (B, T)
-        if key in self._bufs:
-            return self._bufs[key]
-        if len(self._bufs) > 2:
-            self._bufs.pop(next(iter(self._bufs)))
+        return self._bufs.get((B, T), lambda: self._make_workspace(B, T, dev))
+
+    def _make_workspace(self, B: int, T: int, dev) -> dict:
         sp = self.split
         pitch = T + self.gap_frames                                            # rows per item at mel rate
         rows = B * pitch
@@ -234,7 +233,6 @@ class HiFiGANGenerator(nn.Module):
             rows = n_i
         b["mask_mel"] = torch.zeros(B * pitch + 1, dtype=torch.float32, device=dev)
         b["out"] = torch.zeros(rows + 256, 1, dtype=torch.float32, device=dev)
-        self._bufs[key] = b
         return b
 
     def _branch_streams(self, dev, count: int):
