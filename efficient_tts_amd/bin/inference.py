@@ -21,7 +21,10 @@ HiFi-GAN V1 generator (efficient_tts_amd.vocoder).  Differences from the referen
     output is converted on the device (efficient_tts_amd.resample) in front of the 16-bit quantisation;
   * `--write_f0` writes the pitch contour of every utterance next to its wav (<id>_<step>.f0.txt: frame index, time in seconds, f0 in Hz with 0 for an
     unvoiced frame), tracked on the device from the vocoder's output (efficient_tts_amd.pitch) on the mel frames' grid;
-    `--f0_smooth` decides the frames of an utterance together (the tracker's Viterbi path over all lags) instead of one by one.
+    `--f0_smooth` decides the frames of an utterance together (the tracker's Viterbi path over all lags) instead of one by one;
+  * `--loudness L [--loudness_peak_ceiling 0.99]` brings every utterance to an integrated loudness of L LUFS (ITU-R BS.1770, for example -23)
+    on the device (efficient_tts_amd.loudness), behind the vocoder and in front of the optional rate conversion; a gain that would take the
+    peak over the ceiling is cut back.  Without the flag the wav files are byte for byte what they were.
 """
 from __future__ import annotations
 
@@ -38,6 +41,7 @@ import yaml
 
 from efficient_tts_amd import models
 from efficient_tts_amd.griffinlim import GriffinLimVocoder
+from efficient_tts_amd.loudness import LoudnessNormalizer
 from efficient_tts_amd.pitch import PitchTracker
 from efficient_tts_amd.resample import QUALITIES, Resampler
 from efficient_tts_amd.vocoder import HiFiGANGenerator, load_hifigan_generator
@@ -71,6 +75,9 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--write_f0", action="store_true",
                    help="also write <id>_<step>.f0.txt: frame index, time in seconds, f0 in Hz (0: unvoiced) of the vocoder's output")
     p.add_argument("--f0_smooth", action="store_true", help="--write_f0: smooth the contour across frames (the cheapest path over the lags of all frames)")
+    p.add_argument("--loudness", type=float, default=None,
+                   help="bring every utterance to this integrated loudness in LUFS (ITU-R BS.1770), for example -23 (default: leave the level)")
+    p.add_argument("--loudness_peak_ceiling", type=float, default=0.99, help="--loudness: no sample may exceed this (default 0.99; <= 0: no ceiling)")
     p.add_argument("--verbose", type=int, default=1)
     return p
 
@@ -148,8 +155,19 @@ def check_f0_smooth(args) -> None:
         raise ValueError("--f0_smooth smooths the contour that --write_f0 writes: give --write_f0 as well")
 
 
+def build_loudness(args, device=None):
+    """the LoudnessNormalizer for the vocoder's output, or None without --loudness (checked on the host, before anything is loaded)"""
+    if args.loudness is None:
+        return None
+    if args.no_vocoder:
+        raise ValueError("--loudness sets the level of the vocoder's output: it cannot be combined with --no_vocoder")
+    ceiling = args.loudness_peak_ceiling
+    return LoudnessNormalizer(device, SAMPLING_RATE, target_lufs=args.loudness, peak_ceiling=ceiling if ceiling > 0 else None)
+
+
 def run_tts(args) -> float:
     check_f0_smooth(args)
+    build_loudness(args)
     level = {0: logging.WARNING, 1: logging.INFO}.get(args.verbose, logging.DEBUG)
     logging.basicConfig(level=level, stream=sys.stdout, force=True, format="%(asctime)s %(levelname)s %(name)s:%(lineno)d  %(message)s")
     if not torch.cuda.is_available():
@@ -174,6 +192,7 @@ def run_tts(args) -> float:
         raise ValueError("--write_f0 tracks the vocoder's output: it cannot be combined with --no_vocoder")
     vocoder = None if args.no_vocoder else build_vocoder(args, device)
     tracker = PitchTracker(device, sampling_rate=SAMPLING_RATE, n_fft=1024, hop_size=256, smooth=args.f0_smooth) if args.write_f0 else None
+    loudness = build_loudness(args, device)
     resampler = None
     if vocoder is not None and out_rate != SAMPLING_RATE:
         resampler = Resampler(device, SAMPLING_RATE, out_rate, quality=args.resample_quality)
@@ -202,11 +221,15 @@ def run_tts(args) -> float:
                 outs = mels
             elif len(chunk) == 1:
                 outs = raw = [vocoder(mels[0].t()[None].contiguous())[0, 0]]
+                if loudness is not None:
+                    outs = [loudness(outs[0][None].float())[0]]
                 if resampler is not None:
                     outs = [resampler(outs[0][None].float())[0][0]]
             else:                                       # one batched generator pass; every item equals its single-utterance result
                 audio = vocoder(mel.transpose(1, 2).contiguous(), mel_lens)
                 raw = [audio[n, 0, :int(mel_lens[n]) * 256] for n in range(len(chunk))]
+                if loudness is not None:                # ragged as well: every item is measured over its own samples only
+                    audio = loudness(audio[:, 0].float(), mel_lens.to(audio.device) * 256)[:, None]
                 if resampler is None:
                     outs = [audio[n, 0, :int(mel_lens[n]) * 256] for n in range(len(chunk))]
                 else:                                   # ragged: every item is converted from its own samples only

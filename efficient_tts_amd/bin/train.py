@@ -32,6 +32,7 @@ from efficient_tts_amd import datasets, models, optimizers, schedulers, trainers
 from efficient_tts_amd.dist import DistributedEFTS
 from efficient_tts_amd.frontend import LogMelFrontend
 from efficient_tts_amd.resample import Resampler
+from efficient_tts_amd.loudness import LoudnessNormalizer
 from efficient_tts_amd.trim import SilenceTrimmer
 
 # (flags, kwargs) of the reference command line, kept as data so the parser and the docs cannot drift apart
@@ -133,6 +134,25 @@ def build_trimmer(config: Dict[str, Any], device=None) -> Optional[SilenceTrimme
                           peak=None if peak is None else float(peak), max_wav_value=float(front.get("max_wav_value", 32768.0)), trim=trim)
 
 
+def build_loudness(config: Dict[str, Any], device=None) -> Optional[LoudnessNormalizer]:
+    """the LoudnessNormalizer that the recipe asks for, at the front-end's rate; None without `normalize_loudness`.
+    `normalize_loudness: -23.0` brings every recording to that integrated loudness in LUFS (ITU-R BS.1770), `loudness_peak_ceiling`
+    (default 0.99; null: none) bounds the peak that the gain may lead to.  Level is set once: together with `normalize_peak` it is refused."""
+    target = config.get("normalize_loudness")
+    if target is None or target is False:
+        return None
+    if isinstance(target, bool):
+        target = -23.0
+    if config.get("normalize_peak") not in (None, False):
+        raise ValueError("normalize_loudness and normalize_peak both set the level of a recording: give one of them")
+    front = config.get("frontend_params") or {}
+    data = config.get("dataset_params") or {}
+    rate = int(front.get("sampling_rate", data.get("sampling_rate", 22050)))
+    ceiling = config.get("loudness_peak_ceiling", 0.99)
+    return LoudnessNormalizer(device, rate, target_lufs=float(target), peak_ceiling=None if ceiling is None else float(ceiling),
+                              max_wav_value=float(front.get("max_wav_value", 32768.0)))
+
+
 def _build_trainer(config: Dict[str, Any], loaders, samplers, proc: _Process):
     device = proc.device
     net = getattr(models, config["model_name"])(**config["model_params"]).to(device)
@@ -161,6 +181,11 @@ def _build_trainer(config: Dict[str, Any], loaders, samplers, proc: _Process):
         t = trainer.trimmer
         logging.info(f"on the device, per recording: " + (f"silence trimmed at {t.top_db} dB under the loudest frame, {t.keep_frames} frames kept" if t.trim
                                                            else "no trimming") + (f", peak set to {t.peak}" if t.peak is not None else ""))
+    trainer.loudness = build_loudness(config, device)
+    if trainer.loudness is not None:
+        n = trainer.loudness
+        logging.info(f"on the device, per recording: integrated loudness set to {n.target_lufs} LUFS at {n.sampling_rate} Hz"
+                     + (f", peak held under {n.peak_ceiling}" if n.peak_ceiling is not None else ""))
     return trainer
 
 
@@ -174,6 +199,7 @@ def main(argv=None) -> int:
         torch.distributed.init_process_group(backend="nccl", init_method="env://", device_id=proc.device)
     _setup_logging(args.verbose, quiet=proc.rank != 0)
     config = _load_config(args, proc)
+    build_loudness(config)                     # a recipe that sets the level twice is refused here, before any data is read
     loaders, samplers = _build_data(config, args, proc)
     trainer = _build_trainer(config, loaders, samplers, proc)
     if args.pretrain:

@@ -216,6 +216,10 @@ _SIGS = {
     "efts_stft_mag": (i32, [vp, i32, f32, i64, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "efts_stft_dist_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "efts_stft_dist": (i32, [vp, i32, i64, vp, i32, i64, f32, vp, i32, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
+    # BS.1770 integrated loudness and the gain to a target
+    "efts_loudness_workspace_bytes": (i64, [i32, i64, i32]),
+    "efts_loudness": (i32, [vp, i64, vp, i32, C.POINTER(C.c_double), C.c_double, C.c_double, vp, i64, vp, vp, vp, vp, vp, i32, vp]),
+    "efts_loudness_pcm16": (i32, [vp, i64, vp, i32, C.POINTER(C.c_double), C.c_double, C.c_double, f32, vp, i64, vp, vp, vp, vp, vp, i32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

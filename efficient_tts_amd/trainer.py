@@ -17,7 +17,8 @@ Everything inside is organised for this engine rather than copied from the refer
   * with `EftsAdam` the gradient clip is part of the fused optimizer kernel; with `DistributedEFTS` the
     bucketed RCCL all-reduce launched during backward is joined right before the optimizer step;
   * an optional `frontend` (efficient_tts_amd.frontend.LogMelFrontend) turns waveform batches into
-    log-mels on the GPU, behind an optional `resampler` and an optional `trimmer` (efficient_tts_amd.trim.SilenceTrimmer);
+    log-mels on the GPU, behind an optional `resampler`, an optional `trimmer` (efficient_tts_amd.trim.SilenceTrimmer) and an optional
+    `loudness` (efficient_tts_amd.loudness.LoudnessNormalizer);
     `bucket_frames` / `bucket_phones` pad shapes up to multiples so the engine's per-shape workspaces are re-used across ragged batches;
   * `eval_mcd: true` (YAML, default false) adds the free-running pass to every evaluation and publishes its mel-cepstral distortion
     against the dev recordings (efficient_tts_amd.score) -- the only figure here that sees the duration predictor;
@@ -80,6 +81,7 @@ class EfficientTTSTrainer:
         self.frontend = None                   # optional LogMelFrontend (set by efficient_tts_amd.bin.train)
         self.resampler = None                  # optional Resampler in front of it: corpus rate -> front-end rate (set by efficient_tts_amd.bin.train)
         self.trimmer = None                    # optional SilenceTrimmer between the two: `trim_silence` / `normalize_peak` (set by efficient_tts_amd.bin.train)
+        self.loudness = None                   # optional LoudnessNormalizer behind the trimmer: `normalize_loudness` (set by efficient_tts_amd.bin.train)
         self.finish_train = False
         self._tb = _TBWriter(config["outdir"]) if _TBWriter is not None else None
         self._bar = None
@@ -123,6 +125,9 @@ class EfficientTTSTrainer:
         if self.trimmer is not None:
             # the quiet ends cut off and / or the level set, item by item: a padded fp32 batch with the new lengths, so the frame count below shrinks
             third, third_lengths = self.trimmer(third, third_lengths)
+        if self.loudness is not None:
+            # every item brought to one integrated loudness (BS.1770) over its own samples: a padded fp32 batch, the lengths stay
+            third = self.loudness(third, third_lengths)
         n_frames = int(self.frontend.frames_of(third_lengths).max())
         # default buckets: ragged LJSpeech batches otherwise bring a new (B, T1, T2) almost every step, and every new shape
         # allocates and zero-fills a multi-GB activation workspace (4 are cached); 0 in the YAML turns the padding off
