@@ -24,12 +24,17 @@ HiFi-GAN V1 generator (efficient_tts_amd.vocoder).  Differences from the referen
     `--f0_smooth` decides the frames of an utterance together (the tracker's Viterbi path over all lags) instead of one by one;
   * `--loudness L [--loudness_peak_ceiling 0.99]` brings every utterance to an integrated loudness of L LUFS (ITU-R BS.1770, for example -23)
     on the device (efficient_tts_amd.loudness), behind the vocoder and in front of the optional rate conversion; a gain that would take the
-    peak over the ceiling is cut back.  Without the flag the wav files are byte for byte what they were.
+    peak over the ceiling is cut back.  Without the flag the wav files are byte for byte what they were;
+  * `--denoise S` (S > 0, for example 0.01) removes the vocoder's bias noise on the device (efficient_tts_amd.denoise): the magnitude spectrum
+    of the vocoder's answer to a blank mel is measured once after the vocoder is built, and S times it is subtracted from every frame of
+    every utterance (1024-point STFT, hop 256, phases kept) -- behind the vocoder, in front of `--loudness` and `--sampling_rate`;
+    `--write_f0` then tracks the denoised signal.  Without the flag the wav files are byte for byte what they were.
 """
 from __future__ import annotations
 
 import argparse
 import logging
+import math
 import os
 import sys
 import time
@@ -40,6 +45,7 @@ import torch
 import yaml
 
 from efficient_tts_amd import models
+from efficient_tts_amd.denoise import BiasDenoiser
 from efficient_tts_amd.griffinlim import GriffinLimVocoder
 from efficient_tts_amd.loudness import LoudnessNormalizer
 from efficient_tts_amd.pitch import PitchTracker
@@ -78,6 +84,8 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--loudness", type=float, default=None,
                    help="bring every utterance to this integrated loudness in LUFS (ITU-R BS.1770), for example -23 (default: leave the level)")
     p.add_argument("--loudness_peak_ceiling", type=float, default=0.99, help="--loudness: no sample may exceed this (default 0.99; <= 0: no ceiling)")
+    p.add_argument("--denoise", type=float, default=None,
+                   help="subtract this many times the vocoder's bias spectrum from every frame's magnitudes, for example 0.01 (default: no denoiser)")
     p.add_argument("--verbose", type=int, default=1)
     return p
 
@@ -165,9 +173,24 @@ def build_loudness(args, device=None):
     return LoudnessNormalizer(device, SAMPLING_RATE, target_lufs=args.loudness, peak_ceiling=ceiling if ceiling > 0 else None)
 
 
+def build_denoiser(args, vocoder=None, device=None):
+    """the BiasDenoiser for the vocoder's output, its bias measured from `vocoder`, or None without --denoise.  Without a vocoder: only the
+    checks (on the host, before anything is loaded)"""
+    if args.denoise is None:
+        return None
+    if args.no_vocoder:
+        raise ValueError("--denoise cleans the vocoder's output: it cannot be combined with --no_vocoder")
+    if not (args.denoise > 0 and math.isfinite(args.denoise)):
+        raise ValueError("--denoise must be a finite strength > 0 (leave the flag out for no denoiser)")
+    if vocoder is None:
+        return None
+    return BiasDenoiser.from_vocoder(vocoder, device, strength=args.denoise)
+
+
 def run_tts(args) -> float:
     check_f0_smooth(args)
     build_loudness(args)
+    build_denoiser(args)
     level = {0: logging.WARNING, 1: logging.INFO}.get(args.verbose, logging.DEBUG)
     logging.basicConfig(level=level, stream=sys.stdout, force=True, format="%(asctime)s %(levelname)s %(name)s:%(lineno)d  %(message)s")
     if not torch.cuda.is_available():
@@ -192,6 +215,7 @@ def run_tts(args) -> float:
         raise ValueError("--write_f0 tracks the vocoder's output: it cannot be combined with --no_vocoder")
     vocoder = None if args.no_vocoder else build_vocoder(args, device)
     tracker = PitchTracker(device, sampling_rate=SAMPLING_RATE, n_fft=1024, hop_size=256, smooth=args.f0_smooth) if args.write_f0 else None
+    denoiser = build_denoiser(args, vocoder, device)
     loudness = build_loudness(args, device)
     resampler = None
     if vocoder is not None and out_rate != SAMPLING_RATE:
@@ -221,12 +245,16 @@ def run_tts(args) -> float:
                 outs = mels
             elif len(chunk) == 1:
                 outs = raw = [vocoder(mels[0].t()[None].contiguous())[0, 0]]
+                if denoiser is not None:
+                    outs = raw = [denoiser(outs[0][None].float())[0]]
                 if loudness is not None:
                     outs = [loudness(outs[0][None].float())[0]]
                 if resampler is not None:
                     outs = [resampler(outs[0][None].float())[0][0]]
             else:                                       # one batched generator pass; every item equals its single-utterance result
                 audio = vocoder(mel.transpose(1, 2).contiguous(), mel_lens)
+                if denoiser is not None:                # ragged: every item is framed and reflected at its own ends
+                    audio = denoiser(audio[:, 0].float(), mel_lens.to(audio.device) * 256)[:, None]
                 raw = [audio[n, 0, :int(mel_lens[n]) * 256] for n in range(len(chunk))]
                 if loudness is not None:                # ragged as well: every item is measured over its own samples only
                     audio = loudness(audio[:, 0].float(), mel_lens.to(audio.device) * 256)[:, None]

@@ -2,7 +2,7 @@
 
     python -m efficient_tts_amd.bin.vocoder_score --test_fid_scp test.txt --outdir exp/vocoder/score \\
         --vocoder griffinlim|hifigan [--vocoder_config c.json --vocoder_checkpoint g.pt] [--gl_iters 32] [--precision bf16x3]
-        [--batch_size 16] [--wav_path wavs/]
+        [--batch_size 16] [--wav_path wavs/] [--denoise 0.01]
 
 Copy-synthesis: recording -> log-mel (`LogMelFrontend`) -> vocoder (the `--vocoder` switches of `efficient_tts_amd.bin.inference`) -> audio,
 compared with the recording over min(len) samples by `MultiResolutionSTFTDistance` at the reference's three resolutions.  No acoustic
@@ -13,6 +13,9 @@ have a value -- and prints those means.  An utterance too short for a resolution
 
 sc is the spectral convergence ||mag_rec - mag_syn||_F / ||mag_rec||_F, log_mag the mean |ln mag_rec - ln mag_syn|; both are 0 for a perfect
 copy.  The numbers judge `--precision`, `--gl_iters` and vocoder checkpoints against each other on the same recordings.
+
+`--denoise S` (S > 0) passes the copy-synthesis through `efficient_tts_amd.denoise.BiasDenoiser` before it is scored, the bias measured once from
+the vocoder's answer to a blank mel: the table then says whether a strength helps or eats the signal.
 """
 from __future__ import annotations
 
@@ -39,6 +42,8 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--precision", type=str, default="bf16x3", choices=["bf16x3", "bf16", "fp32"], help="MFMA operand mode of the vocoder")
     p.add_argument("--batch_size", type=int, default=16, help="utterances per call (default 16; every item is scored as if alone)")
     p.add_argument("--wav_path", type=str, default=None, help="directory searched, by file name, for a wav path that does not exist")
+    p.add_argument("--denoise", type=float, default=None,
+                   help="denoise the copy-synthesis before scoring: subtract this many times the vocoder's bias spectrum, for example 0.01 (default: off)")
     return p
 
 
@@ -49,6 +54,8 @@ def check_args(args) -> None:
                          "to score); --vocoder griffinlim needs no weights")
     if args.batch_size < 1:
         raise ValueError("--batch_size must be >= 1")
+    if args.denoise is not None and not (args.denoise > 0 and np.isfinite(args.denoise)):
+        raise ValueError("--denoise must be a finite strength > 0 (leave the flag out for no denoiser)")
 
 
 def columns(resolutions=DEFAULT_RESOLUTIONS):
@@ -95,6 +102,10 @@ def run_score(args):
     os.makedirs(args.outdir, exist_ok=True)
     frontend = LogMelFrontend(device)
     vocoder = build_vocoder(args, device)
+    denoiser = None
+    if args.denoise is not None:
+        from efficient_tts_amd.denoise import BiasDenoiser
+        denoiser = BiasDenoiser.from_vocoder(vocoder, device, strength=args.denoise)
     scorer = MultiResolutionSTFTDistance(device, max_wav_value=frontend.max_wav_value)
     items = _read_paths(args.test_fid_scp)
     rows = []
@@ -106,6 +117,8 @@ def run_score(args):
         with torch.no_grad():
             mel, mel_len = frontend(audio, wav_len)
             syn = vocoder(mel.transpose(1, 2).contiguous(), mel_len)[:, 0].float()
+            if denoiser is not None:
+                syn = denoiser(syn, (mel_len.to(wav_len.dtype) * frontend.hop).clamp(max=syn.shape[1]))
             n = torch.minimum(wav_len, mel_len.to(wav_len.dtype) * frontend.hop).clamp(max=min(syn.shape[1], audio.shape[1]))
             out = scorer(syn, audio, n)
         for (utt, _), k, sc, lm in zip(chunk, n.tolist(), out["sc"].tolist(), out["log_mag"].tolist()):

@@ -220,6 +220,9 @@ _SIGS = {
     "efts_loudness_workspace_bytes": (i64, [i32, i64, i32]),
     "efts_loudness": (i32, [vp, i64, vp, i32, C.POINTER(C.c_double), C.c_double, C.c_double, vp, i64, vp, vp, vp, vp, vp, i32, vp]),
     "efts_loudness_pcm16": (i32, [vp, i64, vp, i32, C.POINTER(C.c_double), C.c_double, C.c_double, f32, vp, i64, vp, vp, vp, vp, vp, i32, vp]),
+    # spectral subtraction of a vocoder's bias noise
+    "efts_denoise_workspace_bytes": (i64, [i32, i32]),
+    "efts_denoise": (i32, [vp, i64, vp, i32, vp, vp, f32, vp, i64, vp, vp, i64, i32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -92,7 +92,9 @@ extern "C" {
  *        + efts_stft_mag, efts_stft_dist, efts_stft_dist_workspace_bytes (STFT magnitudes at four sizes and the multi-resolution STFT
  *          distance): exports added, the revision stays by the same rule
  *        + efts_loudness, efts_loudness_pcm16, efts_loudness_workspace_bytes (BS.1770 integrated loudness and the gain to a target):
- *          exports added, the revision stays by the same rule */
+ *          exports added, the revision stays by the same rule
+ *        + efts_denoise, efts_denoise_workspace_bytes (spectral subtraction of a vocoder's bias noise): exports added, the revision stays
+ *          by the same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -1077,6 +1079,39 @@ int efts_loudness(const float* in, int64_t ld_in, const int32_t* lengths, int32_
 int efts_loudness_pcm16(const int16_t* in, int64_t ld_in, const int32_t* lengths, int32_t fs, const double* kweight, double target_lufs,
                         double peak_ceiling, float pcm_scale, float* out, int64_t ld_out, double* loudness, float* gain, int32_t* flags,
                         int32_t* blocks, void* workspace, int32_t B, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Spectral denoiser for a vocoder's bias noise: STFT -> subtract strength * bias from the magnitudes, clamp at 0, keep the phase -> inverse
+ * STFT -> overlap-add, in one launch.  What the published Tacotron 2 / WaveGlow / HiFi-GAN inference scripts do with torch.stft / torch.istft.
+ * Fixed configuration: N = 1024, H = 256, W = 1024, everything fp32; the entry takes no argument that could ask for another one (a later
+ * entry that does refuses what it was not built for with EFTS_ESHAPE).
+ *   samples : fp32.  Item b is row b of audio [B][ld] and has len = lengths[b], clamped to 0 .. max_len, samples; nothing behind them is read.
+ *   window  : [1024] fp32, DEVICE memory: the periodic Hann window w[i] = 0.5 - 0.5 cos(2 pi i / 1024), computed by the caller in float64 and
+ *             rounded once; the same window for analysis and synthesis.
+ *   bias    : [513] fp32, DEVICE memory: non-negative magnitudes per bin.  strength: a finite float >= 0, passed by value.
+ *   frames  : exactly those of efts_stft_mag: an item has T = 1 + len / 256 frames when len > 512.  Sample n of frame t is index
+ *             i = 256 t - 512 + n of the signal, reflected without edge repeat: i < 0 -> -i, i >= len -> 2 (len - 1) - i.
+ *   per frame: X = DFT(w * frame) for f = 0 .. 512; m = sqrt(fma(re, re, im * im)); d = m - strength * bias[f]; g = d / m if d > 0, otherwise
+ *             0 (so g = 0 where m = 0); X' = g X; x' = the real inverse DFT of X' (the imaginary parts of DC and Nyquist are dropped).
+ *   out[b * ld_out + s] = (sum over the frames t that cover s, oldest first, of w[n] * x'_t[n], n = s + 512 - 256 t) / max(sum of their w[n]^2, 1e-8)
+ *             for s < len, exactly 0.0f for len <= s < ld_out.  This is torch.stft(center=True, pad_mode="reflect") -> gain ->
+ *             torch.istft(center=True, length=len).
+ *   An item with len <= 512 cannot be reflect-padded: its samples are copied to out bit for bit and frames[b] = 0.  frames [B] int32: T.  The
+ *   device decides; nothing is read back.
+ *   ONE fixed order, no atomics.  Frames 2 p and 2 p + 1 of an item share one complex transform, forward and inverse (frame 2 p the real
+ *   part; an unpaired last frame has a zero partner whose gain is 0); a pair never crosses items.  A run of 16 consecutive hops (hop c =
+ *   samples 256 c .. 256 c + 255; runs begin at multiples of 16 hops of the item) is overlap-added by one wave, which computes frames
+ *   c0 - 2 .. c0 + 17 of its run c0 .. c0 + 15 itself: every sample starts from 0 and receives w[n] * x'_t[n] of its up to four frames in
+ *   ascending t, the sum of w[n]^2 likewise, then one division.  An item gives the same bits alone, at any batch position, in any run and
+ *   whatever lies behind its samples.  No spectrum and no frame goes to memory.
+ *   workspace: none is needed: the size entry returns 0 for every argument, workspace may be NULL (or 16-byte aligned) and is not touched.
+ * EFTS_EINVAL, nothing launched, the entry's name in efts_last_error(): a null pointer (other than workspace) or one not aligned to its
+ * element, B outside 1 .. 65535, max_len outside 1 .. 2^31 - 8193, a leading dimension below max_len, ld_out >= 2^31, a negative or
+ * non-finite strength, workspace_bytes < 0, out [B][ld_out] overlapping audio.
+ * ---------------------------------------------------------------------------------- */
+int64_t efts_denoise_workspace_bytes(int32_t B, int32_t max_len);
+int efts_denoise(const float* audio, int64_t ld, const int32_t* lengths, int32_t max_len, const float* window, const float* bias, float strength,
+                 float* out, int64_t ld_out, int32_t* frames, void* workspace, int64_t workspace_bytes, int32_t B, void* stream);
 
 #ifdef __cplusplus
 }
