@@ -57,15 +57,20 @@ def _check(kernel, case, got, ref64, ref32, chain=False, extra=0.0):
     assert err <= min(max(FACTOR * e32, FLOOR), COND) + extra, f"{kernel} {case}: error {err:.3e} vs float64, float32 transcription {e32:.3e}"
 
 
-def unpack_plane(pl, B, Tp, T, kp, split):
+def unpack_plane(pl, B, Tp, T, kp, split, parts=False):
     """rows (b * Tp + j), j < T, of an operand plane [B * Tp][ld bytes] -> float32 [B, T, kp].  Format 1: kp bf16; format 2: every
     128-byte chunk holds 32 hi then 32 lo bf16, the value is hi + lo (tests/test_align_gpu.py, test_pack_vt_layout_both_kernels);
-    format 3: kp float32 (tests/test_gpu_fp32.py)"""
+    format 3: kp float32 (tests/test_gpu_fp32.py).
+    parts: (hi, lo) instead of the value -- the two numbers a format-2 contraction multiplies (lo is zero for formats 1 and 3)"""
     raw = pl.cpu()
     if split == 3:
-        return raw.view(torch.float32).view(B, Tp, -1)[:, :T, :kp].clone()
+        v = raw.view(torch.float32).view(B, Tp, -1)[:, :T, :kp].clone()
+        return (v, torch.zeros_like(v)) if parts else v
     if split == 1:
-        return raw.view(torch.bfloat16).view(B, Tp, -1)[:, :T, :kp].float()
+        v = raw.view(torch.bfloat16).view(B, Tp, -1)[:, :T, :kp].float()
+        return (v, torch.zeros_like(v)) if parts else v
     nchunk = kp // 32
     w = raw.view(torch.bfloat16).view(B, Tp, -1)[:, :T, :nchunk * 64].reshape(B, T, nchunk, 2, 32).float()
+    if parts:
+        return w[:, :, :, 0].reshape(B, T, kp), w[:, :, :, 1].reshape(B, T, kp)
     return (w[:, :, :, 0] + w[:, :, :, 1]).reshape(B, T, kp)
