@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "efts_gemm_kernels.h"
+#include "efts_gemm_epilogue.h"
 
 namespace efts {
 
@@ -32,12 +32,7 @@ __global__ __launch_bounds__(256, 2) void conv5_kernel(GemmKernelArgs p) {
     const int z = blockIdx.y;
     const int lrow = lane & 31, lhalf = lane >> 5;
     const int nsteps = p.nchunk * TAPS;
-    const int c4 = (tid & 31) << 2;
     constexpr int RPP = 8, NPS = 16, NRING = 8;
-    const float* resid = p.resid ? p.resid + (long)z * p.r_bs : nullptr;
-    const float* rowmask = p.rowmask ? p.rowmask + (long)z * p.m_bs : nullptr;
-    float* of = p.out_f32 ? p.out_f32 + (long)z * p.o_bs : nullptr;
-    char* ob = p.out_bf16 ? p.out_bf16 + (long)z * p.ob_bs : nullptr;
     const char* A = p.a + (long)z * p.a_bs;
     const char* Bw = p.b + (long)z * p.b_bs;
     const int ntot = p.mtiles * p.ntiles;
@@ -50,8 +45,7 @@ __global__ __launch_bounds__(256, 2) void conv5_kernel(GemmKernelArgs p) {
     }
     const int mt = bid / p.ntiles, nt = bid - mt * p.ntiles;
     const int m0 = mt * C5_BM, n0 = nt * BN;
-    const int col = n0 + c4;
-    const bool vec = p.vec_ok && (col + 3 < p.n);
+    const EpiTile et = epi_tile<BN>(p, z, 0, m0, n0, C5_WIN, C5_BM);
 
     unsigned voa[8], vow[4];      // per-lane DMA offsets: 8 window pieces + 4 weight pieces per wave
     {
@@ -167,122 +161,29 @@ __global__ __launch_bounds__(256, 2) void conv5_kernel(GemmKernelArgs p) {
         ws = (ws == 2) ? 0 : ws + 1;
     }
 
-    // ---- last step + epilogue (two passes; operands of the first 8 sweeps of each pass prefetched, ring of 8)
+    // ---- last step + epilogue (efts_gemm_epilogue.h), two passes through the 64 KiB staging tile: pass ep takes accumulator
+    // blocks 2 * ep, 2 * ep + 1 of every wave, i.e. tile rows 64 * ep + (0 .. 63) and 128 + 64 * ep + (0 .. 63).  The operands of
+    // the first 8 sweeps of a pass are requested ahead of its staging, the other 8 as the ring of 8 falls free.
     u32x4 rres[NRING];
     float rmv[NRING];
-    const bool pre = vec && col < p.n;
-    const int rows_in = p.m - m0 < C5_WIN ? p.m - m0 : C5_WIN;
-    const int rows_out = p.m - m0 < C5_BM ? p.m - m0 : C5_BM;
-    const unsigned trow = tid >> 5;
-    const __amdgpu_buffer_rsrc_t rr = make_rsrc(resid ? resid + (long)m0 * p.ldr : nullptr, resid ? (long)rows_in * p.ldr * 4 : 0);
-    const __amdgpu_buffer_rsrc_t rk = make_rsrc(rowmask ? rowmask + m0 : nullptr, rowmask ? (long)rows_in * 4 : 0);
-    const unsigned vr = trow * (unsigned)p.ldr * 4 + col * 4;
-    // sweep ps of pass ep covers tile rows row_of(ep, ps) + (0..7)
-    auto row_of = [&](int ep, int ps) { return ps * RPP + 64 * ep + (ps >= 8 ? 64 : 0); };
-    auto request = [&](int ep, int ps) {
-        rres[ps % NRING] = __builtin_amdgcn_raw_buffer_load_b128(rr, vr, row_of(ep, ps) * (unsigned)p.ldr * 4, EFTS_AUX_LD);
-        rmv[ps % NRING] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rk, trow * 4, row_of(ep, ps) * 4, 0));
-    };
     compute(ws, TAPS - 1);
     lds_barrier();
 
     float* cs = (float*)smem;
-    const __amdgpu_buffer_rsrc_t ro = make_rsrc(of ? of + (long)m0 * p.ldo : nullptr, of ? (long)rows_out * p.ldo * 4 : 0);
-    const __amdgpu_buffer_rsrc_t rb = make_rsrc(ob ? ob + (long)m0 * p.ldob : nullptr, ob ? (long)rows_out * p.ldob : 0);
-    const unsigned vo = trow * (unsigned)p.ldo * 4 + col * 4;
-    const unsigned vb = trow * (unsigned)p.ldob + (unsigned)plane_off_hi(col, p.out_split);
-    const bool has_mask = rowmask != nullptr;
-    const unsigned ld_sg = (unsigned)(p.n >> 3);
-    const __amdgpu_buffer_rsrc_t rsg = make_rsrc(p.sign ? p.sign + (long)m0 * ld_sg : nullptr, p.sign ? (long)rows_out * ld_sg : 0);
 #pragma unroll
     for (int ep = 0; ep < 2; ++ep) {
-        if (pre) {
+        const auto rowof = [ep](int ps) { return ps * RPP + 64 * ep + (ps >= 8 ? 64 : 0); };
+        if (et.vec) epi_prefetch(p, et, rres, rmv, rowof);          // in flight while the accumulators are staged
 #pragma unroll
-            for (int ps = 0; ps < NRING; ++ps) request(ep, ps);     // in flight while the accumulators are staged
-        }
-        {
-            const float* bias = p.bias;
+        for (int j = 0; j < 2; ++j) {
+            const int cl = wn * 64 + j * 32 + lrow;
+            const float bv = epi_bias(p, n0 + cl);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int cl = wn * 64 + j * 32 + lrow;
-                const float bv = (bias && n0 + cl < p.n) ? bias[n0 + cl] : 0.f;
-#pragma unroll
-                for (int ii = 0; ii < 2; ++ii) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int rl = wm * 64 + ii * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
-                        float v = acc[2 * ep + ii][j][r] * p.alpha + bv;
-                        if (p.act == EFTS_ACT_LEAKY) v = v > 0.f ? v : v * p.slope;
-                        else if (p.act == EFTS_ACT_RELU) v = v > 0.f ? v : 0.f;
-                        cs[rl * 128 + cl] = v;
-                    }
-                }
-            }
+            for (int ii = 0; ii < 2; ++ii) epi_stage<BN, EPI_WIDE>(p, cs, acc[2 * ep + ii][j], wm * 64 + ii * 32, cl, bv);
         }
         lds_barrier();
-        if (pre) {
-#pragma unroll
-            for (int ps = 0; ps < NPS; ++ps) {
-                const int rl = ps * RPP + trow;
-                float4 v = *(const float4*)(cs + rl * 128 + c4);
-                if (p.sign) {                                // sign words of efts_abi.h `sign_mask` (see gemm_kernel)
-                    const unsigned long long b0 = __ballot(v.x > 0.f), b1 = __ballot(v.y > 0.f), b2 = __ballot(v.z > 0.f), b3 = __ballot(v.w > 0.f);
-                    if ((tid & 31) == 0) {
-                        const int sh = tid & 32;
-                        const u32x4 w = {(unsigned)(b0 >> sh), (unsigned)(b1 >> sh), (unsigned)(b2 >> sh), (unsigned)(b3 >> sh)};
-                        store_b128(w, rsg, trow * ld_sg + (unsigned)(n0 >> 7) * 16, row_of(ep, ps) * ld_sg);
-                    }
-                }
-                if (p.drop_thresh) {                         // Dropout on the activated value (see gemm_kernel)
-                    const unsigned e0 = (unsigned)(m0 + row_of(ep, ps) + (int)trow) * (unsigned)p.n + col;
-                    v.x *= drop_scale(p.drop_seed_h, e0, p.drop_thresh, p.drop_inv_keep); v.y *= drop_scale(p.drop_seed_h, e0 + 1, p.drop_thresh, p.drop_inv_keep);
-                    v.z *= drop_scale(p.drop_seed_h, e0 + 2, p.drop_thresh, p.drop_inv_keep); v.w *= drop_scale(p.drop_seed_h, e0 + 3, p.drop_thresh, p.drop_inv_keep);
-                }
-                const u32x4 x = rres[ps % NRING];
-                const float rm = has_mask ? rmv[ps % NRING] : 1.f;
-                if (ps + NRING < NPS) request(ep, ps + NRING);
-                v.x = (v.x + __uint_as_float(x.x)) * rm; v.y = (v.y + __uint_as_float(x.y)) * rm;
-                v.z = (v.z + __uint_as_float(x.z)) * rm; v.w = (v.w + __uint_as_float(x.w)) * rm;
-                if (of) {
-                    const u32x4 o = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
-                    { __builtin_amdgcn_raw_buffer_store_b128(o, ro, vo, row_of(ep, ps) * (unsigned)p.ldo * 4, EFTS_AUX_STF); asm volatile("s_nop 4" ::"v"(o)); }
-                }
-                if (ob) {
-                    float r0, r1, r2, r3;
-                    const u32x2 hi = {pack_bf16x2(v.x, v.y, &r0, &r1), pack_bf16x2(v.z, v.w, &r2, &r3)};
-                    __builtin_amdgcn_raw_buffer_store_b64(hi, rb, vb, row_of(ep, ps) * (unsigned)p.ldob, EFTS_AUX_STP);
-                    if (p.out_split == 2) {
-                        float d0, d1;
-                        const u32x2 lo = {pack_bf16x2(r0, r1, &d0, &d1), pack_bf16x2(r2, r3, &d0, &d1)};
-                        __builtin_amdgcn_raw_buffer_store_b64(lo, rb, vb + 64, row_of(ep, ps) * (unsigned)p.ldob, EFTS_AUX_STP);
-                    }
-                }
-            }
-        } else if (col < p.n) {
-            for (int ps = 0; ps < NPS; ++ps) {
-                const int rl = ps * RPP + trow;
-                const int trl = row_of(ep, ps) + trow;
-                const int row = m0 + trl;
-                if (trl >= C5_BM || row >= p.m) continue;
-                const float4 v = *(const float4*)(cs + rl * 128 + c4);
-                const float rm = rowmask ? rowmask[row] : 1.f;
-                float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (col + u >= p.n) break;
-                    float t = vv[u];
-                    if (resid) t += resid[(long)row * p.ldr + col + u];
-                    t *= rm;
-                    if (of) of[(long)row * p.ldo + col + u] = t;
-                    if (ob) {
-                        const unsigned short hi = f32_to_bf16(t);
-                        char* d = ob + (long)row * p.ldob + plane_off_hi(col + u, p.out_split);
-                        *(unsigned short*)d = hi;
-                        if (p.out_split == 2) *(unsigned short*)(d + 64) = f32_to_bf16(t - bf16_to_f32(hi));
-                    }
-                }
-            }
-        }
+        if (et.vec) epi_sweep_vec<BN, RPP, NPS, NRING, EPI_WIDE>(p, et, cs, rres, rmv, rowof);
+        else if (et.col < p.n) epi_sweep_scalar<BN, RPP, NPS, EPI_WIDE>(p, et, cs, rowof);
         lds_barrier();
     }
   }   // tile loop
@@ -308,10 +209,6 @@ __global__ __launch_bounds__(512, 2) void conv8_kernel(GemmKernelArgs p) {
     const int z = blockIdx.y;
     const int lrow = lane & 31, lhalf = lane >> 5;
     const int nsteps = p.nchunk * TAPS;
-    const float* resid = p.resid ? p.resid + (long)z * p.r_bs : nullptr;
-    const float* rowmask = p.rowmask ? p.rowmask + (long)z * p.m_bs : nullptr;
-    float* of = p.out_f32 ? p.out_f32 + (long)z * p.o_bs : nullptr;
-    char* ob = p.out_bf16 ? p.out_bf16 + (long)z * p.ob_bs : nullptr;
     const char* A = p.a + (long)z * p.a_bs;
     const char* Bw = p.b + (long)z * p.b_bs;
     const int ntot = p.mtiles * p.ntiles;
@@ -412,76 +309,28 @@ __global__ __launch_bounds__(512, 2) void conv8_kernel(GemmKernelArgs p) {
         ws = (ws == 2) ? 0 : ws + 1;
     }
 
-    // ---- epilogue: two column halves of 128 through [256][128] fp32 = 128 KiB; 32 threads per 512-byte row, 16 rows a sweep
-    constexpr int NPS = 16, NRING = 4;
+    // ---- epilogue (efts_gemm_epilogue.h): two column halves of 128 through [256][128] fp32 = 128 KiB; 32 threads per 512-byte
+    // row, 16 rows a sweep, operands in a ring of 4.  The dispatcher sends aligned launches with n % 256 == 0 only: no scalar sweep.
+    constexpr int RPP = 16, NPS = 16, NRING = 4;
     float* cs = (float*)smem;
-    const int c4 = (tid & 31) << 2;
-    const unsigned trow = tid >> 5;
-    const int rows_in = p.m - m0 < C5_WIN ? p.m - m0 : C5_WIN;
-    const int rows_out = p.m - m0 < C5_BM ? p.m - m0 : C5_BM;
-    const __amdgpu_buffer_rsrc_t rr = make_rsrc(resid ? resid + (long)m0 * p.ldr : nullptr, resid ? (long)rows_in * p.ldr * 4 : 0);
-    const __amdgpu_buffer_rsrc_t rk = make_rsrc(rowmask ? rowmask + m0 : nullptr, rowmask ? (long)rows_in * 4 : 0);
-    const __amdgpu_buffer_rsrc_t ro = make_rsrc(of ? of + (long)m0 * p.ldo : nullptr, of ? (long)rows_out * p.ldo * 4 : 0);
-    const __amdgpu_buffer_rsrc_t rb = make_rsrc(ob ? ob + (long)m0 * p.ldob : nullptr, ob ? (long)rows_out * p.ldob : 0);
-    const bool has_mask = rowmask != nullptr;
+    const auto rowof = [](int ps) { return ps * RPP; };
 #pragma unroll 1
     for (int h = 0; h < 2; ++h) {
-        const int col = n0 + h * 128 + c4;
-        const unsigned vr = trow * (unsigned)p.ldr * 4 + col * 4;
-        const unsigned vo = trow * (unsigned)p.ldo * 4 + col * 4;
-        const unsigned vb = trow * (unsigned)p.ldob + (unsigned)plane_off_hi(col, p.out_split);
+        const EpiTile et = epi_tile<128>(p, z, 0, m0, n0 + h * 128, C5_WIN, C5_BM);
         u32x4 rres[NRING];
         float rmv[NRING];
-        auto request = [&](int ps) {
-            rres[ps % NRING] = __builtin_amdgcn_raw_buffer_load_b128(rr, vr, ps * 16 * (unsigned)p.ldr * 4, EFTS_AUX_LD);
-            rmv[ps % NRING] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rk, trow * 4, ps * 16 * 4, 0));
-        };
-#pragma unroll
-        for (int ps = 0; ps < NRING; ++ps) request(ps);
+        epi_prefetch(p, et, rres, rmv, rowof);
         if ((wn >> 1) == h) {
-            const float* bias = p.bias;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int cl = (wn & 1) * 64 + j * 32 + lrow;
-                const float bv = bias ? bias[n0 + h * 128 + cl] : 0.f;
+                const float bv = epi_bias(p, et.n0 + cl);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int rl = wm * 128 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
-                        float v = acc[i][j][r] * p.alpha + bv;
-                        if (p.act == EFTS_ACT_LEAKY) v = v > 0.f ? v : v * p.slope;
-                        else if (p.act == EFTS_ACT_RELU) v = v > 0.f ? v : 0.f;
-                        cs[rl * 128 + cl] = v;
-                    }
-                }
+                for (int i = 0; i < 4; ++i) epi_stage<128, 0>(p, cs, acc[i][j], wm * 128 + i * 32, cl, bv);
             }
         }
         lds_barrier();
-#pragma unroll
-        for (int ps = 0; ps < NPS; ++ps) {
-            const int rl = ps * 16 + trow;
-            float4 v = *(const float4*)(cs + rl * 128 + c4);
-            const u32x4 x = rres[ps % NRING];
-            const float rm = has_mask ? rmv[ps % NRING] : 1.f;
-            if (ps + NRING < NPS) request(ps + NRING);
-            v.x = (v.x + __uint_as_float(x.x)) * rm; v.y = (v.y + __uint_as_float(x.y)) * rm;
-            v.z = (v.z + __uint_as_float(x.z)) * rm; v.w = (v.w + __uint_as_float(x.w)) * rm;
-            if (of) {
-                const u32x4 o = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
-                { __builtin_amdgcn_raw_buffer_store_b128(o, ro, vo, ps * 16 * (unsigned)p.ldo * 4, EFTS_AUX_STF); asm volatile("s_nop 4" ::"v"(o)); }
-            }
-            if (ob) {
-                float r0, r1, r2, r3;
-                const u32x2 hi = {pack_bf16x2(v.x, v.y, &r0, &r1), pack_bf16x2(v.z, v.w, &r2, &r3)};
-                __builtin_amdgcn_raw_buffer_store_b64(hi, rb, vb, ps * 16 * (unsigned)p.ldob, EFTS_AUX_STP);
-                if (p.out_split == 2) {
-                    float d0, d1;
-                    const u32x2 lo = {pack_bf16x2(r0, r1, &d0, &d1), pack_bf16x2(r2, r3, &d0, &d1)};
-                    __builtin_amdgcn_raw_buffer_store_b64(lo, rb, vb + 64, ps * 16 * (unsigned)p.ldob, EFTS_AUX_STP);
-                }
-            }
-        }
+        epi_sweep_vec<128, RPP, NPS, NRING, 0>(p, et, cs, rres, rmv, rowof);
         lds_barrier();
     }
 }

@@ -1,6 +1,7 @@
 // efts_gemm_kernels.h -- what the kernels of efts_gemm share: the argument block, tile constants, and the launchers each
-// translation unit exports (efts_gemm.hip: generic 124-row ring kernel + dispatch; efts_gemm_narrow.hip: 64- / 32-column tiles and
-// the LDS-resident kernel; efts_conv5.hip: the 256-row k5 kernel).
+// translation unit exports.  efts_gemm_ring.h: gemm_kernel<TAPS, SPLIT, BNT, DBG>, the ring kernel; efts_gemm_epilogue.h: the row-sweep
+// epilogue of every tiling.  efts_gemm.hip: dispatch + the 128-column ring tiles; efts_gemm_narrow.hip: the 64- / 32-column ring tiles and
+// resident32_kernel; efts_conv5.hip: conv5_kernel (256-row k5 windows); efts_smallm.hip: smallm_kernel.
 #pragma once
 #include "efts_mma.h"
 
@@ -25,7 +26,7 @@ struct GemmKernelArgs {
     const float* rowmask;
     float* out_f32;
     char* out_bf16;
-    char* out_lo;               // out_split 1 only: separate plane for the bf16 remainder (generic gemm_kernel only)
+    char* out_lo;               // out_split 1 only: separate plane for the bf16 remainder (EPI_LO: 128-column ring tiles only)
     char* sign;                 // sign words of the activated outputs (efts_abi.h `sign_mask`), row stride n / 8 bytes, or null
     float* sidx;                // soft index of the softmax over each output row (efts_abi.h `soft_index`), [batch][m], or null
     const int* klen;            // valid columns per batch item

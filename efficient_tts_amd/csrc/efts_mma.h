@@ -27,8 +27,6 @@ __device__ __forceinline__ int lds_off(int row, int slot) {
     return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4);
 }
 
-
-
 // One LDS-DMA piece = one wave instruction = 8 tile rows x 128 B.  Lane l lands at LDS
 // m0 + 16*l, i.e. tile row 8*piece + l/8, physical slot l%8; its source is sbase + voff.
 __device__ __forceinline__ void dma16(unsigned lds_addr, unsigned voff, const char* sbase) {
@@ -39,13 +37,19 @@ __device__ __forceinline__ void dma16(unsigned lds_addr, unsigned voff, const ch
                  : "memory");
 }
 
-__device__ __forceinline__ void wait_vmcnt(int n) {   // n = LDS-DMA pieces allowed to stay in flight (multiple of 4)
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    }
+// Counted wait: at most n LDS-DMA pieces stay in flight.  The ring kernels count what they issued: up to two window groups (4
+// pieces per wave) and one weight group (W pieces per wave: 4, 2 or 1 for 128-, 64-, 32-column tiles), so n = 4 i + {0, W},
+// i = 0 .. 2.  The immediate of s_waitcnt must be a constant, hence the chain.
+template <int W = 4>
+__device__ __forceinline__ void wait_vmcnt(int n) {
+#define EFTS_VMCNT(k) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(k) : "memory")
+    if (n == 0) EFTS_VMCNT(0);
+    else if (n == W) EFTS_VMCNT(W);
+    else if (n == 4) EFTS_VMCNT(4);
+    else if (n == 4 + W) EFTS_VMCNT(4 + W);
+    else if (n == 8) EFTS_VMCNT(8);
+    else EFTS_VMCNT(8 + W);
+#undef EFTS_VMCNT
 }
 
 // barrier that orders LDS traffic only: global loads / stores in flight stay in flight
@@ -64,8 +68,10 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, long 
 // compiler re-used data register 0 for the next store's address (v_add right behind the s_nop), and lanes 12-15 of every
 // 16-lane group stored the address instead of the value (tests/test_resconv_gpu.py caught it as 1e-40-sized outputs).
 // Naming the data as an input of a trailing asm keeps it live -- and unmodified -- across 5 more wait states.
+// AUX: cache-policy bits of the store (the EFTS_AUX_* lab switches of efts_gemm_kernels.h).
+template <int AUX = 0>
 __device__ __forceinline__ void store_b128(u32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, AUX);
     asm volatile("s_nop 4" ::"v"(v));
 }
 

@@ -21,7 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "efts_gemm_kernels.h"
+#include "efts_gemm_epilogue.h"
 
 namespace efts {
 
@@ -109,8 +109,8 @@ __global__ __launch_bounds__(256) void smallm_kernel(GemmKernelArgs p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) part[wave][i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhalf][lrow] = acc[i][r];
     __syncthreads();
-    // ---- combine in wave order + the fused epilogue of efts_gemm: alpha, bias, activation, residual, row mask; fp32 and / or
-    // operand-plane rows of 8 columns per thread
+    // ---- combine in wave order + the fused epilogue of efts_gemm in the element order of efts_gemm_epilogue.h (alpha, bias,
+    // activation, residual, row mask, hi / lo rounding); fp32 and / or operand-plane rows of 8 columns per thread, one sweep
     const int row = tid >> 2, c8 = (tid & 3) * 8;
     const int grow = m0 + row;
     if (grow >= p.m) return;
@@ -125,12 +125,7 @@ __global__ __launch_bounds__(256) void smallm_kernel(GemmKernelArgs p) {
         x[0] = q0.x; x[1] = q0.y; x[2] = q0.z; x[3] = q0.w; x[4] = q1.x; x[5] = q1.y; x[6] = q1.z; x[7] = q1.w;
     }
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        float t = v[u] * p.alpha + (p.bias ? p.bias[col + u] : 0.f);
-        if (p.act == EFTS_ACT_LEAKY) t = t > 0.f ? t : t * p.slope;
-        else if (p.act == EFTS_ACT_RELU) t = t > 0.f ? t : 0.f;
-        v[u] = (t + x[u]) * rm;
-    }
+    for (int u = 0; u < 8; ++u) v[u] = epi_resid_mask(epi_activate<0>(p, v[u], epi_bias(p, col + u)), x[u], rm);
     if (p.out_f32) {
         *(float4*)(p.out_f32 + (long)grow * p.ldo + col) = make_float4(v[0], v[1], v[2], v[3]);
         *(float4*)(p.out_f32 + (long)grow * p.ldo + col + 4) = make_float4(v[4], v[5], v[6], v[7]);

@@ -15,6 +15,9 @@ BOUND_ONLY names the cases held to the a-priori bound alone (see there).
 The packers (section 2): efts_pack_rows and efts_pack_weight byte for byte against the encoders; the weight-norm fold against float64.
 """
 import ctypes as C
+import hashlib
+import json
+import os
 
 import pytest
 import torch
@@ -92,7 +95,7 @@ def _device_operands(c, dev):
                 mask=op.mask.to(dev))
 
 
-def _launch(lib, c, d, o, tiling):
+def _launch(lib, c, d, o, tiling, extra=None):
     from efficient_tts_amd import lib as L
     g = L.GemmArgs()
     ra = R.A_GUARD_LO + c.m + R.A_GUARD_HI
@@ -119,6 +122,8 @@ def _launch(lib, c, d, o, tiling):
     if c.lo:
         g.out_bf16_lo = o.plane_ptr(o.l)
     g.tiling = tiling
+    if extra is not None:
+        extra(g)
     _call("efts_gemm", lib.efts_gemm(C.byref(g), _st()))
 
 
@@ -194,6 +199,91 @@ def test_gemm_case(lib, case):
             assert (x is None and y is None) or torch.equal(x.view(torch.int32) if x.dtype == torch.float32 else x,
                                                             y.view(torch.int32) if y.dtype == torch.float32 else y), \
                 f"{c.name}: {what} of {R.TILING_NAME[t]} differ from {R.TILING_NAME[ring[0]]}"
+
+
+# ------------------------------------------------------------------------------------------------------------ 1b. the recorded bits
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemm_digests.json")
+
+
+def _sha(*buffers):
+    h = hashlib.sha256()
+    for t in buffers:
+        h.update(b"-" if t is None else t.cpu().contiguous().view(torch.uint8).numpy().tobytes())
+    return h.hexdigest()[:32]
+
+
+def _extras(dev):
+    """launches of the epilogue features that no case of gemm_reference.CASES carries (sign words + dropout, soft index, squared-error
+    parts): (case, tilings, make), make() -> (canary-filled side outputs, hook that points the launch's arguments at them)"""
+    G, W, A = R.GENERIC, R.WIDE, R.AUTO
+    out = []
+    for sp in (1, 2):
+        c = R.Case(name=f"x-sign-drop-split{sp}", tilings=(G, W), split=sp, taps=5, m=362, n=128, K=R.chunk_k(sp), bias=True, act=R.ACT_LEAKY,
+                   resid=True, mask=True, out="both")
+
+        def make(c=c):
+            sign = torch.full((c.m + 2 * R.OUT_GUARD, c.n // 8), R.CANARY, dtype=torch.uint8, device=dev)
+
+            def hook(g):
+                g.sign_mask, g.drop_p, g.drop_seed = sign.data_ptr() + R.OUT_GUARD * (c.n // 8), 0.25, 1234
+            return [sign], hook
+        out.append((c, (G, W, A), make))
+    c = R.Case(name="x-soft-index", tilings=(G,), m=130, n=96, K=64, batch=2, alpha=0.125)
+
+    def make(c=c):
+        sidx = torch.full((c.batch * c.m + 8,), CANARY32, dtype=torch.int32, device=dev)
+        kl, ql = (torch.tensor(v, dtype=torch.int32, device=dev) for v in ([96, 57], [130, 77]))
+
+        def hook(g):
+            g.soft_index, g.key_len, g.query_len = sidx.data_ptr(), kl.data_ptr(), ql.data_ptr()
+        return [sidx], hook
+    out.append((c, (G, A), make))
+    c = R.Case(name="x-sqerr", tilings=(G,), m=130, n=96, K=64, batch=2, bias=True, mask=True)
+
+    def make(c=c):
+        target = torch.randn(c.batch, c.m, c.n, generator=torch.Generator().manual_seed(7)).to(dev)
+        part = torch.full((c.batch * 2 * 4 + 4,), CANARY32, dtype=torch.int32, device=dev)       # [batch][2 tiles][4 waves]
+
+        def hook(g):
+            g.sqerr_target, g.ld_target, g.target_batch_stride, g.sqerr_part = target.data_ptr(), c.n, c.m * c.n, part.data_ptr()
+        return [part], hook
+    out.append((c, (G, A), make))
+    return out
+
+
+def gemm_digests(lib):
+    """{"<case>/<tiling>": sha256 of the raw output buffers of that launch, canary rows and padding included}: every case of
+    gemm_reference.CASES and of _extras on every tiling that accepts it and on AUTO"""
+    dev = _dev()
+    out = {}
+
+    def run(c, tilings, make=lambda: ([], None)):
+        d = _device_operands(c, dev)
+        for tiling in tilings:
+            if not R.accepts(c, tiling):
+                continue
+            o = _Outputs(c, dev)
+            side, hook = make()
+            _launch(lib, c, d, o, tiling, hook)
+            torch.cuda.synchronize()
+            out[f"{c.name}/{R.TILING_NAME[tiling]}"] = _sha(o.f, o.p, o.l, *side)
+
+    for c in R.CASES:
+        run(c, R.EXPLICIT + (R.AUTO,))
+    for c, tilings, make in _extras(dev):
+        run(c, tilings, make)
+    return out
+
+
+def test_gemm_bits_equal_the_recorded_launches(lib):
+    """Every launch writes, bit for bit, what the commit named in tests/golden/gemm_digests.json wrote (tests/record_gemm_digests.py, run
+    against a library built from that commit, records the file): a change of the kernels that is meant to keep their results keeps these."""
+    with open(DIGESTS) as f:
+        want = json.load(f)["digests"]
+    got = gemm_digests(lib)
+    assert sorted(got) == sorted(want), "the (case, tiling) launches differ from the recorded set"
+    bad = sorted(k for k in got if got[k] != want[k])
+    assert not bad, f"{len(bad)} of {len(got)} launches differ from the recorded bits: {bad[:12]}"
 
 
 # ------------------------------------------------------------------------------------------------------------ 2. the forward packers
