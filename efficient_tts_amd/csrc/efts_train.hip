@@ -77,7 +77,7 @@ __global__ void loss_bwd_kernel(const float* __restrict__ mp, long ldm, const fl
 __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ g, const float* __restrict__ y,
                                                       const float* __restrict__ x, const float* __restrict__ rowmask,
                                                       float slope, int mode, float* __restrict__ dz, char* __restrict__ plane,
-                                                      long ldp, int split, float* __restrict__ dbias, int bias_parts, int rows, int c,
+                                                      long ldp, int split, float* __restrict__ dbias, int bias_parts, int rows, int c, int kp,
                                                       unsigned drop_thresh, unsigned drop_seed_h, float drop_inv_keep) {
     // block: 64 rows x 128 columns (blockIdx.y = column group); 256 threads = 32 column quads x 8
     // rows in flight.  Column sums are combined in LDS first: ONE global atomic per column per
@@ -125,6 +125,8 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
             if (plane) plane_store4(plane + (long)r * ldp, c4, gv.x, gv.y, gv.z, gv.w, split);
             acc.x += gv.x; acc.y += gv.y; acc.z += gv.z; acc.w += gv.w;
         }
+        else if (plane && c4 < kp)                           // the plane's K padding c .. Kp: zero, as every plane producer leaves it
+            for (int r = r0 + rsub; r < r1; r += rpar) plane_store4(plane + (long)r * ldp, c4, 0.f, 0.f, 0.f, 0.f, split);
         if (dbias) {
             colsum[rsub][q * 4] = acc.x; colsum[rsub][q * 4 + 1] = acc.y;
             colsum[rsub][q * 4 + 2] = acc.z; colsum[rsub][q * 4 + 3] = acc.w;
@@ -646,8 +648,8 @@ __global__ __launch_bounds__(256) void pack_weight_t_kernel(const float* __restr
 // was 0.4 ms of a 5 ms step, almost all of it launch latency.
 struct PackItem { const float* w; const float* g; float* wout; char* plane; char* plane_t; };
 
-__global__ __launch_bounds__(256) void pack_weight_group_kernel(const PackItem* __restrict__ items, long ldb, int cout, int cin,
-                                                                int taps, int kp, int split) {
+__global__ __launch_bounds__(256) void pack_weight_group_kernel(const PackItem* __restrict__ items, float* __restrict__ scale_out, long ldb,
+                                                                int cout, int cin, int taps, int kp, int split) {
     __shared__ float sh[4];
     const PackItem it = items[blockIdx.y];
     const int co = blockIdx.x;
@@ -659,6 +661,7 @@ __global__ __launch_bounds__(256) void pack_weight_group_kernel(const PackItem* 
         ss = block_sum256t(ss, sh);
         scale = it.g[co] / sqrtf(ss);
     }
+    if (scale_out && threadIdx.x == 0) scale_out[(long)blockIdx.y * cout + co] = scale;    // for pack_weight_t_group_kernel
     if (it.wout)
         for (int i = threadIdx.x; i < cin * taps; i += 256) it.wout[(long)co * cin * taps + i] = wr[i] * scale;
     if (!it.plane) return;
@@ -671,18 +674,25 @@ __global__ __launch_bounds__(256) void pack_weight_group_kernel(const PackItem* 
     }
 }
 
-// transposed planes of the group; reads the folded copy when the item has one (written by the kernel above)
-__global__ __launch_bounds__(256) void pack_weight_t_group_kernel(const PackItem* __restrict__ items, long ldb, int cout, int cin,
-                                                                  int taps, int kp, int split) {
+// transposed planes of the group; reads the folded copy when the item has one (written by the kernel above).  A weight-normed item
+// without one is folded here, v * scale[co] with the scales the kernel above left in scale_ws: the same fp32 product as the folded copy
+// and as the tile kernel's.  Without scale_ws either there is nothing to fold with: the plane is NaN, loudly, instead of the unfolded v.
+__global__ __launch_bounds__(256) void pack_weight_t_group_kernel(const PackItem* __restrict__ items, const float* __restrict__ scale, long ldb,
+                                                                  int cout, int cin, int taps, int kp, int split) {
     const PackItem it = items[blockIdx.y];
     if (!it.plane_t) return;
+    const bool fold = it.g && !it.wout;
     const float* w = (it.g && it.wout) ? it.wout : it.w;
+    const float* sc = scale ? scale + (long)blockIdx.y * cout : nullptr;
     const int ci = blockIdx.x;
     for (int q = threadIdx.x; q < (kp >> 2) * taps; q += 256) {
         const int k = q / (kp >> 2), c4 = (q - k * (kp >> 2)) << 2;
         float v[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = (c4 + u < cout) ? w[((long)(c4 + u) * cin + ci) * taps + k] : 0.f;
+        for (int u = 0; u < 4; ++u) {
+            v[u] = (c4 + u < cout) ? w[((long)(c4 + u) * cin + ci) * taps + k] : 0.f;
+            if (fold && c4 + u < cout) v[u] = sc ? v[u] * sc[c4 + u] : __builtin_nanf("");
+        }
         plane_store4(it.plane_t + ((long)(taps - 1 - k) * cin + ci) * ldb, c4, v[0], v[1], v[2], v[3], split);
     }
 }
@@ -708,7 +718,7 @@ __global__ __launch_bounds__(256) void weight_scale_kernel(const PackItem* __res
 
 constexpr int PT_CO = 32, PT_CI = 64, PT_MAXT = 5;
 __global__ __launch_bounds__(256) void pack_weight_tile_kernel(const PackItem* __restrict__ items, const float* __restrict__ scale,
-                                                               long ldb, long ldb_t, int cout, int cin, int taps, int split) {
+                                                               long ldb, long ldb_t, int cout, int cin, int taps, int split, int with_t) {
     __shared__ float tile[PT_CO][PT_CI * PT_MAXT + 1];
     __shared__ float sc[PT_CO];
     const PackItem it = items[blockIdx.z];
@@ -732,7 +742,7 @@ __global__ __launch_bounds__(256) void pack_weight_tile_kernel(const PackItem* _
             const float* t = &tile[c][(4 * q) * taps + k];
             plane_store4(it.plane + ((long)k * cout + co0 + c) * ldb, ci0 + 4 * q, t[0] * s, t[taps] * s, t[2 * taps] * s, t[3 * taps] * s, split);
         }
-    if (it.plane_t)                             // [taps-1-k][ci][Kp(co)]: 8 threads per 32-co row piece
+    if (it.plane_t && with_t)                   // [taps-1-k][ci][Kp(co)]: 8 threads per 32-co row piece (with_t == 0: as the row path, no plane_t)
         for (int i = threadIdx.x; i < taps * PT_CI * (PT_CO / 4); i += 256) {
             const int q = i & 7, c = (i >> 3) & (PT_CI - 1), k = i >> 9;
             const int r = c * taps + k;
@@ -760,12 +770,13 @@ extern "C" int efts_pack_weights_grouped(const efts_pack_item* items, int32_t n_
     if (scale_ws && cout % 64 == 0 && cin % PT_CI == 0 && taps <= PT_MAXT) {
         hipLaunchKernelGGL(weight_scale_kernel, dim3(cout, n_items), dim3(256), 0, ST, (const PackItem*)items, scale_ws, cout, cin * taps);
         hipLaunchKernelGGL(pack_weight_tile_kernel, dim3(cout / PT_CO, cin / PT_CI, n_items), dim3(256), 0, ST, (const PackItem*)items,
-                           (const float*)scale_ws, (long)ldb, (long)ldb_t, cout, cin, taps, split);
+                           (const float*)scale_ws, (long)ldb, (long)ldb_t, cout, cin, taps, split, with_t);
         return efts_check_launch("efts_pack_weights_grouped");
     }
-    hipLaunchKernelGGL(pack_weight_group_kernel, dim3(cout, n_items), dim3(256), 0, ST, (const PackItem*)items, (long)ldb, cout, cin, taps, kp, split);
+    hipLaunchKernelGGL(pack_weight_group_kernel, dim3(cout, n_items), dim3(256), 0, ST, (const PackItem*)items, scale_ws, (long)ldb, cout, cin, taps, kp, split);
     if (with_t)
-        hipLaunchKernelGGL(pack_weight_t_group_kernel, dim3(cin, n_items), dim3(256), 0, ST, (const PackItem*)items, (long)ldb_t, cout, cin, taps, kpt, split);
+        hipLaunchKernelGGL(pack_weight_t_group_kernel, dim3(cin, n_items), dim3(256), 0, ST, (const PackItem*)items, (const float*)scale_ws, (long)ldb_t, cout,
+                           cin, taps, kpt, split);
     return efts_check_launch("efts_pack_weights_grouped");
 }
 
@@ -809,8 +820,11 @@ extern "C" int efts_act_bwd_dropout(const float* g, const float* y, const float*
         seed_h = hash_u32(drop_seed);
         inv_keep = 1.f / (1.f - drop_p);
     }
+    // Kp of the plane (<= the (c + 127) / 128 column groups of the grid): the kernel writes the K padding c .. Kp as zero
+    const int kp = split == 1 ? (c + 63) & ~63 : (c + 31) & ~31;
+    if (plane && ld_plane < (split == 1 ? kp * 2 : kp * 4)) return efts_fail(EFTS_ESHAPE, "efts_act_bwd: ld_plane too small for Kp(c) values");
     hipLaunchKernelGGL(act_bwd_kernel, dim3((rows + 63) / 64, (c + 127) / 128), dim3(256), 0, ST, g, y, x, rowmask, slope, mode, dz, (char*)plane, (long)ld_plane,
-                       split, dbias, parts, rows, c, thresh, seed_h, inv_keep);
+                       split, dbias, parts, rows, c, kp, thresh, seed_h, inv_keep);
     return efts_check_launch("efts_act_bwd");
 }
 

@@ -499,9 +499,12 @@ int efts_pack_weight_t(const float* w, void* plane, int64_t ldb, int32_t cout, i
  * efts_pack_weight (plane and/or w_f32_out; either may be NULL) and, with with_t != 0, efts_pack_weight_t into plane_t
  * (NULL = skip the item) from the folded weight.  `items` is an array in DEVICE memory.  scale_ws: n_items * cout
  * floats of device scratch (weight-norm scales); with it, shapes with cout % 64 == 0, cin % 64 == 0, taps <= 5 take
- * the tiled path (one pass over the weights writes both planes); NULL or other shapes: row kernels, which need
- * w_f32_out for a weight-normed item that has a plane_t.  The reference does this work implicitly per layer and
- * step: the weight_norm hook (efts_modules.py:92-99) in every forward, the transposed operand inside cuDNN's dgrad. */
+ * the tiled path (one pass over the weights writes both planes); NULL or other shapes: row kernels, which leave the
+ * scales in scale_ws too.  Both paths write the same bytes into plane, plane_t and w_f32_out.  PRECONDITION: a
+ * weight-normed item (g != NULL) that has a plane_t needs w_f32_out or scale_ws -- the row kernels fold plane_t from
+ * the one or the other; with neither they fill the item's plane_t with NaN instead of packing the unfolded weight.
+ * With with_t == 0 no plane_t is written on either path.  The reference does this work implicitly per layer and step:
+ * the weight_norm hook (efts_modules.py:92-99) in every forward, the transposed operand inside cuDNN's dgrad. */
 typedef struct efts_pack_item {
     const float* w;        /* [cout][cin][taps] fp32: weight_v, or the plain weight when g == NULL */
     const float* g;        /* weight-norm gain [cout] or NULL */
@@ -522,6 +525,7 @@ int efts_loss_bwd(const float* mel_pred, int64_t ldm, const float* speech, const
  * 5: LeakyReLU with the plain sign bits efts_resconv5 wrote (`sign_bits`) passed as y (row stride c / 8 bytes);
  * 4: LeakyReLU with the sign words efts_gemm wrote (`sign_mask` of the forward launch) passed as y (row stride c / 8 bytes,
  * c % 128 == 0), x unused.
+ * plane (optional): rows of Kp(c) values, the K padding c .. Kp written as zero; ld_plane >= the bytes of Kp values.
  * mode | EFTS_ACT_BWD_BIAS_PARTS: dbias is a [ceil(rows / 64)][c] workspace that receives one column sum per 64-row block
  * (plain stores, overwritten) instead of atomic adds into the gradient; efts_wgrad_reduce_grouped adds them up. */
 #define EFTS_ACT_BWD_BIAS_PARTS 16
