@@ -2,7 +2,7 @@
 
     python -m efficient_tts_amd.bin.vocoder_score --test_fid_scp test.txt --outdir exp/vocoder/score \\
         --vocoder griffinlim|hifigan [--vocoder_config c.json --vocoder_checkpoint g.pt] [--gl_iters 32] [--precision bf16x3]
-        [--batch_size 16] [--wav_path wavs/] [--denoise 0.01]
+        [--batch_size 16] [--wav_path wavs/] [--denoise 0.01] [--stoi]
 
 Copy-synthesis: recording -> log-mel (`LogMelFrontend`) -> vocoder (the `--vocoder` switches of `efficient_tts_amd.bin.inference`) -> audio,
 compared with the recording over min(len) samples by `MultiResolutionSTFTDistance` at the reference's three resolutions.  No acoustic
@@ -16,6 +16,12 @@ copy.  The numbers judge `--precision`, `--gl_iters` and vocoder checkpoints aga
 
 `--denoise S` (S > 0) passes the copy-synthesis through `efficient_tts_amd.denoise.BiasDenoiser` before it is scored, the bias measured once from
 the vocoder's answer to a blank mel: the table then says whether a strength helps or eats the signal.
+
+`--stoi` also scores every utterance's intelligibility with `efficient_tts_amd.stoi.ShortTimeIntelligibility` on the same (synthesis, recording,
+samples) -- behind the denoiser where `--denoise` is given --, the recording as the clean signal: every line of mrstft.tsv gains the columns stoi,
+estoi and stoi_kept_frames (the frames at 10 kHz left after silent-frame removal), the last line the means of the first two (and `-`), and
+the two means are printed.  The spectral distances do not say whether the speech stays intelligible; these two do (1 for a perfect copy, nan
+for an utterance with at most 30 kept frames).  Without the flag the file is byte for byte what it was.
 """
 from __future__ import annotations
 
@@ -44,6 +50,7 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--wav_path", type=str, default=None, help="directory searched, by file name, for a wav path that does not exist")
     p.add_argument("--denoise", type=float, default=None,
                    help="denoise the copy-synthesis before scoring: subtract this many times the vocoder's bias spectrum, for example 0.01 (default: off)")
+    p.add_argument("--stoi", action="store_true", help="also score STOI and ESTOI of the copy-synthesis against the recording (columns stoi, estoi, stoi_kept_frames)")
     return p
 
 
@@ -58,16 +65,35 @@ def check_args(args) -> None:
         raise ValueError("--denoise must be a finite strength > 0 (leave the flag out for no denoiser)")
 
 
-def columns(resolutions=DEFAULT_RESOLUTIONS):
-    """the columns of mrstft.tsv"""
+STOI_COLUMNS = ("stoi", "estoi", "stoi_kept_frames")
+
+
+def _mean_of_finite(col) -> float:
+    col = np.asarray(col, dtype=np.float64)
+    return float(np.mean(col[np.isfinite(col)])) if np.isfinite(col).any() else float("nan")
+
+
+def columns(resolutions=DEFAULT_RESOLUTIONS, stoi: bool = False):
+    """the columns of mrstft.tsv; `stoi`: with the three columns of --stoi behind them"""
     names = ["utt", "samples"]
     for n, h, w in resolutions:
         names += [f"sc_{n}_{h}_{w}", f"log_mag_{n}_{h}_{w}"]
-    return names + ["sc_mean", "log_mag_mean"]
+    return names + ["sc_mean", "log_mag_mean"] + (list(STOI_COLUMNS) if stoi else [])
 
 
-def format_rows(rows, resolutions=DEFAULT_RESOLUTIONS):
-    """the lines of mrstft.tsv from (utt, samples, sc [R], log_mag [R]) per utterance, and the two means that the last line ends with"""
+def format_rows(rows, resolutions=DEFAULT_RESOLUTIONS, stoi=None):
+    """the lines of mrstft.tsv from (utt, samples, sc [R], log_mag [R]) per utterance, and the two means that the last line ends with.
+    `stoi`: (stoi, estoi, kept frames) per utterance, in the rows' order: three more columns on every line (the last line: the means of the
+    first two over the utterances that have a value, and `-`); the return value then ends with those two means."""
+    if stoi is not None:
+        if len(stoi) != len(rows):
+            raise ValueError("stoi must hold one (stoi, estoi, kept frames) per row")
+        lines, sc_mean, lm_mean = format_rows(rows, resolutions)
+        for i, (s, e, kept) in enumerate(stoi):
+            lines[i] += "\t" + "\t".join([f"{float(s):.6f}", f"{float(e):.6f}", str(int(kept))])
+        s_mean, e_mean = _mean_of_finite([v[0] for v in stoi]), _mean_of_finite([v[1] for v in stoi])
+        lines[-1] += "\t" + "\t".join([f"{s_mean:.6f}", f"{e_mean:.6f}", "-"])
+        return lines, sc_mean, lm_mean, s_mean, e_mean
     lines, table = [], []
     for utt, n, sc, lm in rows:
         vals = [v for pair in zip(sc, lm) for v in pair] + [float(np.mean(sc)), float(np.mean(lm))]       # (nan in a resolution: nan in the mean)
@@ -107,8 +133,12 @@ def run_score(args):
         from efficient_tts_amd.denoise import BiasDenoiser
         denoiser = BiasDenoiser.from_vocoder(vocoder, device, strength=args.denoise)
     scorer = MultiResolutionSTFTDistance(device, max_wav_value=frontend.max_wav_value)
+    intelligibility = None
+    if args.stoi:
+        from efficient_tts_amd.stoi import ShortTimeIntelligibility
+        intelligibility = ShortTimeIntelligibility(device, SAMPLING_RATE, max_wav_value=frontend.max_wav_value)
     items = _read_paths(args.test_fid_scp)
-    rows = []
+    rows, stoi_rows = [], []
     for lo in range(0, len(items), args.batch_size):
         chunk = items[lo:lo + args.batch_size]
         wavs = [read_wav(path, args.wav_path, SAMPLING_RATE)[0] for _, path in chunk]
@@ -121,12 +151,20 @@ def run_score(args):
                 syn = denoiser(syn, (mel_len.to(wav_len.dtype) * frontend.hop).clamp(max=syn.shape[1]))
             n = torch.minimum(wav_len, mel_len.to(wav_len.dtype) * frontend.hop).clamp(max=min(syn.shape[1], audio.shape[1]))
             out = scorer(syn, audio, n)
+            if intelligibility is not None:                  # the recording is the clean signal, the copy-synthesis the processed one
+                si = intelligibility(audio, syn, n)
+                stoi_rows += list(zip(si["stoi"].tolist(), si["estoi"].tolist(), si["kept"].tolist()))
         for (utt, _), k, sc, lm in zip(chunk, n.tolist(), out["sc"].tolist(), out["log_mag"].tolist()):
             rows.append((utt, k, sc, lm))
-    lines, sc_mean, lm_mean = format_rows(rows)
+    if intelligibility is None:
+        lines, sc_mean, lm_mean = format_rows(rows)
+    else:
+        lines, sc_mean, lm_mean, stoi_mean, estoi_mean = format_rows(rows, stoi=stoi_rows)
     with open(os.path.join(args.outdir, "mrstft.tsv"), "w") as handle:
         handle.write("\n".join(lines) + "\n")
     print(f"copy-synthesis of {len(rows)} utterances with {args.vocoder}: mean spectral convergence {sc_mean:.4f}, mean log-magnitude distance {lm_mean:.4f}")
+    if intelligibility is not None:
+        print(f"intelligibility of the copy-synthesis against the recordings: mean STOI {stoi_mean:.4f}, mean ESTOI {estoi_mean:.4f}")
     return sc_mean, lm_mean
 
 

@@ -223,6 +223,9 @@ _SIGS = {
     # spectral subtraction of a vocoder's bias noise
     "efts_denoise_workspace_bytes": (i64, [i32, i32]),
     "efts_denoise": (i32, [vp, i64, vp, i32, vp, vp, f32, vp, i64, vp, vp, i64, i32, vp]),
+    # STOI and ESTOI intelligibility scores
+    "efts_stoi_workspace_bytes": (i64, [i32, i32]),
+    "efts_stoi": (i32, [vp, i64, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

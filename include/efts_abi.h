@@ -94,7 +94,9 @@ extern "C" {
  *        + efts_loudness, efts_loudness_pcm16, efts_loudness_workspace_bytes (BS.1770 integrated loudness and the gain to a target):
  *          exports added, the revision stays by the same rule
  *        + efts_denoise, efts_denoise_workspace_bytes (spectral subtraction of a vocoder's bias noise): exports added, the revision stays
- *          by the same rule */
+ *          by the same rule
+ *        + efts_stoi, efts_stoi_workspace_bytes (STOI and ESTOI intelligibility scores): exports added, the revision stays by the same
+ *          rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -1116,6 +1118,53 @@ int efts_loudness_pcm16(const int16_t* in, int64_t ld_in, const int32_t* lengths
 int64_t efts_denoise_workspace_bytes(int32_t B, int32_t max_len);
 int efts_denoise(const float* audio, int64_t ld, const int32_t* lengths, int32_t max_len, const float* window, const float* bias, float strength,
                  float* out, int64_t ld_out, int32_t* frames, void* workspace, int64_t workspace_bytes, int32_t B, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Short-time objective intelligibility: STOI (Taal, Hendriks, Heusdens, Jensen 2011) and ESTOI (Jensen, Taal 2016) of a processed signal y
+ * against the clean signal x, time-aligned and both at 10 000 Hz, as the authors' Matlab code computes them (which pystoi follows), quirks
+ * included.  Fixed configuration: frame 256, hop 128, FFT 512 (the frame followed by 256 zeros), J = 15 one-third-octave bands from 150 Hz,
+ * segments of N = 30 frames, beta = -15 dB, dynamic range 40 dB; the entry takes no argument that could ask for another one.
+ *   samples : fp32.  Item b is row b of x [B][ldx] and of y [B][ldy] and is compared over n = lengths[b], clamped to 0 .. max_len, samples;
+ *             nothing behind them is read.
+ *   window  : [256] fp32, DEVICE memory: w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / 257) (numpy's hanning(258)[1:-1]), computed by the caller in
+ *             float64 and rounded once.
+ *   1 frames   : F = (n - 256) / 128 + 1 when n >= 256, otherwise 0.  Frame f of a signal s is w[i] s[128 f + i], i = 0 .. 255.
+ *   2 silent frames, decided on x alone: e[f] = sum_i (w[i] x[128 f + i])^2 in fp32 -- lane l of a wave takes i = l + 64 j, j = 0 .. 3: s = 0,
+ *             v = w[i] x[..] (rounded), s = fmaf(v, v, s) in ascending j; then s += (s of lane l xor 32), xor 16, 8, 4, 2, 1.  e_max = max_f
+ *             e[f].  Frame f is kept iff (double) e[f] * 10^4 > (double) e_max, strictly: the reference's 20 log10 ||frame|| > max - 40
+ *             without a logarithm deciding anything, and without the eps inside the reference's logarithm, so an all-zero x keeps
+ *             nothing.  k_0 < k_1 < .. < k_(K-1) are the kept frames; the same frames are kept from y.
+ *   3 compacted signals: the kept windowed frames overlap-added at hop 128: xs[p] = sum over the at most two j that cover p, in ascending
+ *             j, of w[p - 128 j] x[128 k_j + p - 128 j] -- the older product rounded, the younger one fused onto it (fmaf) --; ys likewise.
+ *             They have 128 (K - 1) + 256 samples and never exist in memory.
+ *   4 spectral frames: T = K - 1 (the reference's loop stops before the last frame).  Frame t holds w[i] xs[128 t + i]; it needs the kept
+ *             frames k_(t-1) (second half; absent at t = 0), k_t and k_(t+1) (first half).  The x frame and the y frame run as ONE complex
+ *             512-point fp32 transform z = x frame + i y frame; X[f] = (Z[f] + conj Z[512 - f]) / 2, Y[f] = (Z[f] - conj Z[512 - f]) / 2i;
+ *             P[t][f] = fmaf(re, re, im im).
+ *   5 bands    : X[t][j] = sqrt(sum_{f = lo_j}^{hi_j - 1} P[t][f]), fp32, in ascending f, with [lo, hi) = [7,9) [9,11) [11,14) [14,17) [17,22)
+ *             [22,27) [27,34) [34,43) [43,55) [55,69) [69,87) [87,109) [109,138) [138,174) [174,219): the bins nearest to
+ *             150 2^((2 j -+ 1) / 6) Hz on the grid f 10000 / 512, upper bin excluded.  Y[t][j] likewise from y's spectrum.
+ *   6 segments : M = T - 29 = K - 30 when K > 30, otherwise there is none.  Segment m is the [15][30] block X[m .. m + 29][.] transposed, Y
+ *             likewise; from here on everything is float64, eps = 2^-52.  A sum over the 30 frames of a segment is the xor tree over 32
+ *             lanes (lane n holds frame n, lanes 30 and 31 hold 0: v += v of lane n xor 16, then 8, 4, 2, 1); a sum over the 15 bands
+ *             runs in ascending j.
+ *             STOI, per band j: c = ||x_j|| / (||y_j|| + eps); y' = min(c y_j, x_j (1 + 10^(15/20))); x_j and y' minus their means (sum / 30),
+ *             each divided by (its norm + eps); d_mj = sum over the frames of their product.  stoi = (sum_m (sum_j d_mj)) / (15 M).
+ *             ESTOI: both blocks are normalised alike: every row (a band over the 30 frames) minus its mean, divided by (its norm + eps);
+ *             then every column (a frame over the 15 bands) minus its mean (sum / 15), divided by (its norm + eps) (squares and products
+ *             summed with fma).  estoi = (sum_m (sum over the frames of (sum_j x~ y~))) / (30 M).
+ *             The segments' sums are added per item in ascending m.
+ *   stoi, estoi [B] float64; frames, kept, segments [B] int32: F, K and M.  An item without a segment (F = 0, K <= 30, an all-zero x) gets
+ *   NaN in both scores and segments = 0: the reference code warns and returns 1e-5 there.  The device decides; nothing is read back, no
+ *   launch geometry depends on device data, and the call can be captured.  ONE fixed order, no atomics: an item gives the same bits
+ *   alone, at any batch position and whatever lies behind its samples.
+ *   workspace: efts_stoi_workspace_bytes(B, max_len) bytes, 16-byte aligned; the size entry returns 0 for arguments that efts_stoi refuses.
+ * EFTS_EINVAL, nothing launched, the entry's name in efts_last_error(): a null pointer or one not aligned to its element, B outside
+ * 1 .. 65535, max_len outside 1 .. 2^31 - 8193, a leading dimension below max_len, a workspace smaller than the size entry asks for.
+ * ---------------------------------------------------------------------------------- */
+int64_t efts_stoi_workspace_bytes(int32_t B, int32_t max_len);
+int efts_stoi(const float* x, int64_t ldx, const float* y, int64_t ldy, const int32_t* lengths, int32_t max_len, const float* window, double* stoi,
+              double* estoi, int32_t* frames, int32_t* kept, int32_t* segments, void* workspace, int64_t workspace_bytes, int32_t B, void* stream);
 
 #ifdef __cplusplus
 }
