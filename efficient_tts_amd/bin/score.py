@@ -3,7 +3,7 @@
     python -m efficient_tts_amd.bin.score --checkpoint exp/efts/checkpoint-100000steps.pkl --test_fid_scp test.txt --outdir exp/efts/score \\
         [--config exp/efts/config.yml] [--batch_size 16] [--precision bf16x3] [--length_scale 1.0]
         [--f0 --vocoder griffinlim|hifigan [--vocoder_config c.json --vocoder_checkpoint g.pt] [--gl_iters 32] [--f0_min 60] [--f0_max 600] [--f0_threshold 0.15] [--f0_smooth]]
-        [--trim_silence [--trim_top_db 40]] [--normalize_peak 0.95]
+        [--trim_silence [--trim_top_db 40]] [--normalize_peak 0.95] [--mcd_wave]
 
 Reads the `wav_path|phonemes` list of `efficient_tts_amd.bin.inference` (16-bit wav files at the front-end's rate; a path that does not
 exist is looked up by its file name under dataset_params.wav_path).  Per batch, on the device: the recordings' log-mels (`LogMelFrontend`
@@ -23,8 +23,14 @@ instead of YIN's frame-by-frame rule, whose octave errors of 1200 cents each oth
 recordings carries no silence at its ends, and the recordings it is scored against should not either.  mcd.tsv then ends every line with two
 more columns, ref_trim_start and ref_trim_len (samples), and "-" in them on the line of the means.  Without the flags nothing changes.
 
-The numbers compare checkpoints of this project with each other (natural-log mels of this front-end); they are not comparable to MCDs
-computed from SPTK cepstra of waveforms.
+`--mcd_wave` adds the number that papers report: the synthesis is vocoded (the same `--vocoder` switches, required as for `--f0`) and
+`efficient_tts_amd.mcep.WaveformMCD` scores it against the recording -- order-24 all-pass-warped mel-cepstra of the two waveforms along their own
+warping path, behind `--trim_silence` / `--normalize_peak` where those are given; there is no per-frame silence gating.  Every line of mcd.tsv
+ends with two more columns, mcd_wave_db and mcd_wave_path_len, the last line with the mean of the first (and `-`).  Without the flag nothing
+changes.
+
+The numbers of the first column compare checkpoints of this project with each other (natural-log mels of this front-end); they are not
+comparable to MCDs computed from SPTK cepstra of waveforms.  The `--mcd_wave` column is the literature's definition by the periodogram route.
 """
 from __future__ import annotations
 
@@ -39,6 +45,7 @@ from efficient_tts_amd.bin._io import read_wav
 from efficient_tts_amd.bin.inference import SAMPLING_RATE, _read_list, build_vocoder, load_acoustic_model
 from efficient_tts_amd.frontend import LogMelFrontend
 from efficient_tts_amd.pitch import PitchTracker, lag_range
+from efficient_tts_amd.mcep import WaveformMCD
 from efficient_tts_amd.score import F0Error, MelCepstralDistortion
 from efficient_tts_amd.trim import SilenceTrimmer
 
@@ -65,6 +72,8 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--trim_silence", action="store_true", help="cut the silence at both ends of every recording before it is scored against")
     p.add_argument("--trim_top_db", type=float, default=40.0, help="--trim_silence: a frame this far under the loudest one is silence (default 40)")
     p.add_argument("--normalize_peak", type=float, default=None, help="bring every recording to this peak, in (0, 1], before it is scored against")
+    p.add_argument("--mcd_wave", action="store_true",
+                   help="also score mel-cepstral distortion between the vocoded synthesis and the recording (needs the --vocoder switches, as --f0 does)")
     return p
 
 
@@ -79,17 +88,51 @@ def check_f0_args(args, front=None) -> None:
     """--f0 needs audio of the synthesis that means something: refused on the host, before anything is loaded"""
     if args.f0_smooth and not args.f0:
         raise ValueError("--f0_smooth smooths the contours that --f0 scores: give --f0 as well")
-    if not args.f0:
+    mcd_wave = getattr(args, "mcd_wave", False)
+    if not args.f0 and not mcd_wave:
         return
+    flag = "--f0" if args.f0 else "--mcd_wave"
     if args.vocoder == "hifigan" and not (args.vocoder_checkpoint and args.vocoder_config):
-        raise ValueError("--f0 needs audio of the synthesis: give --vocoder griffinlim, or --vocoder hifigan with --vocoder_checkpoint and "
-                         "--vocoder_config (a generator with random weights has no pitch to score)")
+        raise ValueError(f"{flag} needs audio of the synthesis: give --vocoder griffinlim, or --vocoder hifigan with --vocoder_checkpoint and "
+                         f"--vocoder_config (a generator with random weights has no {'pitch' if args.f0 else 'spectrum'} to score)")
     if front is not None:
         rate, n_fft, hop = int(front.get("sampling_rate", SAMPLING_RATE)), int(front.get("n_fft", 1024)), int(front.get("hop_size", 256))
         if (rate, n_fft, hop) != (SAMPLING_RATE, 1024, 256):
-            raise ValueError(f"--f0: the vocoders produce {SAMPLING_RATE} Hz audio of 256 samples per frame; the recipe's front-end has "
+            raise ValueError(f"{flag}: the vocoders produce {SAMPLING_RATE} Hz audio of 256 samples per frame; the recipe's front-end has "
                              f"sampling_rate {rate}, n_fft {n_fft}, hop_size {hop}")
-        lag_range(rate, n_fft, args.f0_min, args.f0_max)
+        if args.f0:
+            lag_range(rate, n_fft, args.f0_min, args.f0_max)
+
+
+def _mean_of_finite(values) -> float:
+    values = [v for v in values if np.isfinite(v)]
+    return float(np.mean(values)) if values else float("nan")
+
+
+def format_lines(rows, extra=None, cuts=None, wave=None):
+    """the lines of mcd.tsv from (utt, mcd, frames synthesised, frames recorded, path length) per utterance; the last line holds the means.
+    `extra`: (f0_rmse_cents, vuv_error, voiced_pairs) per utterance (--f0); `cuts`: (start, length) per recording (--trim_silence /
+    --normalize_peak); `wave`: (mcd_wave_db, mcd_wave_path_len) per utterance (--mcd_wave).  Each adds its columns behind those before it."""
+    for name, col in (("extra", extra), ("cuts", cuts), ("wave", wave)):
+        if col is not None and len(col) != len(rows):
+            raise ValueError(f"{name} must hold one entry per row")
+    lines = []
+    for i, (utt, m, a, b, n) in enumerate(rows):
+        tail = f"\t{extra[i][0]:.4f}\t{extra[i][1]:.6f}\t{extra[i][2]}" if extra is not None else ""
+        if cuts is not None:
+            tail += f"\t{cuts[i][0]}\t{cuts[i][1]}"
+        if wave is not None:
+            tail += f"\t{float(wave[i][0]):.6f}\t{int(wave[i][1])}"
+        lines.append(f"{utt}\t{m:.6f}\t{a}\t{b}\t{n}{tail}")
+    tail = ""
+    if extra is not None:
+        tail = f"\t{_mean_of_finite([e[0] for e in extra]):.4f}\t{_mean_of_finite([e[1] for e in extra]):.6f}\t{_mean_of_finite([e[2] for e in extra]):.1f}"
+    if cuts is not None:
+        tail += "\t-\t-"
+    if wave is not None:
+        tail += f"\t{_mean_of_finite([w[0] for w in wave]):.6f}\t-"
+    lines.append(f"mean\t{_mean_of_finite([r[1] for r in rows]):.6f}{tail}")
+    return lines
 
 
 def run_score(args) -> float:
@@ -107,15 +150,18 @@ def run_score(args) -> float:
     scorer = MelCepstralDistortion(device, num_mels=frontend.n_mels)
     check_f0_args(args, front)
     trimmer = build_trimmer(args, frontend.hop, frontend.max_wav_value, device)
-    if args.f0:
+    if args.f0 or args.mcd_wave:
         vocoder = build_vocoder(args, device)
+    if args.mcd_wave:
+        wave_scorer = WaveformMCD(device, sampling_rate=rate, hop_size=frontend.hop, max_wav_value=frontend.max_wav_value)
+    if args.f0:
         tracker = PitchTracker(device, sampling_rate=rate, n_fft=frontend.n_fft, hop_size=frontend.hop, fmin=args.f0_min, fmax=args.f0_max,
                                threshold=args.f0_threshold, max_wav_value=frontend.max_wav_value, smooth=args.f0_smooth)
         f0_error = F0Error(device)
     wav_dir = (config.get("dataset_params") or {}).get("wav_path")
     items = _read_list(args.test_fid_scp, phn2idx, with_paths=True)
     bs = max(1, int(args.batch_size))
-    rows, extra, cuts = [], [], []
+    rows, extra, cuts, wave = [], [], [], []
     for lo in range(0, len(items), bs):
         chunk = items[lo:lo + bs]
         wavs = [read_wav(path, wav_dir, rate)[0] for _, _, path in chunk]
@@ -130,8 +176,12 @@ def run_score(args) -> float:
             syn, syn_len = model.inference_batch(ids.to(device), torch.tensor([len(t) for _, t, _ in chunk], device=device),
                                                  length_scale=args.length_scale)[:2]
             out = scorer(syn, syn_len, rec, rec_len, return_path=True) if args.f0 else scorer(syn, syn_len, rec, rec_len)
-            if args.f0:
+            if args.f0 or args.mcd_wave:
                 wav = vocoder(syn.transpose(1, 2).contiguous(), syn_len)[:, 0].float()
+            if args.mcd_wave:                      # the vocoded synthesis against the recording (trimmed where the flags say so), along their own path
+                wave_out = wave_scorer(wav, (syn_len * frontend.hop).clamp(max=wav.shape[1]), audio.to(device), wav_len)
+                wave.extend(zip(wave_out["mcd"].tolist(), wave_out["count"].tolist()))
+            if args.f0:
                 f0_syn = tracker(wav, syn_len * frontend.hop, max_frames=syn.shape[1], short_ok=True)[0]
                 f0_rec = tracker(audio, wav_len, max_frames=rec.shape[1])[0]
                 pitch = f0_error(f0_syn, f0_rec, out["path"], out["path_len"])
@@ -142,19 +192,14 @@ def run_score(args) -> float:
     mean = float(np.mean(scored)) if scored else float("nan")
     mean_of = lambda k: float(np.mean([e[k] for e in extra if np.isfinite(e[k])])) if any(np.isfinite(e[k]) for e in extra) else float("nan")
     with open(os.path.join(args.outdir, "mcd.tsv"), "w") as handle:
-        for i, (utt, m, a, b, n) in enumerate(rows):
-            tail = f"\t{extra[i][0]:.4f}\t{extra[i][1]:.6f}\t{extra[i][2]}" if args.f0 else ""
-            if trimmer is not None:
-                tail += f"\t{cuts[i][0]}\t{cuts[i][1]}"
-            handle.write(f"{utt}\t{m:.6f}\t{a}\t{b}\t{n}{tail}\n")
-        tail = f"\t{mean_of(0):.4f}\t{mean_of(1):.6f}\t{mean_of(2):.1f}" if args.f0 else ""
-        if trimmer is not None:
-            tail += "\t-\t-"
-        handle.write(f"mean\t{mean:.6f}{tail}\n")
+        handle.write("\n".join(format_lines(rows, extra if args.f0 else None, cuts if trimmer is not None else None, wave if args.mcd_wave else None)) + "\n")
     print(f"mean MCD over {len(scored)} of {len(rows)} utterances: {mean:.4f} dB")
     if args.f0:
         print(f"mean F0 error {mean_of(0):.2f} cents over {sum(np.isfinite(e[0]) for e in extra)} utterances with a voiced pair, "
               f"mean voiced/unvoiced error {mean_of(1):.4f}")
+    if args.mcd_wave:
+        print(f"mean waveform MCD (order-24 mel-cepstra, warped) over {sum(np.isfinite(w[0]) for w in wave)} of {len(rows)} utterances: "
+              f"{_mean_of_finite([w[0] for w in wave]):.4f} dB")
     return mean
 
 

@@ -2,7 +2,7 @@
 
     python -m efficient_tts_amd.bin.vocoder_score --test_fid_scp test.txt --outdir exp/vocoder/score \\
         --vocoder griffinlim|hifigan [--vocoder_config c.json --vocoder_checkpoint g.pt] [--gl_iters 32] [--precision bf16x3]
-        [--batch_size 16] [--wav_path wavs/] [--denoise 0.01] [--stoi]
+        [--batch_size 16] [--wav_path wavs/] [--denoise 0.01] [--stoi] [--mcd]
 
 Copy-synthesis: recording -> log-mel (`LogMelFrontend`) -> vocoder (the `--vocoder` switches of `efficient_tts_amd.bin.inference`) -> audio,
 compared with the recording over min(len) samples by `MultiResolutionSTFTDistance` at the reference's three resolutions.  No acoustic
@@ -22,6 +22,12 @@ samples) -- behind the denoiser where `--denoise` is given --, the recording as 
 estoi and stoi_kept_frames (the frames at 10 kHz left after silent-frame removal), the last line the means of the first two (and `-`), and
 the two means are printed.  The spectral distances do not say whether the speech stays intelligible; these two do (1 for a perfect copy, nan
 for an utterance with at most 30 kept frames).  Without the flag the file is byte for byte what it was.
+
+`--mcd` also scores the mel-cepstral distortion that vocoder papers report, `efficient_tts_amd.mcep.WaveformMCD` in aligned mode (copy-synthesis
+shares the recording's time axis: frame t against frame t, no warping) on the same (synthesis, recording, samples), behind the denoiser where
+`--denoise` is given: order-24 all-pass-warped mel-cepstra of both waveforms by the periodogram route, every frame counted (no silence gating).
+Every line gains the columns mcd_db and mcd_frames -- behind the `--stoi` columns when both are given --, the last line the mean of the first
+(and `-`), and the mean is printed.  Without the flag the file is byte for byte what it was.
 """
 from __future__ import annotations
 
@@ -51,6 +57,7 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--denoise", type=float, default=None,
                    help="denoise the copy-synthesis before scoring: subtract this many times the vocoder's bias spectrum, for example 0.01 (default: off)")
     p.add_argument("--stoi", action="store_true", help="also score STOI and ESTOI of the copy-synthesis against the recording (columns stoi, estoi, stoi_kept_frames)")
+    p.add_argument("--mcd", action="store_true", help="also score the mel-cepstral distortion of the copy-synthesis against the recording, frame by frame (columns mcd_db, mcd_frames)")
     return p
 
 
@@ -66,6 +73,7 @@ def check_args(args) -> None:
 
 
 STOI_COLUMNS = ("stoi", "estoi", "stoi_kept_frames")
+MCD_COLUMNS = ("mcd_db", "mcd_frames")
 
 
 def _mean_of_finite(col) -> float:
@@ -73,18 +81,29 @@ def _mean_of_finite(col) -> float:
     return float(np.mean(col[np.isfinite(col)])) if np.isfinite(col).any() else float("nan")
 
 
-def columns(resolutions=DEFAULT_RESOLUTIONS, stoi: bool = False):
-    """the columns of mrstft.tsv; `stoi`: with the three columns of --stoi behind them"""
+def columns(resolutions=DEFAULT_RESOLUTIONS, stoi: bool = False, mcd: bool = False):
+    """the columns of mrstft.tsv; `stoi`: with the three columns of --stoi behind them; `mcd`: with the two columns of --mcd behind those"""
     names = ["utt", "samples"]
     for n, h, w in resolutions:
         names += [f"sc_{n}_{h}_{w}", f"log_mag_{n}_{h}_{w}"]
-    return names + ["sc_mean", "log_mag_mean"] + (list(STOI_COLUMNS) if stoi else [])
+    return names + ["sc_mean", "log_mag_mean"] + (list(STOI_COLUMNS) if stoi else []) + (list(MCD_COLUMNS) if mcd else [])
 
 
-def format_rows(rows, resolutions=DEFAULT_RESOLUTIONS, stoi=None):
+def format_rows(rows, resolutions=DEFAULT_RESOLUTIONS, stoi=None, mcd=None):
     """the lines of mrstft.tsv from (utt, samples, sc [R], log_mag [R]) per utterance, and the two means that the last line ends with.
     `stoi`: (stoi, estoi, kept frames) per utterance, in the rows' order: three more columns on every line (the last line: the means of the
-    first two over the utterances that have a value, and `-`); the return value then ends with those two means."""
+    first two over the utterances that have a value, and `-`); the return value then ends with those two means.
+    `mcd`: (mcd in dB, frames compared) per utterance: two more columns behind everything else (the last line: the mean of the first over
+    the utterances that have a value, and `-`); the return value then ends with that mean."""
+    if mcd is not None:
+        if len(mcd) != len(rows):
+            raise ValueError("mcd must hold one (mcd in dB, frames) per row")
+        lines, *means = format_rows(rows, resolutions, stoi)
+        for i, (m, frames) in enumerate(mcd):
+            lines[i] += f"\t{float(m):.6f}\t{int(frames)}"
+        m_mean = _mean_of_finite([v[0] for v in mcd])
+        lines[-1] += f"\t{m_mean:.6f}\t-"
+        return (lines, *means, m_mean)
     if stoi is not None:
         if len(stoi) != len(rows):
             raise ValueError("stoi must hold one (stoi, estoi, kept frames) per row")
@@ -137,8 +156,12 @@ def run_score(args):
     if args.stoi:
         from efficient_tts_amd.stoi import ShortTimeIntelligibility
         intelligibility = ShortTimeIntelligibility(device, SAMPLING_RATE, max_wav_value=frontend.max_wav_value)
+    distortion = None
+    if args.mcd:
+        from efficient_tts_amd.mcep import WaveformMCD
+        distortion = WaveformMCD(device, sampling_rate=SAMPLING_RATE, max_wav_value=frontend.max_wav_value)
     items = _read_paths(args.test_fid_scp)
-    rows, stoi_rows = [], []
+    rows, stoi_rows, mcd_rows = [], [], []
     for lo in range(0, len(items), args.batch_size):
         chunk = items[lo:lo + args.batch_size]
         wavs = [read_wav(path, args.wav_path, SAMPLING_RATE)[0] for _, path in chunk]
@@ -154,17 +177,22 @@ def run_score(args):
             if intelligibility is not None:                  # the recording is the clean signal, the copy-synthesis the processed one
                 si = intelligibility(audio, syn, n)
                 stoi_rows += list(zip(si["stoi"].tolist(), si["estoi"].tolist(), si["kept"].tolist()))
+            if distortion is not None:                       # one time axis: frame t of the copy-synthesis against frame t of the recording
+                md = distortion(syn, n, audio, n, aligned=True)
+                mcd_rows += list(zip(md["mcd"].tolist(), md["count"].tolist()))
         for (utt, _), k, sc, lm in zip(chunk, n.tolist(), out["sc"].tolist(), out["log_mag"].tolist()):
             rows.append((utt, k, sc, lm))
     if intelligibility is None:
-        lines, sc_mean, lm_mean = format_rows(rows)
+        lines, sc_mean, lm_mean, *more = format_rows(rows, mcd=mcd_rows if distortion is not None else None)
     else:
-        lines, sc_mean, lm_mean, stoi_mean, estoi_mean = format_rows(rows, stoi=stoi_rows)
+        lines, sc_mean, lm_mean, stoi_mean, estoi_mean, *more = format_rows(rows, stoi=stoi_rows, mcd=mcd_rows if distortion is not None else None)
     with open(os.path.join(args.outdir, "mrstft.tsv"), "w") as handle:
         handle.write("\n".join(lines) + "\n")
     print(f"copy-synthesis of {len(rows)} utterances with {args.vocoder}: mean spectral convergence {sc_mean:.4f}, mean log-magnitude distance {lm_mean:.4f}")
     if intelligibility is not None:
         print(f"intelligibility of the copy-synthesis against the recordings: mean STOI {stoi_mean:.4f}, mean ESTOI {estoi_mean:.4f}")
+    if distortion is not None:
+        print(f"mel-cepstral distortion of the copy-synthesis against the recordings (order-24 mel-cepstra, frame by frame): mean MCD {more[0]:.4f} dB")
     return sc_mean, lm_mean
 
 

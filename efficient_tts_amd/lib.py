@@ -226,6 +226,9 @@ _SIGS = {
     # STOI and ESTOI intelligibility scores
     "efts_stoi_workspace_bytes": (i64, [i32, i32]),
     "efts_stoi": (i32, [vp, i64, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp]),
+    # a linear map of every frame's log power spectrum (waveform mel-cepstra) and the distance between frames paired one to one
+    "efts_logspec_project": (i32, [vp, i32, f32, i64, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp]),
+    "efts_frame_dist": (i32, [vp, i64, i64, vp, i32, vp, i64, i64, vp, i32, i32, vp, vp, i32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -179,7 +179,8 @@ class MelCepstralDistortion:
     `return_path=True` runs `dtw_path` in the place of `dtw` and adds `path` [B, Ta + Tb - 1, 2]; every other entry keeps its bits.
 
     The mels are this project's natural-log mels: the numbers compare checkpoints of this project with each other and are not comparable
-    to MCDs computed from SPTK cepstra of waveforms."""
+    to MCDs computed from SPTK cepstra of waveforms.  `efficient_tts_amd.mcep.WaveformMCD` computes the literature's number, from
+    order-24 all-pass-warped mel-cepstra of the two waveforms."""
 
     def __init__(self, device, num_mels: int = 80, n_coef: int = 13):
         self.dev = torch.device(device)

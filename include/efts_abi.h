@@ -96,7 +96,9 @@ extern "C" {
  *        + efts_denoise, efts_denoise_workspace_bytes (spectral subtraction of a vocoder's bias noise): exports added, the revision stays
  *          by the same rule
  *        + efts_stoi, efts_stoi_workspace_bytes (STOI and ESTOI intelligibility scores): exports added, the revision stays by the same
- *          rule */
+ *          rule
+ *        + efts_logspec_project, efts_frame_dist (waveform mel-cepstra and the distance between frames paired one to one): exports added,
+ *          the revision stays by the same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -1165,6 +1167,45 @@ int efts_denoise(const float* audio, int64_t ld, const int32_t* lengths, int32_t
 int64_t efts_stoi_workspace_bytes(int32_t B, int32_t max_len);
 int efts_stoi(const float* x, int64_t ldx, const float* y, int64_t ldy, const int32_t* lengths, int32_t max_len, const float* window, double* stoi,
               double* estoi, int32_t* frames, int32_t* kept, int32_t* segments, void* workspace, int64_t workspace_bytes, int32_t B, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * A linear map of the log power spectrum of every frame of a waveform batch, in one launch, and the summed distance between the frames of
+ * two feature sequences paired one to one.  With the table of efficient_tts_amd/mcep.py the first gives mel-cepstra of waveforms -- the
+ * all-pass frequency transform (Oppenheim's recursion, SPTK's freqt) of the FFT cepstrum of the periodogram, without the level c0 -- and
+ * both give the mel-cepstral distortion that TTS and vocoder papers report.  The entries themselves know nothing about cepstra.
+ * efts_logspec_project:
+ *   framing : that of efts_stft_mag, exactly, at N = 1024 only: hop 1 <= H <= N, the periodic Hann window [W] (2 <= W <= N, DEVICE memory)
+ *             with (N - W) / 2 zeros in front, reflect padding without edge repeat, T = 1 + len / H frames when len > N / 2 and none
+ *             otherwise, len = lengths[b] clamped to 0 .. max_len, int16 PCM (pcm16 != 0) multiplied by pcm_scale at the load, frames 2 p
+ *             and 2 p + 1 through one complex transform.  Nothing behind an item's samples is read.
+ *   power   : P[t][f] = max(re^2 + im^2, 1e-7) for f = 0 .. K, K = N / 2 -- the clamp of efts_stft_mag, applied before its square root, the
+ *             same bits -- and L[t][f] = ln P[t][f] (fp32 logf).
+ *   project : out[b][t][k] = sum_f table[k][f] L[t][f], k < n_coef; table [n_coef][K + 1] fp32 in DEVICE memory, 1 <= n_coef <= 32.
+ *             fp32, ONE fixed order: lane l of 64 starts from 0 and takes its bins f = l, l + 64, .., (lane 0: .., 512) in ascending order,
+ *             s = fma(table[k][f], L[f], s); the 64 lane sums are combined by v = v + (the v of the lane 32 across), then 16, .., 1 across.
+ *   out [B][T_max][n_coef], T_max = 1 + max_len / H; rows at and beyond an item's T are 0.  frames [B] int32: T.
+ *   No spectrum goes to memory, no atomics, no launch geometry from device data; the call can be captured.  An item gives the same bits
+ *   alone, at any batch position, in any run and whatever lies behind its samples.
+ *   The table of mel-cepstra (built by the caller in float64, rounded once to fp32): rows 1 .. M of  1/2 A(alpha) diag(w) D,  where
+ *   D[n][f] = s_f cos(pi n f / K) / K with s_0 = s_K = 1 and s_f = 2 otherwise, w_0 = w_K = 1/2 and w_n = 1 otherwise -- so that
+ *   c = diag(w) D ln|X| is the one-sided cepstrum, ln|X(w_f)| = sum_{n = 0 .. K} c[n] cos(n w_f) exactly, and the factor 1/2 turns ln P
+ *   into ln|X| --, and A(alpha) is the (M + 1) x (K + 1) matrix of the recursion: g = 0, beta = 1 - alpha^2; for i = K down to 0, with d the
+ *   previous g:  g[0] = c[i] + alpha d[0],  g[1] = beta d[0] + alpha d[1],  g[j] = d[j - 1] + alpha (d[j] - g[j - 1]) for j = 2 .. M.
+ *   Row 0, the level, is left out, as efts_mel_cepstrum leaves it out.
+ * efts_frame_dist: x [B] items of rows of D <= 32 fp32 (row stride ldx, item stride x_item_stride, in elements), x_frames [B] int32 clamped
+ *   to 0 .. Tx; y likewise.  n = min of the two clamped frame counts;  cost[b] (float64) = sum over t = 0 .. n - 1, in ascending t, one
+ *   float64 addition per frame, of d(t, t), the local cost of efts_dtw: sqrt (correctly rounded, fp32) of s = fma(x[t][k] - y[t][k], the same,
+ *   s) over ascending k.  count[b] = n.  An item without frames gets NaN and 0.  One workgroup per item, no atomics; rows at and beyond n
+ *   are never read.
+ * From either, mcd = (10 / ln 10) sqrt(2) cost / count dB, cost and count those of efts_dtw (warped) or of efts_frame_dist (aligned).
+ * Nothing launched and the entry's name in efts_last_error(): EFTS_ESHAPE for N other than 1024, H, W, n_coef, D or B (1 .. 65535) out of
+ * range, max_len outside 1 .. 2^31 - 8193, a leading dimension below max_len, a row stride below D, a negative item stride, Tx or Ty below 1;
+ * EFTS_EINVAL for a null pointer or one not aligned to its element.
+ * ---------------------------------------------------------------------------------- */
+int efts_logspec_project(const void* audio, int32_t pcm16, float pcm_scale, int64_t ld, const int32_t* lengths, int32_t max_len, const float* window,
+                         const float* table, int32_t n_coef, float* out, int32_t* frames, int32_t B, int32_t N, int32_t H, int32_t W, void* stream);
+int efts_frame_dist(const float* x, int64_t ldx, int64_t x_item_stride, const int32_t* x_frames, int32_t Tx, const float* y, int64_t ldy,
+                    int64_t y_item_stride, const int32_t* y_frames, int32_t Ty, int32_t D, double* cost, int32_t* count, int32_t B, void* stream);
 
 #ifdef __cplusplus
 }
