@@ -32,6 +32,7 @@ from efficient_tts_amd import datasets, models, optimizers, schedulers, trainers
 from efficient_tts_amd.dist import DistributedEFTS
 from efficient_tts_amd.frontend import LogMelFrontend
 from efficient_tts_amd.resample import Resampler
+from efficient_tts_amd.denoise import SpectralGate
 from efficient_tts_amd.loudness import LoudnessNormalizer
 from efficient_tts_amd.trim import SilenceTrimmer
 
@@ -134,6 +135,28 @@ def build_trimmer(config: Dict[str, Any], device=None) -> Optional[SilenceTrimme
                           peak=None if peak is None else float(peak), max_wav_value=float(front.get("max_wav_value", 32768.0)), trim=trim)
 
 
+_GATE_KEYS = ("denoise_strength", "denoise_floor", "denoise_top_db", "denoise_min_frames")
+
+
+def build_gate(config: Dict[str, Any], device=None) -> Optional[SpectralGate]:
+    """the SpectralGate that the recipe asks for; None without `denoise_corpus: true`.  Every recording is gated with the noise profile
+    measured from its own quiet frames: `denoise_strength` (default 1.0) times the profile is subtracted from the magnitudes,
+    `denoise_floor` (default 0.1) bounds the gain from below, `denoise_top_db` (default 40.0) under the loudest frame is quiet, and a recording
+    with fewer than `denoise_min_frames` (default 8) quiet frames is left as it is.  One of these keys without `denoise_corpus` is refused."""
+    on = config.get("denoise_corpus", False)
+    if not isinstance(on, bool):
+        raise ValueError(f"denoise_corpus must be true or false, got {on!r}")
+    if not on:
+        stray = [k for k in _GATE_KEYS if k in config]
+        if stray:
+            raise ValueError(f"{', '.join(stray)}: set without denoise_corpus: true")
+        return None
+    front = config.get("frontend_params") or {}
+    return SpectralGate(device, strength=config.get("denoise_strength", 1.0), floor=config.get("denoise_floor", 0.1),
+                        top_db=config.get("denoise_top_db", 40.0), min_frames=config.get("denoise_min_frames", 8),
+                        max_wav_value=float(front.get("max_wav_value", 32768.0)))
+
+
 def build_loudness(config: Dict[str, Any], device=None) -> Optional[LoudnessNormalizer]:
     """the LoudnessNormalizer that the recipe asks for, at the front-end's rate; None without `normalize_loudness`.
     `normalize_loudness: -23.0` brings every recording to that integrated loudness in LUFS (ITU-R BS.1770), `loudness_peak_ceiling`
@@ -176,6 +199,11 @@ def _build_trainer(config: Dict[str, Any], loaders, samplers, proc: _Process):
         trainer.resampler = Resampler(device, int(source_rate), front_rate, quality=config.get("resample_quality", "best"),
                                       max_wav_value=float(front.get("max_wav_value", 32768.0)))
         logging.info(f"resampling {source_rate} -> {front_rate} Hz on the device ({trainer.resampler.quality})")
+    trainer.gate = build_gate(config, device)
+    if trainer.gate is not None:
+        g = trainer.gate
+        logging.info(f"on the device, per recording: noise profile from the frames {g.top_db} dB under the loudest, {g.strength} x subtracted, "
+                     f"gain floor {g.floor}, untouched under {g.min_frames} noise frames")
     trainer.trimmer = build_trimmer(config, device)
     if trainer.trimmer is not None:
         t = trainer.trimmer
@@ -200,6 +228,7 @@ def main(argv=None) -> int:
     _setup_logging(args.verbose, quiet=proc.rank != 0)
     config = _load_config(args, proc)
     build_loudness(config)                     # a recipe that sets the level twice is refused here, before any data is read
+    build_gate(config)                         # likewise a gate key that is out of range or stands without `denoise_corpus`
     loaders, samplers = _build_data(config, args, proc)
     trainer = _build_trainer(config, loaders, samplers, proc)
     if args.pretrain:

@@ -12,6 +12,10 @@ which is torch.stft(center=True, pad_mode="reflect") -> gain -> torch.istft(cent
 passed through bit for bit.  include/efts_abi.h has the full definition, the order of every sum included.  It runs in csrc/efts_denoise.hip
 (`efts_denoise`) as ONE launch: no spectrum and no frame goes to memory, no atomics, nothing read back by the host.  No CPU path: the HIP
 library is required.
+
+For corpora the same chain runs as a spectral gate with a noise profile per recording: `NoiseProfile` measures the mean magnitude spectrum
+of an item's own quiet frames (`efts_noise_profile`), `SpectralGate` subtracts `strength` times it with a floor under the gain
+(`efts_spectral_gate`, the same kernel body) and leaves an item without enough quiet frames as it came.
 """
 from __future__ import annotations
 
@@ -34,6 +38,27 @@ def check_strength(value) -> float:
     if not (s >= 0.0 and math.isfinite(s)):
         raise ValueError(f"strength must be a finite number >= 0, got {value!r}")
     return s
+
+
+def check_floor(value) -> float:
+    f = float(value)
+    if not 0.0 <= f <= 1.0:
+        raise ValueError(f"floor must lie in 0 .. 1, got {value!r}")
+    return f
+
+
+def check_top_db(value) -> float:
+    t = float(value)
+    if not (t > 0.0 and math.isfinite(t)):
+        raise ValueError(f"top_db must be a finite number > 0, got {value!r}")
+    return t
+
+
+def check_min_frames(value) -> int:
+    k = A.as_int(value, "min_frames")
+    if k < 1:
+        raise ValueError(f"min_frames must be >= 1, got {value!r}")
+    return k
 
 
 class BiasDenoiser(torch.nn.Module):
@@ -95,3 +120,102 @@ class BiasDenoiser(torch.nn.Module):
             L_.check(lib.efts_denoise(audio.data_ptr(), n, li.data_ptr(), n, window.data_ptr(), bias.data_ptr(), s, out.data_ptr(), n,
                                       frames.data_ptr(), None if ws is None else ws.data_ptr(), nbytes, B, O._stream()), "efts_denoise")
         return (out, frames) if return_frames else out
+
+
+class _Windowed(torch.nn.Module):
+    """what the two corpus modules below share: the window per device and the arguments of a padded batch"""
+
+    def __init__(self, device=None):
+        super().__init__()
+        self.dev = None if device is None else torch.device(device)
+        self._windows = {}
+
+    def _window(self, dev):
+        if dev not in self._windows:
+            self._windows[dev] = torch.from_numpy(hann_window(N_FFT)).to(dev)
+        return self._windows[dev]
+
+    def _batch(self, audio, lengths, who):
+        audio = A.signal(audio, "audio", who)
+        B, n = audio.shape
+        lib = L_.load()
+        L_.require_device()
+        return audio, B, n, lib, A.device_lengths(lengths, B, n, audio.device)
+
+
+class NoiseProfile(_Windowed):
+    """stats = NoiseProfile(device, top_db=40.0, min_frames=8, max_wav_value=32768.0)(audio [B, L] float32 or int16, lengths=None)
+
+    The stationary floor of every item, measured from its own quiet frames: with e[t] the energy of the windowed frame t (N = 1024, hop 256,
+    the framing of `BiasDenoiser`), the frames with e[t] * 10^(top_db / 10) < max e -- the rule of `SilenceTrimmer`, no logarithm -- are the
+    noise frames, and the profile is the mean of their magnitude spectra.  stats: a dict of device tensors, nothing is read back:
+    `profile` fp32 [B, 513] (exactly 0 for an item with fewer than `min_frames` noise frames), `noise_frames` and `frames` int32 [B], `noise_db`
+    float64 [B] (the noise frames' mean energy under the loudest frame's; NaN without a noise frame).  `efts_noise_profile`, four launches."""
+
+    def __init__(self, device=None, top_db: float = 40.0, min_frames: int = 8, max_wav_value: float = 32768.0):
+        super().__init__(device)
+        self.top_db, self.min_frames, self.max_wav_value = check_top_db(top_db), check_min_frames(min_frames), A.max_wav(max_wav_value)
+        self.ratio = float(10.0 ** (np.float64(self.top_db) / 10.0))        # r, float64, once
+        self._ws = A.Cache(capacity=5)   # (device, B, n) -> workspace
+
+    @torch.no_grad()
+    def forward(self, audio: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+        audio, B, n, lib, li = self._batch(audio, lengths, "NoiseProfile")
+        dev = audio.device
+        pcm = audio.dtype == torch.int16
+        profile = torch.empty(B, BINS, dtype=torch.float32, device=dev)
+        counts = torch.empty(2, B, dtype=torch.int32, device=dev)
+        noise_db = torch.empty(B, dtype=torch.float64, device=dev)
+        nbytes = int(lib.efts_noise_profile_workspace_bytes(B, n))
+        ws = self._ws.get((dev, B, n), lambda: torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev))
+        with O.stream_scope():
+            L_.check(lib.efts_noise_profile(audio.data_ptr(), int(pcm), 1.0 / self.max_wav_value if pcm else 1.0, n, li.data_ptr(), n,
+                                            self._window(dev).data_ptr(), self.ratio, self.min_frames, profile.data_ptr(), BINS, counts[0].data_ptr(),
+                                            counts[1].data_ptr(), noise_db.data_ptr(), ws.data_ptr(), nbytes, B, O._stream()), "efts_noise_profile")
+        return {"profile": profile, "noise_frames": counts[0], "frames": counts[1], "noise_db": noise_db}
+
+
+class SpectralGate(_Windowed):
+    """out = SpectralGate(device, strength=1.0, floor=0.1, top_db=40.0, min_frames=8)(audio [B, L] float32 or int16, lengths=None, profile=None,
+                                                                                    strength=None, floor=None, return_stats=False)
+
+    Spectral subtraction with a gain floor: per frame and bin g = max((m - strength * profile) / m, floor) (0 below the profile before the
+    floor), at the frame's own phase, through the STFT / inverse STFT / overlap-add of `BiasDenoiser` in one launch (`efts_spectral_gate`).
+    Without `profile` every item is gated with the profile that `NoiseProfile` measures from its own quiet frames; an item with fewer than
+    `min_frames` of them is returned as it came (the flags are built on the device, nothing is read back).  With `profile`, [513] for the
+    batch or [B, 513] per item -- a room-tone recording's, for instance --, nothing is bypassed.  out: fp32 [B, L], zero behind an item's
+    length; int16 PCM comes back as sample / max_wav_value.  With `return_stats=True` also the dict of `NoiseProfile` (None with a given
+    profile).  `strength` and `floor` override the module's for one call and are passed by value."""
+
+    def __init__(self, device=None, strength: float = 1.0, floor: float = 0.1, top_db: float = 40.0, min_frames: int = 8, max_wav_value: float = 32768.0):
+        super().__init__(device)
+        self.strength, self.floor = check_strength(strength), check_floor(floor)
+        self.measure = NoiseProfile(device, top_db=top_db, min_frames=min_frames, max_wav_value=max_wav_value)
+        self.top_db, self.min_frames, self.max_wav_value = self.measure.top_db, self.measure.min_frames, self.measure.max_wav_value
+
+    @torch.no_grad()
+    def forward(self, audio: torch.Tensor, lengths: Optional[torch.Tensor] = None, profile: Optional[torch.Tensor] = None,
+                strength: Optional[float] = None, floor: Optional[float] = None, return_stats: bool = False):
+        s = self.strength if strength is None else check_strength(strength)
+        fl = self.floor if floor is None else check_floor(floor)
+        if profile is not None and tuple(profile.shape) not in ((BINS,), (audio.shape[0], BINS)):
+            raise ValueError(f"profile must be [{BINS}] or [B, {BINS}], got {tuple(profile.shape)}")
+        audio, B, n, lib, li = self._batch(audio, lengths, "SpectralGate")
+        dev = audio.device
+        pcm = audio.dtype == torch.int16
+        stats = bypass = None
+        if profile is None:
+            stats = self.measure(audio, li)
+            profile, ld_profile = stats["profile"], BINS
+            bypass = (stats["noise_frames"] < self.min_frames).to(torch.int32)
+        else:
+            profile = profile.to(device=dev, dtype=torch.float32).contiguous()
+            ld_profile = 0 if profile.dim() == 1 else BINS
+        out = torch.empty(B, n, dtype=torch.float32, device=dev)
+        frames = torch.empty(B, dtype=torch.int32, device=dev)
+        with O.stream_scope():
+            L_.check(lib.efts_spectral_gate(audio.data_ptr(), int(pcm), 1.0 / self.max_wav_value if pcm else 1.0, n, li.data_ptr(), n,
+                                            self._window(dev).data_ptr(), profile.data_ptr(), ld_profile, s, fl,
+                                            None if bypass is None else bypass.data_ptr(), out.data_ptr(), n, frames.data_ptr(), B, O._stream()),
+                     "efts_spectral_gate")
+        return (out, stats) if return_stats else out

@@ -223,6 +223,10 @@ _SIGS = {
     # spectral subtraction of a vocoder's bias noise
     "efts_denoise_workspace_bytes": (i64, [i32, i32]),
     "efts_denoise": (i32, [vp, i64, vp, i32, vp, vp, f32, vp, i64, vp, vp, i64, i32, vp]),
+    # a noise profile per recording and the spectral gate that uses it
+    "efts_noise_profile_workspace_bytes": (i64, [i32, i32]),
+    "efts_noise_profile": (i32, [vp, i32, f32, i64, vp, i32, vp, C.c_double, i32, vp, i64, vp, vp, vp, vp, i64, i32, vp]),
+    "efts_spectral_gate": (i32, [vp, i32, f32, i64, vp, i32, vp, vp, i64, f32, f32, vp, vp, i64, vp, i32, vp]),
     # STOI and ESTOI intelligibility scores
     "efts_stoi_workspace_bytes": (i64, [i32, i32]),
     "efts_stoi": (i32, [vp, i64, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp]),

@@ -80,6 +80,7 @@ class EfficientTTSTrainer:
         self.device = device
         self.frontend = None                   # optional LogMelFrontend (set by efficient_tts_amd.bin.train)
         self.resampler = None                  # optional Resampler in front of it: corpus rate -> front-end rate (set by efficient_tts_amd.bin.train)
+        self.gate = None                       # optional SpectralGate behind the resampler: `denoise_corpus` (set by efficient_tts_amd.bin.train)
         self.trimmer = None                    # optional SilenceTrimmer between the two: `trim_silence` / `normalize_peak` (set by efficient_tts_amd.bin.train)
         self.loudness = None                   # optional LoudnessNormalizer behind the trimmer: `normalize_loudness` (set by efficient_tts_amd.bin.train)
         self.finish_train = False
@@ -122,6 +123,10 @@ class EfficientTTSTrainer:
         if self.resampler is not None:
             # the padded int16 batch at the corpus' rate -> a padded fp32 batch at the front-end's rate, with the converted lengths
             third, third_lengths = self.resampler(third, third_lengths)
+        if self.gate is not None:
+            # the stationary floor under the speech taken out, item by item, with the profile of the item's own quiet frames: a padded fp32 batch,
+            # the lengths stay; in front of the trimmer, so that its threshold sees the cleaned signal
+            third = self.gate(third, third_lengths)
         if self.trimmer is not None:
             # the quiet ends cut off and / or the level set, item by item: a padded fp32 batch with the new lengths, so the frame count below shrinks
             third, third_lengths = self.trimmer(third, third_lengths)

@@ -98,7 +98,9 @@ extern "C" {
  *        + efts_stoi, efts_stoi_workspace_bytes (STOI and ESTOI intelligibility scores): exports added, the revision stays by the same
  *          rule
  *        + efts_logspec_project, efts_frame_dist (waveform mel-cepstra and the distance between frames paired one to one): exports added,
- *          the revision stays by the same rule */
+ *          the revision stays by the same rule
+ *        + efts_noise_profile, efts_noise_profile_workspace_bytes, efts_spectral_gate (a noise profile per recording and the spectral gate
+ *          that uses it): exports added, the revision stays by the same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -1206,6 +1208,59 @@ int efts_logspec_project(const void* audio, int32_t pcm16, float pcm_scale, int6
                          const float* table, int32_t n_coef, float* out, int32_t* frames, int32_t B, int32_t N, int32_t H, int32_t W, void* stream);
 int efts_frame_dist(const float* x, int64_t ldx, int64_t x_item_stride, const int32_t* x_frames, int32_t Tx, const float* y, int64_t ldy,
                     int64_t y_item_stride, const int32_t* y_frames, int32_t Ty, int32_t D, double* cost, int32_t* count, int32_t B, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Spectral gating of a corpus with a noise profile per recording: the stationary floor under the speech (room tone, fan noise, hiss) is
+ * measured from every item's own quiet frames and subtracted from its magnitudes, with a floor under the gain.  Fixed configuration, that of
+ * efts_denoise: N = 1024, H = 256, W = 1024; samples fp32, or int16 PCM (pcm16 != 0) multiplied by pcm_scale (1 / max_wav_value) at the load,
+ * x = fl32((float) sample * pcm_scale); an fp32 signal is not scaled.  Item b is row b of audio [B][ld] and has len = lengths[b], clamped to
+ * 0 .. max_len, samples; nothing behind them is read.  window: [1024] fp32, DEVICE memory, the periodic Hann window of efts_denoise.  Frames:
+ * those of efts_denoise, T = 1 + len / 256 when len > 512 and none otherwise, centred, reflected without edge repeat; frames 2 p and 2 p + 1
+ * of an item share one complex transform (frame 2 p the real part, an unpaired last frame has a zero partner), and the magnitude of a bin is
+ * m = sqrtf(fma(re, re, im * im)): the same instructions in both entries and in efts_denoise, so all three see the same bits.
+ * efts_noise_profile:
+ *   energy  : v = fl32(w[n] * x_t[n]); e[t] = sum_n (double) v * (double) v (every product is exact in float64).  ONE order: lane l of 64 starts
+ *             from 0 and takes n = l, l + 64, .., l + 960 in ascending order, then v = v + (the v of the lane 32 across), then 16, 8, 4, 2, 1.
+ *   noise frames: e_max = max_t e[t]; r = 10^(top_db / 10), computed by the caller in float64 and passed by value (as efts_trim's); frame t is
+ *             a noise frame iff e[t] * r < e_max -- one float64 multiply, one strict compare, no logarithm.  K = their count.  An all-zero
+ *             item has none.
+ *   profile : profile[b][f] = (float) (S[f] / (double) K), f = 0 .. 512, where S[f] is the float64 sum of m[t][f] over the noise frames: the
+ *             item's frames are cut into runs of 16 (run q = frames 16 q .. 16 q + 15); every run adds its noise frames from 0 in
+ *             ascending t; the runs' sums are added from 0 in ascending q (a run without a noise frame adds nothing).  Rounded once.
+ *             K < min_frames (by value, >= 1), or no frame at all: the row is exactly 0.0f and noise_frames still says K.  Entries of a row
+ *             behind 512 are not touched.
+ *   noise_frames [B], frames [B] int32: K and T.  noise_db [B] float64: 10 log10((sum of e over the noise frames / K) / e_max), NaN for
+ *             K = 0; the sum: thread t of 256 adds its noise frames among t, t + 256, .. in ascending order, the xor tree above inside each
+ *             wave, then ((wave 0 + wave 1) + wave 2) + wave 3.  Informational: no decision depends on it.
+ *   Four launches on one stream whatever the data: the energies (one wave per frame); per item e_max, the flags and the counts; the
+ *   transforms of the pairs that hold a noise frame (one wave per run, the sums in registers, one partial row per run to the workspace); the
+ *   sum over the runs.  No spectrogram in memory, no atomics, no launch geometry from device data, nothing read back: the call can be
+ *   captured.  An item gives the same bits alone, at any batch position and whatever lies behind its samples.
+ *   workspace: efts_noise_profile_workspace_bytes(B, max_len) bytes, 16-byte aligned (energies and flags [B][T_max], T_max = 1 + max_len / 256,
+ *   counts and partial rows [B][ceil(T_max / 16)][513] float64); contents afterwards unspecified.  The size entry returns 0 for a B or max_len
+ *   that the call refuses.
+ * efts_spectral_gate: efts_denoise, to the letter (pairing, runs of 16 hops, overlap-add oldest first, one division, zeros behind len up to
+ *   ld_out, items of at most 512 samples copied, frames [B] = T), with four differences:
+ *   (a) profile [B][ld_profile] fp32, DEVICE memory, row b for item b; ld_profile = 0: one shared row [513] (efts_denoise's bias).
+ *   (b) d = m - strength * profile[b][f]; g = d / m if d > 0, otherwise 0; then g = max(g, floor), 0 <= floor <= 1 by value; X' = g X (0
+ *       where m = 0).  The zero partner of an unpaired last frame keeps gain 0.  floor = 0 on fp32 samples with a shared row gives the bits
+ *       of efts_denoise.
+ *   (c) int16 input as above; out is always fp32.
+ *   (d) bypass [B] int32, DEVICE memory, may be NULL: a non-zero entry copies the item's samples (int16: fl32((float) sample * pcm_scale))
+ *       to out bit for bit, as an item of at most 512 samples is copied; frames[b] is still T.
+ *   One launch, no workspace, no atomics, nothing read back.
+ * EFTS_EINVAL, nothing launched, the entry's name in efts_last_error(): a null pointer (other than bypass) or one not aligned to its element
+ * (the workspace: to 16 bytes), B outside 1 .. 65535, max_len outside 1 .. 2^31 - 8193, a leading dimension below max_len, ld_out >= 2^31,
+ * ld_profile below 513 (the gate: other than 0 and below 513), a negative or non-finite strength, a floor outside 0 .. 1, r not a finite
+ * number > 1, min_frames < 1, pcm_scale not a positive number with pcm16, a workspace too small, out [B][ld_out] overlapping audio.
+ * ---------------------------------------------------------------------------------- */
+int64_t efts_noise_profile_workspace_bytes(int32_t B, int32_t max_len);
+int efts_noise_profile(const void* audio, int32_t pcm16, float pcm_scale, int64_t ld, const int32_t* lengths, int32_t max_len, const float* window,
+                       double r, int32_t min_frames, float* profile, int64_t ld_profile, int32_t* noise_frames, int32_t* frames, double* noise_db,
+                       void* workspace, int64_t workspace_bytes, int32_t B, void* stream);
+int efts_spectral_gate(const void* audio, int32_t pcm16, float pcm_scale, int64_t ld, const int32_t* lengths, int32_t max_len, const float* window,
+                       const float* profile, int64_t ld_profile, float strength, float floor, const int32_t* bypass, float* out, int64_t ld_out,
+                       int32_t* frames, int32_t B, void* stream);
 
 #ifdef __cplusplus
 }
