@@ -40,6 +40,7 @@
 
 #include "efts_internal.h"
 #include "efts_fft.h"
+#include "efts_stft_frame.h"
 
 namespace efts {
 
@@ -50,36 +51,7 @@ constexpr int DN_RUN = 16;                               // hops per wave: even,
 constexpr int DN_RUN_SAMPLES = DN_RUN * DN_HOP;
 static_assert(DN_RUN % 2 == 0 && DN_RUN >= 4, "a run begins and ends on a pair of frames");
 
-__device__ __forceinline__ int dn_reflect(int s, int len) {
-    s = s < 0 ? -s : s;
-    s = s >= len ? 2 * (len - 1) - s : s;
-    return min(max(s, 0), len - 1);                      // (out of range only for a frame past the item's count, whose values are dropped)
-}
-
-// sample i of a row: fp32 as it is, int16 PCM times pcm_scale (rounded once)
-template <typename I> __device__ __forceinline__ float dn_sample(const float* x, I i, float) { return x[i]; }
-template <typename I> __device__ __forceinline__ float dn_sample(const short* x, I i, float scale) { return (float)x[i] * scale; }
-
-// the 1280 samples of the pair of frames that begins at sample s0 (frame t0: values 0 .. 15, frame t0 + 1: values 4 .. 19), reflected at the
-// item's ends: sm[j] is sample s0 + 64 j + lane
-template <typename S>
-__device__ __forceinline__ void dn_load_pair(const S* __restrict__ x, float scale, int s0, int len, int lane, float (&sm)[20]) {
-    if (s0 >= 0 && s0 + DN_N + DN_HOP <= len) {
-        const S* p = x + s0 + lane;
-#pragma unroll
-        for (int j = 0; j < 20; ++j) sm[j] = dn_sample(p, 64 * j, scale);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 20; ++j) sm[j] = dn_sample(x, dn_reflect(s0 + 64 * j + lane, len), scale);
-    }
-}
-
-// the two spectra of a pair's transform Z at bin k, zf = Z[k], zn = Z[N - k]: X_a[k] = (Z[k] + conj Z[N - k]) / 2 = ar + i ai,
-// X_b[k] = (Z[k] - conj Z[N - k]) / 2i = br + i bi; and the magnitude that every gain and every profile is taken from
-__device__ __forceinline__ void dn_split(cf zf, cf zn, float& ar, float& ai, float& br, float& bi) {
-    ar = 0.5f * (zf.x + zn.x), ai = 0.5f * (zf.y - zn.y);
-    br = 0.5f * (zf.y + zn.y), bi = 0.5f * (zn.x - zf.x);
-}
+// the magnitude that every gain and every profile is taken from (the pair loader and the split of the two spectra: efts_stft_frame.h)
 __device__ __forceinline__ float dn_mag(float re, float im) { return sqrtf(fmaf(re, re, im * im)); }
 
 // GATE = false, S = float: efts_denoise (ld_bias, floor, pcm_scale and bypass are not looked at).  GATE = true: efts_spectral_gate.
@@ -92,8 +64,7 @@ __global__ __launch_bounds__(64 * DN_WAVES) void denoise_kernel(const S* __restr
     __shared__ cf tw1s[15][64];
     __shared__ cf tw2s[4][16];
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int len = min(max(lengths[b], 0), max_len);
-    const int T = len > DN_N / 2 ? 1 + len / DN_HOP : 0;
+    const int len = st_len(lengths, b, max_len), T = st_frames(len, DN_N, DN_HOP);
     if (blockIdx.x == 0 && threadIdx.x == 0) frames[b] = T;
     const S* x = audio + (long)b * ld;
     float* o = out + (long)b * ld_out;
@@ -105,7 +76,7 @@ __global__ __launch_bounds__(64 * DN_WAVES) void denoise_kernel(const S* __restr
     }
     if (pass || g0 >= len) {                             // (uniform in the workgroup) a short or bypassed item passes through; behind an item: zeros
         const long g1 = min(ld_out, g0 + DN_WAVES * DN_RUN_SAMPLES);
-        for (long s = g0 + threadIdx.x; s < g1; s += 64 * DN_WAVES) o[s] = s < len ? dn_sample(x, s, pcm_scale) : 0.f;
+        for (long s = g0 + threadIdx.x; s < g1; s += 64 * DN_WAVES) o[s] = s < len ? pcm_sample(x, s, pcm_scale) : 0.f;
         return;
     }
     fft::fill_twiddles<64 * DN_WAVES>(tw1s, tw2s);
@@ -135,10 +106,9 @@ __global__ __launch_bounds__(64 * DN_WAVES) void denoise_kernel(const S* __restr
         if (va) {
             const int s0 = t0 * DN_HOP - DN_N / 2;       // acc[j] is sample s0 + 64 j + lane
             float sm[20];
-            dn_load_pair(x, pcm_scale, s0, len, lane, sm);
+            st_load_pair20(x, pcm_scale, s0, len, lane, sm);
             cf v[16];
-#pragma unroll
-            for (int n1 = 0; n1 < 16; ++n1) v[n1] = cf{sm[n1] * win[n1], vb ? sm[n1 + 4] * win[n1] : 0.f};
+            st_pair_values(sm, win, vb, v);
             fft::fft1024(v, zw, tw1s, tw2s, lane);
             // X_a[k] = (Z[k] + conj Z[N - k]) / 2, X_b[k] = (Z[k] - conj Z[N - k]) / 2i for ALL k (the upper half is the conjugate of the lower
             // one to the bit, so is its gain); Z' = g_a X_a + i g_b X_b; v = conj Z'
@@ -147,7 +117,7 @@ __global__ __launch_bounds__(64 * DN_WAVES) void denoise_kernel(const S* __restr
                 const int k = 64 * n1 + lane;
                 const cf zf = zw[fft::bin_slot(k)], zn = zw[fft::bin_slot((DN_N - k) & (DN_N - 1))];
                 float ar, ai, br, bi;
-                dn_split(zf, zn, ar, ai, br, bi);
+                st_split(zf, zn, ar, ai, br, bi);
                 const float ma = dn_mag(ar, ai), mb = dn_mag(br, bi);
                 const float da = ma - bs[n1], db = mb - bs[n1];
                 float ga = da > 0.f ? da / ma : 0.f;
@@ -186,35 +156,16 @@ __global__ __launch_bounds__(64 * DN_WAVES) void denoise_kernel(const S* __restr
     for (long s = (long)(c_last + 1) * DN_HOP + lane; s < r1; s += 64) o[s] = 0.f;
 }
 
-static const char* dn_bad_shape(int32_t B, int32_t max_len) {
-    if (B < 1 || B > 65535) return "1 .. 65535 items per launch";
-    if (max_len < 1 || max_len > 0x7fffffff - 4 * 2048) return "max_len must lie in 1 .. 2^31 - 8193";
-    return nullptr;
-}
-
 // ---- efts_noise_profile
 constexpr int NP_RUN = 16, NP_WAVES = 4, NP_THREADS = 64 * NP_WAVES;     // frames per run (even: a run begins with a pair); waves per workgroup
 static_assert(NP_RUN % 2 == 0, "a run begins on a pair of frames");
-
-__device__ __forceinline__ int np_frames(const int* lengths, int b, int max_len, int& len) {
-    len = min(max(lengths[b], 0), max_len);
-    return len > DN_N / 2 ? 1 + len / DN_HOP : 0;
-}
-
-// the documented order of a wave's float64 sum: v = v + (the value 32, 16, 8, 4, 2, 1 lanes across); every lane ends with the same bits
-__device__ __forceinline__ double np_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
-    return v;
-}
 
 // launch 1: one wave per frame
 template <typename S>
 __global__ __launch_bounds__(NP_THREADS) void np_energy_kernel(const S* __restrict__ audio, long ld, const int* __restrict__ lengths, int max_len,
                                                                const float* __restrict__ window, float pcm_scale, double* __restrict__ energy, int T_max) {
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int len;
-    const int T = np_frames(lengths, b, max_len, len);
+    const int len = st_len(lengths, b, max_len), T = st_frames(len, DN_N, DN_HOP);
     const int t = blockIdx.x * NP_WAVES + wave;
     if (t >= T) return;
     const S* x = audio + (long)b * ld;
@@ -224,10 +175,10 @@ __global__ __launch_bounds__(NP_THREADS) void np_energy_kernel(const S* __restri
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         const int n = 64 * j + lane;
-        const float v = window[n] * dn_sample(x, inside ? s0 + n : dn_reflect(s0 + n, len), pcm_scale);
+        const float v = window[n] * pcm_sample(x, inside ? s0 + n : st_reflect(s0 + n, len), pcm_scale);
         s = fma((double)v, (double)v, s);
     }
-    s = np_wave_sum(s);
+    s = wave_sum(s);
     if (lane == 0) energy[(long)b * T_max + t] = s;
 }
 
@@ -238,13 +189,11 @@ __global__ __launch_bounds__(NP_THREADS) void np_select_kernel(const int* __rest
     __shared__ double s_m[NP_WAVES], s_s[NP_WAVES];
     __shared__ int s_k[NP_WAVES];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int len;
-    const int T = np_frames(lengths, b, max_len, len);
+    const int T = st_frames(st_len(lengths, b, max_len), DN_N, DN_HOP);
     const double* e = energy + (long)b * T_max;
     double m = 0.0;
     for (int t = tid; t < T; t += NP_THREADS) m = fmax(m, e[t]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+    m = wave_max(m);
     if (lane == 0) s_m[wave] = m;
     __syncthreads();
     const double e_max = fmax(fmax(s_m[0], s_m[1]), fmax(s_m[2], s_m[3]));
@@ -263,9 +212,8 @@ __global__ __launch_bounds__(NP_THREADS) void np_select_kernel(const int* __rest
         for (int t = q * NP_RUN; t < min(T, (q + 1) * NP_RUN); ++t) c += e[t] * r < e_max ? 1 : 0;
         run_count[(long)b * R_max + q] = c;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) k += __shfl_xor(k, o);
-    sum = np_wave_sum(sum);
+    k = wave_sum(k);
+    sum = wave_sum(sum);
     if (lane == 0) { s_k[wave] = k; s_s[wave] = sum; }
     __syncthreads();
     if (tid == 0) {
@@ -286,8 +234,7 @@ __global__ __launch_bounds__(NP_THREADS) void np_accum_kernel(const S* __restric
     __shared__ cf tw1s[15][64];
     __shared__ cf tw2s[4][16];
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int len;
-    const int T = np_frames(lengths, b, max_len, len);
+    const int len = st_len(lengths, b, max_len), T = st_frames(len, DN_N, DN_HOP);
     const int R = (T + NP_RUN - 1) / NP_RUN;
     const int* rc = run_count + (long)b * R_max;
     int any = 0;                                         // (uniform in the workgroup)
@@ -315,17 +262,16 @@ __global__ __launch_bounds__(NP_THREADS) void np_accum_kernel(const S* __restric
         const bool fa = fl[t0] != 0, fb = vb && fl[t0 + 1] != 0;
         if (!fa && !fb) continue;                        // (uniform in the wave)
         float sm[20];
-        dn_load_pair(x, pcm_scale, t0 * DN_HOP - DN_N / 2, len, lane, sm);
+        st_load_pair20(x, pcm_scale, t0 * DN_HOP - DN_N / 2, len, lane, sm);
         cf v[16];
-#pragma unroll
-        for (int n1 = 0; n1 < 16; ++n1) v[n1] = cf{sm[n1] * win[n1], vb ? sm[n1 + 4] * win[n1] : 0.f};
+        st_pair_values(sm, win, vb, v);
         fft::fft1024(v, zw, tw1s, tw2s, lane);
 #pragma unroll
         for (int j = 0; j < 9; ++j) {                    // bins 64 j + lane; j = 8: bin 512, in every lane alike
             const int k = j < 8 ? 64 * j + lane : DN_N / 2;
             const cf zf = zw[fft::bin_slot(k)], zn = zw[fft::bin_slot((DN_N - k) & (DN_N - 1))];
             float ar, ai, br, bi;
-            dn_split(zf, zn, ar, ai, br, bi);
+            st_split(zf, zn, ar, ai, br, bi);
             if (fa) acc[j] = acc[j] + (double)dn_mag(ar, ai);
             if (fb) acc[j] = acc[j] + (double)dn_mag(br, bi);
         }
@@ -342,8 +288,7 @@ __global__ __launch_bounds__(NP_THREADS) void np_reduce_kernel(const int* __rest
                                                                const int* __restrict__ noise_frames, int R_max, const double* __restrict__ partial,
                                                                float* __restrict__ profile, long ld_profile) {
     const int b = blockIdx.x;
-    int len;
-    const int T = np_frames(lengths, b, max_len, len);
+    const int T = st_frames(st_len(lengths, b, max_len), DN_N, DN_HOP);
     const int R = (T + NP_RUN - 1) / NP_RUN, K = noise_frames[b];
     const int* rc = run_count + (long)b * R_max;
     const bool keep = K > 0 && K >= min_frames;
@@ -356,17 +301,16 @@ __global__ __launch_bounds__(NP_THREADS) void np_reduce_kernel(const int* __rest
     }
 }
 
-static inline int64_t np_round16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 struct np_layout { int64_t T_max, R_max, energy, flags, runs, partial, bytes; };
 static np_layout np_workspace(int32_t B, int32_t max_len) {
     np_layout w;
     w.T_max = 1 + max_len / DN_HOP;
     w.R_max = (w.T_max + NP_RUN - 1) / NP_RUN;
     w.energy = 0;
-    w.flags = w.energy + np_round16((int64_t)B * w.T_max * 8);
-    w.runs = w.flags + np_round16((int64_t)B * w.T_max * 4);
-    w.partial = w.runs + np_round16((int64_t)B * w.R_max * 4);
-    w.bytes = w.partial + np_round16((int64_t)B * w.R_max * (DN_N / 2 + 1) * 8);
+    w.flags = w.energy + efts_round16((int64_t)B * w.T_max * 8);
+    w.runs = w.flags + efts_round16((int64_t)B * w.T_max * 4);
+    w.partial = w.runs + efts_round16((int64_t)B * w.R_max * 4);
+    w.bytes = w.partial + efts_round16((int64_t)B * w.R_max * (DN_N / 2 + 1) * 8);
     return w;
 }
 
@@ -400,7 +344,7 @@ extern "C" int64_t efts_denoise_workspace_bytes(int32_t, int32_t) {
 extern "C" int efts_denoise(const float* audio, int64_t ld, const int32_t* lengths, int32_t max_len, const float* window, const float* bias,
                             float strength, float* out, int64_t ld_out, int32_t* frames, void* workspace, int64_t workspace_bytes, int32_t B,
                             void* stream) {
-    if (const char* why = dn_bad_shape(B, max_len)) return efts_fail(EFTS_EINVAL, "efts_denoise: %s", why);
+    if (const char* why = efts_audio_bad_shape(B, max_len)) return efts_fail(EFTS_EINVAL, "efts_denoise: %s", why);
     if (ld < max_len || ld_out < max_len) return efts_fail(EFTS_EINVAL, "efts_denoise: a leading dimension is smaller than the longest item");
     if (ld_out > 0x7fffffffLL) return efts_fail(EFTS_EINVAL, "efts_denoise: ld_out must stay below 2^31 (every sample of a row is written)");
     if (!(strength >= 0.f) || !std::isfinite(strength)) return efts_fail(EFTS_EINVAL, "efts_denoise: the strength must be a finite number >= 0");
@@ -423,7 +367,7 @@ extern "C" int efts_spectral_gate(const void* audio, int32_t pcm16, float pcm_sc
                                   const float* profile, int64_t ld_profile, float strength, float floor, const int32_t* bypass, float* out, int64_t ld_out,
                                   int32_t* frames, int32_t B, void* stream) {
     const char* who = "efts_spectral_gate";
-    if (const char* why = dn_bad_shape(B, max_len)) return efts_fail(EFTS_EINVAL, "%s: %s", who, why);
+    if (const char* why = efts_audio_bad_shape(B, max_len)) return efts_fail(EFTS_EINVAL, "%s: %s", who, why);
     if (ld < max_len || ld_out < max_len) return efts_fail(EFTS_EINVAL, "%s: a leading dimension is smaller than the longest item", who);
     if (ld_out > 0x7fffffffLL) return efts_fail(EFTS_EINVAL, "%s: ld_out must stay below 2^31 (every sample of a row is written)", who);
     if (ld_profile != 0 && ld_profile < DN_N / 2 + 1) return efts_fail(EFTS_EINVAL, "%s: ld_profile must be 0 (one shared row) or at least 513", who);
@@ -450,7 +394,7 @@ extern "C" int efts_spectral_gate(const void* audio, int32_t pcm16, float pcm_sc
 }
 
 extern "C" int64_t efts_noise_profile_workspace_bytes(int32_t B, int32_t max_len) {
-    if (dn_bad_shape(B, max_len)) return 0;
+    if (efts_audio_bad_shape(B, max_len)) return 0;
     return np_workspace(B, max_len).bytes;
 }
 
@@ -458,7 +402,7 @@ extern "C" int efts_noise_profile(const void* audio, int32_t pcm16, float pcm_sc
                                   double r, int32_t min_frames, float* profile, int64_t ld_profile, int32_t* noise_frames, int32_t* frames, double* noise_db,
                                   void* workspace, int64_t workspace_bytes, int32_t B, void* stream) {
     const char* who = "efts_noise_profile";
-    if (const char* why = dn_bad_shape(B, max_len)) return efts_fail(EFTS_EINVAL, "%s: %s", who, why);
+    if (const char* why = efts_audio_bad_shape(B, max_len)) return efts_fail(EFTS_EINVAL, "%s: %s", who, why);
     if (ld < max_len) return efts_fail(EFTS_EINVAL, "%s: a leading dimension is smaller than the longest item", who);
     if (ld_profile < DN_N / 2 + 1) return efts_fail(EFTS_EINVAL, "%s: ld_profile must be at least 513", who);
     if (!(r > 1.0) || !std::isfinite(r)) return efts_fail(EFTS_EINVAL, "%s: the threshold ratio r = 10^(top_db / 10) must be a finite number > 1", who);

@@ -48,14 +48,14 @@ __device__ __forceinline__ cf quad(cf a) {       // the value of the quad's lane
 }
 
 // The twiddle tables of the 1024 = 16 x (16 x 4) transform, filled by the whole block of NTHREADS threads (the caller puts a barrier behind it):
-// tw1s[k - 1][n2] = W1024^(n2 k), k = 1 .. 15; tw2s[q][s] = W64^(q s).  UNIT: every W1024 factor 1 (an ablation switch of the front-end).
+// tw1s[k - 1][n2] = W1024^(n2 k), k = 1 .. 15; tw2s[q][s] = W64^(q s).
 constexpr int PITCH = 68;                       // complex values per row of a wave's transpose buffer [16][PITCH]
-template <int NTHREADS, bool UNIT = false>
+template <int NTHREADS>
 __device__ __forceinline__ void fill_twiddles(cf (*tw1s)[64], cf (*tw2s)[16]) {
     for (int i = threadIdx.x; i < 15 * 64; i += NTHREADS) {
         const int k = i / 64 + 1, n2 = i & 63;
         float sn, cs;
-        if (UNIT) { sn = 0.f; cs = 1.f; } else sincospif(-(float)((n2 * k) & 1023) / 512.f, &sn, &cs);
+        sincospif(-(float)((n2 * k) & 1023) / 512.f, &sn, &cs);
         tw1s[k - 1][n2] = cf{cs, sn};
     }
     if (threadIdx.x < 64) {

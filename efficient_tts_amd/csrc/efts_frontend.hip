@@ -20,6 +20,7 @@
 
 #include "efts_internal.h"
 #include "efts_fft.h"
+#include "efts_stft_frame.h"
 
 namespace efts {
 
@@ -296,23 +297,15 @@ __global__ __launch_bounds__(64 * LM_WAVES) void logmel_dit_fast_kernel(const fl
 // One wave per PAIR of neighbouring frames: z = frame_a + i frame_b goes through one complex 1024-point FFT and the two real
 // spectra come apart by conjugate symmetry, X_a[f] = (Z[f] + conj Z[N - f]) / 2, X_b[f] = (Z[f] - conj Z[N - f]) / 2i.
 // The FFT is 1024 = 16 x (16 x 4), 16 complex values per lane:
-//   n = 64 n1 + n2, k = k1 + 16 k2:  X[k] = sum_n2 W1024^(n2 k1) W64^(n2 k2) [sum_n1 z[64 n1 + n2] W16^(n1 k1)]
-//   (1) lane n2 reads its 16 samples of both frames straight from the audio (for a fixed n1 the 64 lanes read 64 consecutive
-//       samples; frame b is frame a moved by one hop = 4 values of n1, so 20 loads serve both), a 16-point DFT in registers,
-//       the twiddles W1024^(n2 k1) (per-lane constants, computed once per wave);
-//   (2) ONE transpose through LDS (rows of 68 complex: the column reads of step 3 then spread over all banks);
-//   (3) lane (k1, q) holds n2 = 4 r + q: 16-point DFT over r, twiddles W64^(q s), and the last radix-4 across the four lanes of
-//       a quad with DPP moves -- lane (k1, q) ends up with X[k1 + 16 s + 256 u(q)], s = 0 .. 15;
-//   (4) Z in natural order through the same LDS region, magnitudes of both frames, the mel filterbank (its non-zero spans in LDS,
+//   lane n2 reads its 16 samples of both frames straight from the audio (for a fixed n1 the 64 lanes read 64 consecutive samples;
+//   frame b is frame a moved by one hop = 4 values of n1, so 20 loads serve both: st_load_pair20, efts_stft_frame.h);
+//   (1) - (3) the transform itself, registers and ONE transpose through LDS: fft::fft1024, efts_fft.h -- this kernel is where it grew up;
+//   (4) Z in natural order in the same LDS region, magnitudes of both frames, the mel filterbank (its non-zero spans in LDS,
 //       filter m and m + 64 per lane), log, store.
 // fp32 throughout (the MFMA pipeline carried 16 mantissa bits).  meldataset.py:49-82, taco2_data.py:66-76, :122-139.
 // ----------------------------------------------------------------------------------------------------------------------------
-// (cmul, dft4, dft16, the DPP quad exchange and the twiddle tables: efts_fft.h, shared with the Griffin-Lim vocoder)
 
-#ifndef FF_ABL
-#define FF_ABL 0
-#endif
-constexpr int FF_WAVES = 4, FF_PITCH = 68, FF_CB = 2560, FF_WIDE = 64;      // filters FF_WIDE .. run on four lanes each (they are the widest)
+constexpr int FF_WAVES = 4, FF_CB = 2560, FF_WIDE = 64;      // filters FF_WIDE .. run on four lanes each (they are the widest)
 // SAMPLE: float (audio in [-1, 1]) or short (int16 PCM as TextMelLoader.get_mel reads it, scaled by `pcm_scale` = 1 / max_wav_value at the load:
 // taco2_data.py:70 -- exact in fp32 for a power of two, so both forms give the same bits; the int16 form saves the conversion pass over the batch)
 template <typename SAMPLE>
@@ -322,7 +315,7 @@ __global__ __launch_bounds__(64 * FF_WAVES, 3) void logmel_fft_kernel(const SAMP
                                                                       int n_mels, float pcm_scale) {
     using namespace fft;
     constexpr int N = 1024, HOP = 256, NBINS = 513, PAD = (N - HOP) / 2;
-    __shared__ __attribute__((aligned(16))) cf zs[FF_WAVES][16 * FF_PITCH];   // transpose buffer, then Z in natural order, then (|X_a|, |X_b|) per bin in place
+    __shared__ __attribute__((aligned(16))) cf zs[FF_WAVES][16 * PITCH];      // transpose buffer, then Z in natural order, then (|X_a|, |X_b|) per bin in place
     __shared__ __attribute__((aligned(16))) float cb[FF_CB];                  // the filterbank's non-zero spans, every span padded with zeros to whole 4-tap steps
     __shared__ cf tw1s[15][64];                             // W1024^(n2 k), k = 1 .. 15
     __shared__ cf tw2s[4][16];                              // W64^(q s)
@@ -330,7 +323,7 @@ __global__ __launch_bounds__(64 * FF_WAVES, 3) void logmel_fft_kernel(const SAMP
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     cf* zw = zs[wave];
     // ---- per block (a block works through many frame pairs): twiddle tables, filterbank
-    fill_twiddles<64 * FF_WAVES, (FF_ABL & 64) != 0>(tw1s, tw2s);
+    fill_twiddles<64 * FF_WAVES>(tw1s, tw2s);
     // span of a filter in cb: filters below FF_WIDE run on one lane, the others on four (a quarter each); all spans of a kind have the length of
     // the widest one (w0 / w1 4-tap steps, per lane), shorter ones are padded with zero weights -- so offsets are closed-form and a lane may run
     // its own number of steps or the common one
@@ -348,7 +341,7 @@ __global__ __launch_bounds__(64 * FF_WAVES, 3) void logmel_fft_kernel(const SAMP
     const int S0 = 4 * (w0 | 1), SQ = 4 * (w1 | 1);
     auto off_of = [&](int m) { return m < FF_WIDE ? S0 * m : S0 * min(n_mels, FF_WIDE) + 4 * SQ * (m - FF_WIDE); };
     // (the padding steps of a span read zw behind the filter's last bin: they must stay inside the wave's 16 x 65 buffer)
-    const bool in_lds = off_of(n_mels) <= FF_CB && NBINS + 4 * w0 <= 16 * FF_PITCH && NBINS + 16 * w1 <= 16 * FF_PITCH;
+    const bool in_lds = off_of(n_mels) <= FF_CB && NBINS + 4 * w0 <= 16 * PITCH && NBINS + 16 * w1 <= 16 * PITCH;
     if (in_lds) {
         for (int m = wave; m < n_mels; m += FF_WAVES) {
             const int lo = ranges[2 * m], hi = ranges[2 * m + 1];
@@ -370,14 +363,13 @@ __global__ __launch_bounds__(64 * FF_WAVES, 3) void logmel_fft_kernel(const SAMP
         lo1 = lo + 4 * w1 * q; o1 = off_of(m1) + SQ * q;
         ns1 = max(0, min(w1, (hi - lo1 + 3) >> 2));
     }
-    const float s1 = (q & 2) ? -1.f : 1.f, s2 = (q & 1) ? -1.f : 1.f;     // signs of the quad radix-4: r = partner + s * own
     float win[16];
 #pragma unroll
     for (int n1 = 0; n1 < 16; ++n1) win[n1] = window[64 * n1 + lane];
     const int PT = (T + 1) >> 1;                                      // frame pairs per item
     const int npairs = B * PT;
     const int stride = gridDim.x * FF_WAVES;
-    for (int pair = blockIdx.x * FF_WAVES + wave; pair < ((FF_ABL & 32) ? 0 : npairs); pair += stride) {
+    for (int pair = blockIdx.x * FF_WAVES + wave; pair < npairs; pair += stride) {
         const int b = pair / PT, t0 = 2 * (pair - b * PT);
         const int L = lengths[b], nfr = L / HOP;
         const bool va = t0 < nfr, vb = t0 + 1 < nfr && t0 + 1 < T;
@@ -387,74 +379,20 @@ __global__ __launch_bounds__(64 * FF_WAVES, 3) void logmel_fft_kernel(const SAMP
             for (int m = lane; m < n_mels; m += 64) { oa[m] = 0.f; if (t0 + 1 < T) ob[m] = 0.f; }
             continue;
         }
-        // (1) the samples of both frames: s[j] = audio[reflect(t0 * hop + 64 j + lane - pad)], j = 0 .. 19 (frame b = frame a moved by 4 j).
-        // Every load is issued, from a clamped address (a predicated load per sample compiled into twenty branches)
-        const SAMPLE* a = audio + (long)b * ld_audio;
+        // the samples of both frames (reflect without edge repeat: meldataset.py:69), (1) - (3) the transform, (4) Z in natural order at bin_slot(f)
         float sm[20];
-        const int s0 = t0 * HOP - PAD;                               // first sample of frame a in the un-padded signal
-        if (s0 >= 0 && s0 + 20 * 64 <= L) {                          // (wave-uniform) every sample of the pair lies inside the item: one base, constant offsets
-            const SAMPLE* ab = a + s0 + lane;
-#pragma unroll
-            for (int j = 0; j < 20; ++j) sm[j] = (FF_ABL & 16) ? (float)j : (float)ab[64 * j] * pcm_scale;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 20; ++j) {
-                int s = s0 + 64 * j + lane;
-                s = s < 0 ? -s : s;                                  // reflect without edge repeat (meldataset.py:69)
-                s = s >= L ? 2 * (L - 1) - s : s;
-                s = min(max(s, 0), L - 1);                           // (out of range only for frame b past the item's length: dropped below)
-                sm[j] = (FF_ABL & 16) ? (float)s : (float)a[s] * pcm_scale;
-            }
-        }
+        st_load_pair20(audio + (long)b * ld_audio, pcm_scale, t0 * HOP - PAD, L, lane, sm);
         cf v[16];
-#pragma unroll
-        for (int n1 = 0; n1 < 16; ++n1) v[n1] = cf{sm[n1] * win[n1], vb ? sm[n1 + 4] * win[n1] : 0.f};
-#if !(FF_ABL & 2)
-        dft16(v);
-#pragma unroll
-        for (int k = 1; k < 16; ++k) v[k] = cmul(v[k], tw1s[k - 1][lane]);
-#endif
-        // (2) transpose: row k1, column n2
-#pragma unroll
-        for (int k = 0; k < 16; ++k) zw[k * FF_PITCH + lane] = v[k];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // (3) lane (k1, q): n2 = 4 r + q
-#pragma unroll
-        for (int r = 0; r < 16; ++r) v[r] = zw[k1 * FF_PITCH + 4 * r + q];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if !(FF_ABL & 2)
-        dft16(v);
-#pragma unroll
-        for (int s = 1; s < 16; ++s) v[s] = cmul(v[s], tw2s[q][s]);
-#endif
-        // radix 4 across the quad: lanes hold x0 .. x3 (q = 0 .. 3); afterwards lane q holds X_u, u = bit-reversed q
-#if !(FF_ABL & 4)
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            cf c = v[s];
-            const cf p = quad<0x4E>(c);                             // quad_perm [2, 3, 0, 1]
-            c = c * s1 + p;                                          // q0: x0 + x2, q1: x1 + x3, q2: x0 - x2, q3: x1 - x3
-            if (q == 3) c = mul_mi(c);
-            const cf p2 = quad<0xB1>(c);                            // quad_perm [1, 0, 3, 2]
-            v[s] = c * s2 + p2;                                      // q0: X0, q1: X2, q2: X1, q3: X3
-        }
-#endif
-        const int u = ((q & 1) << 1) | (q >> 1);
-        // (4) Z in natural order: f = k1 + 16 s + 256 u
-        // (bin f sits at f + 4 (f / 256): the four lanes of a quad hold the same k1, and without the shift their stores meet in the same banks)
-#pragma unroll
-        for (int s = 0; s < 16; ++s) zw[k1 + 16 * s + 260 * u] = v[s];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        st_pair_values(sm, win, vb, v);
+        fft1024(v, zw, tw1s, tw2s, lane);
         // magnitudes of both frames, IN PLACE: bin f of this lane reads Z[f] and Z[N - f] -- no other lane reads either -- and leaves
         // (|X_a[f]|, |X_b[f]|) at zw[f] (unshifted: what sits there belongs to a bin at or below f, read in this or an earlier step)
 #pragma unroll
-        for (int i = 0; i < ((FF_ABL & 8) ? 2 : 9); ++i) {
+        for (int i = 0; i < 9; ++i) {
             const int f = lane + 64 * i;
             if (f < NBINS) {
-                const int fn = (N - f) & (N - 1);
-                const cf zf = zw[f + 4 * (f >> 8)], zn = zw[fn + 4 * (fn >> 8)];
-                const float ar = 0.5f * (zf.x + zn.x), ai = 0.5f * (zf.y - zn.y);
-                const float br = 0.5f * (zf.y + zn.y), bi = -0.5f * (zf.x - zn.x);
+                float ar, ai, br, bi;
+                st_split(zw[bin_slot(f)], zw[bin_slot((N - f) & (N - 1))], ar, ai, br, bi);
                 zw[f] = cf{__builtin_amdgcn_sqrtf(ar * ar + ai * ai + 1e-9f),     // meldataset.py:75 (v_sqrt_f32: 1 ulp)
                            __builtin_amdgcn_sqrtf(br * br + bi * bi + 1e-9f)};
             }
@@ -480,9 +418,6 @@ __global__ __launch_bounds__(64 * FF_WAVES, 3) void logmel_fft_kernel(const SAMP
             ra = a0; rb = b0;
         };
         float sa0, sb0, sa1, sb1;
-#if FF_ABL & 1
-        sa0 = zw[lane].x; sb0 = zw[lane].y; sa1 = zw[lane + 64].x; sb1 = zw[lane + 64].y;
-#else
         if (in_lds) {
             span(o0, lo0, ns0, sa0, sb0);
             span(o1, lo1, ns1, sa1, sb1);
@@ -491,7 +426,6 @@ __global__ __launch_bounds__(64 * FF_WAVES, 3) void logmel_fft_kernel(const SAMP
             if (m0 < n_mels && m0 < FF_WIDE) span_global(m0, ranges[2 * m0], ranges[2 * m0 + 1], sa0, sb0);
             if (m1 < n_mels && q == 0) span_global(m1, ranges[2 * m1], ranges[2 * m1 + 1], sa1, sb1);
         }
-#endif
         // the four quarters of a wide filter
         sa1 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sa1), 0x4E, 0xf, 0xf, false));
         sb1 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sb1), 0x4E, 0xf, 0xf, false));

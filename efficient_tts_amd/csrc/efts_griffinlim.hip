@@ -19,6 +19,7 @@
 
 #include "efts_internal.h"
 #include "efts_fft.h"
+#include "efts_stft_frame.h"
 
 namespace efts {
 
@@ -147,10 +148,8 @@ __global__ __launch_bounds__(64 * GL_WAVES) void gl_analysis_kernel(const float*
         }
     }
     cf v[16];
-#pragma unroll
-    for (int n1 = 0; n1 < 16; ++n1) v[n1] = cf{sm[n1] * win[n1], vb ? sm[n1 + 4] * win[n1] : 0.f};
+    st_pair_values(sm, win, vb, v);
     fft::fft1024(v, zw, tw1s, tw2s, lane);
-    // the two real spectra by conjugate symmetry: X_a[f] = (Z[f] + conj Z[N - f]) / 2, X_b[f] = (Z[f] - conj Z[N - f]) / 2i
     const long row = ((long)b * T + t0) * GL_BINS;
     auto project = [&](cf y, long idx) {
         if (mag == nullptr) { xout[idx] = y; return; }
@@ -166,6 +165,8 @@ __global__ __launch_bounds__(64 * GL_WAVES) void gl_analysis_kernel(const float*
         if (f < GL_BINS) {
             const int fn = (GL_N - f) & (GL_N - 1);
             const cf zf = zw[fft::bin_slot(f)], zn = zw[fft::bin_slot(fn)];
+            // st_split (efts_stft_frame.h), spelled out: the spectrum itself is stored here, and the zero that X_b's imaginary part is at DC and
+            // Nyquist (zf is zn there) keeps the sign it has always had, -0, where st_split's bi is +0 -- no magnitude can tell, a digest can
             project(cf{0.5f * (zf.x + zn.x), 0.5f * (zf.y - zn.y)}, row + f);
             if (vb) project(cf{0.5f * (zf.y + zn.y), -0.5f * (zf.x - zn.x)}, row + GL_BINS + f);
         }

@@ -13,6 +13,14 @@ int efts_check_launch(const char* what);
 __attribute__((visibility("hidden"))) void efts_gemm_init(void);
 // number of compute units of the current device (cached)
 int efts_num_cus(void);
+// the size of a workspace section: every section begins on a 16-byte boundary
+static inline int64_t efts_round16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+// the batch shape that every audio launch accepts (items on grid.y, sample indices in int): nullptr, or what is wrong with it
+static inline const char* efts_audio_bad_shape(int32_t B, int32_t max_len) {
+    if (B < 1 || B > 65535) return "1 .. 65535 items per launch";
+    if (max_len < 1 || max_len > 0x7fffffff - 4 * 2048) return "max_len must lie in 1 .. 2^31 - 8193";
+    return nullptr;
+}
 
 // geometry of a grouped (stream-K) wgrad launch, shared by efts_wgrad_tn_grouped and efts_wgrad_reduce_grouped (efts_wgrad.hip)
 struct efts_wgrad_sk_geom { int steps_tile, tiles_item, ntn, nx, q, total, workgroups, maxseg; };
@@ -76,16 +84,25 @@ __device__ __forceinline__ void plane_store4(char* row, int k, float v0, float v
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// The reductions over the 64 lanes of a wave, for float, double, int and unsigned long long.  The documented order of every one of them:
+// v = v op (the value 32, 16, 8, 4, 2, 1 lanes across); every lane ends with the same bits.
+__device__ __forceinline__ unsigned long long wave_shfl_xor(unsigned long long v, int o) {
+    const unsigned lo = __shfl_xor((unsigned)v, o), hi = __shfl_xor((unsigned)(v >> 32), o);
+    return ((unsigned long long)hi << 32) | lo;
+}
+template <typename T> __device__ __forceinline__ T wave_shfl_xor(T v, int o) { return __shfl_xor(v, o); }
+template <typename T, typename OP> __device__ __forceinline__ T wave_reduce(T v, OP op) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    for (int o = 32; o > 0; o >>= 1) v = op(v, wave_shfl_xor(v, o));
     return v;
 }
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
+template <typename T> __device__ __forceinline__ T wave_sum(T v) { return wave_reduce(v, [](T a, T b) { return a + b; }); }
+// (the device's max / min: fmaxf / fminf and fmax / fmin for float and double -- a NaN loses against a number)
+template <typename T> __device__ __forceinline__ T wave_max(T v) { return wave_reduce(v, [](T a, T b) { return max(a, b); }); }
+template <typename T> __device__ __forceinline__ T wave_min(T v) { return wave_reduce(v, [](T a, T b) { return min(a, b); }); }
+// the same by comparison, `b > a ? b : a`: what the trimmer's peaks and bounds are defined with (a NaN on the left stays)
+template <typename T> __device__ __forceinline__ T wave_max_cmp(T v) { return wave_reduce(v, [](T a, T b) { return b > a ? b : a; }); }
+template <typename T> __device__ __forceinline__ T wave_min_cmp(T v) { return wave_reduce(v, [](T a, T b) { return b < a ? b : a; }); }
 
 // counter-based dropout mask: keep (and scale by 1/(1-p)) iff hash(seed, element index) >= p * 2^32.
 // Stateless, so forward and backward regenerate the same mask from (seed, index).

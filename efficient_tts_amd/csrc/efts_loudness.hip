@@ -195,7 +195,6 @@ __global__ __launch_bounds__(LD_THREADS) void loud_scale_kernel(const S* __restr
     }
 }
 
-static inline int64_t ld_round16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 static inline int64_t ld_nseg(int64_t max_len) { return (max_len + LD_SEG - 1) / LD_SEG; }
 static inline bool ld_rate_ok(int32_t fs) { return fs >= 8000 && fs <= 48000 && fs % 10 == 0; }
 
@@ -206,7 +205,7 @@ using namespace efts;
 extern "C" int64_t efts_loudness_workspace_bytes(int32_t B, int64_t max_len, int32_t fs) {
     if (B <= 0 || max_len <= 0 || !ld_rate_ok(fs)) return 0;
     const int64_t nseg = ld_nseg(max_len), nsub = max_len / (fs / 10) + 1;
-    return ld_round16((int64_t)B * nseg * 16) + ld_round16((int64_t)B * nseg * 4) + ld_round16((int64_t)B * nsub * 8);
+    return efts_round16((int64_t)B * nseg * 16) + efts_round16((int64_t)B * nseg * 4) + efts_round16((int64_t)B * nsub * 8);
 }
 
 template <typename S>
@@ -229,8 +228,8 @@ static int loudness_launch(const S* in, int64_t ld_in, const int32_t* lengths, i
     const int h = fs / 10;
     const long nseg = (long)ld_nseg(ld_in), nsub = (long)(ld_in / h + 1);
     double* part = (double*)workspace;
-    float* seg_peak = (float*)((char*)workspace + ld_round16((int64_t)B * nseg * 16));
-    double* sub = (double*)((char*)seg_peak + ld_round16((int64_t)B * nseg * 4));
+    float* seg_peak = (float*)((char*)workspace + efts_round16((int64_t)B * nseg * 16));
+    double* sub = (double*)((char*)seg_peak + efts_round16((int64_t)B * nseg * 4));
     const double gamma_a = std::pow(10.0, (-70.0 + 0.691) / 10.0);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(loud_filter_kernel<S>, dim3((unsigned)((nseg + LD_FILTER_THREADS - 1) / LD_FILTER_THREADS), (unsigned)B), dim3(LD_FILTER_THREADS), 0, st,

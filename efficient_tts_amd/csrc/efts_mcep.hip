@@ -41,8 +41,7 @@ __global__ __launch_bounds__(LP_THREADS) void logspec_project_kernel(const void*
     cf (*tw2s)[16] = (cf (*)[16])(tw1s + 15);                      // [4][16]
     float* tab = (float*)(tw2s + 4);                               // [n_coef][LP_BINS]
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int len = min(max(lengths[b], 0), max_len);
-    const int T = len > LP_N / 2 ? 1 + len / H : 0;                // as efts_stft_mag: an item of at most N / 2 samples has no frames
+    const int len = st_len(lengths, b, max_len), T = st_frames(len, LP_N, H);       // as efts_stft_mag
     const int p0 = blockIdx.x * LP_UPB;
     if (blockIdx.x == 0 && threadIdx.x == 0) frames[b] = T;
     float win[16];
@@ -50,12 +49,7 @@ __global__ __launch_bounds__(LP_THREADS) void logspec_project_kernel(const void*
         fill_twiddles<LP_THREADS>(tw1s, tw2s);
         for (int i = threadIdx.x; i < n_coef * LP_BINS; i += LP_THREADS) tab[i] = table[i];
         __syncthreads();
-        const int off = (LP_N - W) / 2;
-#pragma unroll
-        for (int n1 = 0; n1 < 16; ++n1) {
-            const int k = 64 * n1 + lane - off;
-            win[n1] = k >= 0 && k < W ? window[k] : 0.f;
-        }
+        st_window_regs<16, 64>(window, W, LP_N, lane, win);
     }
     cf* zw = zs + wave * LP_BUF;
     const int fr = lane >> 5, kk = lane & 31;                      // what the lane holds after the tree: coefficient kk of frame t0 + fr
@@ -77,10 +71,8 @@ __global__ __launch_bounds__(LP_THREADS) void logspec_project_kernel(const void*
                 const int f = lane + 64 * i;
                 la[i] = lb[i] = 0.f;
                 if (f < LP_BINS) {
-                    const int fn = (LP_N - f) & (LP_N - 1);
-                    const cf zf = zw[bin_slot(f)], zn = zw[bin_slot(fn)];
-                    const float ar = 0.5f * (zf.x + zn.x), ai = 0.5f * (zf.y - zn.y);
-                    const float br = 0.5f * (zf.y + zn.y), bi = 0.5f * (zn.x - zf.x);
+                    float ar, ai, br, bi;
+                    st_split(zw[bin_slot(f)], zw[bin_slot((LP_N - f) & (LP_N - 1))], ar, ai, br, bi);
                     la[i] = logf(fmaxf(fmaf(ar, ar, ai * ai), 1e-7f));                  // the clamp of efts_stft_mag, before its square root
                     lb[i] = logf(fmaxf(fmaf(br, br, bi * bi), 1e-7f));
                 }
@@ -167,8 +159,7 @@ extern "C" int efts_logspec_project(const void* audio, int32_t pcm16, float pcm_
     if (H < 1 || H > N) return efts_fail(EFTS_ESHAPE, "efts_logspec_project: the hop must lie in 1 .. the FFT size");
     if (W < 2 || W > N) return efts_fail(EFTS_ESHAPE, "efts_logspec_project: the window length must lie in 2 .. the FFT size");
     if (n_coef < 1 || n_coef > LP_MAX_COEF) return efts_fail(EFTS_ESHAPE, "efts_logspec_project: n_coef 1 .. %d", LP_MAX_COEF);
-    if (B < 1 || B > 65535) return efts_fail(EFTS_ESHAPE, "efts_logspec_project: 1 .. 65535 items per launch");
-    if (max_len < 1 || max_len > 0x7fffffff - 4 * 2048) return efts_fail(EFTS_ESHAPE, "efts_logspec_project: max_len must lie in 1 .. 2^31 - 8193");
+    if (const char* why = efts_audio_bad_shape(B, max_len)) return efts_fail(EFTS_ESHAPE, "efts_logspec_project: %s", why);
     if (ld < max_len) return efts_fail(EFTS_ESHAPE, "efts_logspec_project: the leading dimension is smaller than the longest item");
     if (!audio || !lengths || !window || !table || !out || !frames) return efts_fail(EFTS_EINVAL, "efts_logspec_project: null pointer");
     if (((uintptr_t)audio % (pcm16 ? 2 : 4)) || ((uintptr_t)lengths & 3) || ((uintptr_t)window & 3) || ((uintptr_t)table & 3) || ((uintptr_t)out & 3) ||

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "efts_internal.h"
+#include "efts_stft_frame.h"
 
 namespace efts {
 
@@ -30,20 +31,6 @@ struct yin_geom {
     int xs_floats, ds;          // floats of the sample stage; row stride of d / d'
     float sr, threshold;
 };
-
-__device__ __forceinline__ float yin_sample(const float* p, long i, float) { return p[i]; }
-__device__ __forceinline__ float yin_sample(const int16_t* p, long i, float scale) { return (float)p[i] * scale; }
-
-__device__ __forceinline__ int wave_min_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_min_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
 
 template <typename T>
 __global__ __launch_bounds__(YIN_THREADS) void yin_kernel(const T* __restrict__ audio, long ld, float scale, const int* __restrict__ lengths, yin_geom g,
@@ -76,7 +63,7 @@ __global__ __launch_bounds__(YIN_THREADS) void yin_kernel(const T* __restrict__ 
         if (i < 0) i = -i;
         if (i >= len) i = 2L * (len - 1) - i;
         i = max(0L, min(i, (long)len - 1));
-        xs[p] = yin_sample(ab, i, scale);
+        xs[p] = pcm_sample(ab, i, scale);
     }
     __syncthreads();
 
@@ -143,8 +130,8 @@ __global__ __launch_bounds__(YIN_THREADS) void yin_kernel(const T* __restrict__ 
                 lowest = fminf(lowest, v);
                 if (v < g.threshold && cand == 0x7fffffff) cand = k;
             }
-            int tau = wave_min_int(cand);
-            lowest = wave_min_f(lowest);
+            int tau = wave_min(cand);
+            lowest = wave_min(lowest);
             float pitch = 0.f, ap = lowest;
             if (tau != 0x7fffffff) {                       // (uniform over the wave: the reads below are broadcasts)
                 while (tau + 1 <= g.tau_max - 1 && dr[tau + 1] < dr[tau]) ++tau;

@@ -20,15 +20,13 @@
 #include <stdint.h>
 
 #include "efts_internal.h"
+#include "efts_stft_frame.h"
 
 namespace efts {
 
 constexpr int RS_NB = 512, RS_THREADS = 256, RS_LANES = 16, RS_R = 4, RS_GROUPS = RS_THREADS / RS_LANES;
 constexpr long RS_TABLE_MAX = 1L << 20;                   // floats: 4 MiB
 constexpr int RS_LDS_MAX = 64 * 1024;                     // bytes of window + result row
-
-__device__ __forceinline__ float rs_sample(float v, float) { return v; }
-__device__ __forceinline__ float rs_sample(short v, float scale) { return (float)v * scale; }
 
 template <typename SAMPLE>
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const SAMPLE* __restrict__ in, long ld_in, const int* __restrict__ lengths,
@@ -54,7 +52,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const SAMPLE* __re
         const int span = (p0 + (RS_NB - 1) * M) / L + K;
         const int idx_lo = (int)min((long)span, max(0L, -lo)), idx_hi = (int)max(0L, min((long)span, (long)len - lo));
         const SAMPLE* src = in + (long)b * ld_in + lo;                     // only src[idx_lo .. idx_hi) is read: [0, len) of the item
-        for (int i = tid; i < span; i += RS_THREADS) xs[i] = (i >= idx_lo && i < idx_hi) ? rs_sample(src[i], pcm_scale) : 0.f;
+        for (int i = tid; i < span; i += RS_THREADS) xs[i] = (i >= idx_lo && i < idx_hi) ? pcm_sample(src, i, pcm_scale) : 0.f;
         __syncthreads();
         // ---- work items: (phase class c, chunk q): outputs j = c + L (q RS_R + r), r < RS_R, of this block
         const int Lc = min(L, RS_NB);

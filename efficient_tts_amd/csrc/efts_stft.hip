@@ -63,21 +63,15 @@ __global__ __launch_bounds__(st_cfg<N>::THREADS) void stft_kernel(const void* __
     __shared__ cf tw2s[C::P][M];
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane / G, l = lane % G;
-    const int len = min(max(lengths[b], 0), max_len);
-    const int T = len > N / 2 ? 1 + len / H : 0;                   // an item of at most N / 2 samples cannot be reflect-padded: no frames
+    const int len = st_len(lengths, b, max_len), T = st_frames(len, N, H);
     const int p0 = blockIdx.x * C::UPB;
     if (!DIST && blockIdx.x == 0 && threadIdx.x == 0) frames[b] = T;
     if (DIST && 2 * p0 >= T) return;                               // (uniform) nothing of this item here; the magnitudes' rows are zeroed below
     C::fill(tw1s, tw2s);
     __syncthreads();
     cf* zw = zs[wave * C::TPW + g];
-    const int off = (N - W) / 2;
     float win[M];
-#pragma unroll
-    for (int n1 = 0; n1 < M; ++n1) {
-        const int k = G * n1 + l - off;
-        win[n1] = k >= 0 && k < W ? window[k] : 0.f;
-    }
+    st_window_regs<M, G>(window, W, N, l, win);
     // from here on nothing synchronises more than one group: a group without work just passes
     for (int it = 0; it < ST_ITER; ++it) {
         const int t0 = 2 * (p0 + (it * C::WAVES + wave) * C::TPW + g);
@@ -105,10 +99,8 @@ __global__ __launch_bounds__(st_cfg<N>::THREADS) void stft_kernel(const void* __
                 const int f = l + G * i;
                 ma[i] = mb[i] = 1.f;
                 if (f < NBINS) {
-                    const int fn = (N - f) & (N - 1);
-                    const cf zf = zw[C::slot(f)], zn = zw[C::slot(fn)];
-                    const float ar = 0.5f * (zf.x + zn.x), ai = 0.5f * (zf.y - zn.y);
-                    const float br = 0.5f * (zf.y + zn.y), bi = 0.5f * (zn.x - zf.x);
+                    float ar, ai, br, bi;
+                    st_split(zw[C::slot(f)], zw[C::slot((N - f) & (N - 1))], ar, ai, br, bi);
                     ma[i] = sqrtf(fmaxf(fmaf(ar, ar, ai * ai), 1e-7f));         // stft_loss.py:32
                     mb[i] = sqrtf(fmaxf(fmaf(br, br, bi * bi), 1e-7f));
                 }
@@ -153,8 +145,7 @@ __global__ __launch_bounds__(256) void stft_reduce_kernel(const float* __restric
                                                           double* __restrict__ sums, long long* __restrict__ cells) {
     __shared__ float s[3 * ST_CHUNK];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int len = min(max(lengths[b], 0), max_len);
-    const int T = len > N / 2 ? 1 + len / H : 0;
+    const int T = st_frames(st_len(lengths, b, max_len), N, H);
     const float* p = part + (long)b * T_max * 3;
     double acc = 0.0;
     for (int c0 = 0; c0 < T; c0 += ST_CHUNK) {                     // (T is uniform in the workgroup)
@@ -169,15 +160,11 @@ __global__ __launch_bounds__(256) void stft_reduce_kernel(const float* __restric
     if (tid == 0) cells[b] = (long long)T * (N / 2 + 1);
 }
 
-static inline int64_t st_round16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 static const char* st_bad_shape(int32_t B, int32_t max_len, int32_t N, int32_t H, int32_t W) {
     if (N != 256 && N != 512 && N != 1024 && N != 2048) return "the FFT size must be 256, 512, 1024 or 2048";
     if (H < 1 || H > N) return "the hop must lie in 1 .. the FFT size";
     if (W < 2 || W > N) return "the window length must lie in 2 .. the FFT size";
-    if (B < 1 || B > 65535) return "1 .. 65535 items per launch";
-    if (max_len < 1 || max_len > 0x7fffffff - 4 * 2048) return "max_len must lie in 1 .. 2^31 - 8193";
-    return nullptr;
+    return efts_audio_bad_shape(B, max_len);
 }
 
 template <bool DIST>
@@ -208,7 +195,7 @@ extern "C" int efts_stft_mag(const void* audio, int32_t pcm16, float pcm_scale, 
 
 extern "C" int64_t efts_stft_dist_workspace_bytes(int32_t B, int32_t max_len, int32_t N, int32_t H) {
     if (st_bad_shape(B, max_len, N, H, 2)) return 0;
-    return st_round16((int64_t)B * (1 + max_len / H) * 3 * (int64_t)sizeof(float));
+    return efts_round16((int64_t)B * (1 + max_len / H) * 3 * (int64_t)sizeof(float));
 }
 
 extern "C" int efts_stft_dist(const void* x, int32_t x_pcm16, int64_t ldx, const void* y, int32_t y_pcm16, int64_t ldy, float pcm_scale, const int32_t* lengths,

@@ -22,6 +22,7 @@
 
 #include "efts_internal.h"
 #include "efts_fft.h"
+#include "efts_stft_frame.h"
 
 // every product and sum below is rounded as written (the fused ones are written as fmaf / fma): a sum over lanes must leave the same bits in
 // every lane, which a product contracted into one lane's addition would break
@@ -48,7 +49,7 @@ __host__ __device__ __forceinline__ int si_frames(int len) { return len >= SI_FR
 __global__ __launch_bounds__(64 * SI_E_WAVES) void stoi_energy_kernel(const float* __restrict__ x, long ldx, const int* __restrict__ lengths, int max_len,
                                                                        const float* __restrict__ window, float* __restrict__ e, int F_max) {
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int F = si_frames(min(max(lengths[b], 0), max_len));
+    const int F = si_frames(st_len(lengths, b, max_len));
     const int f0 = (blockIdx.x * SI_E_WAVES + wave) * SI_E_ITER;
     if (f0 >= F) return;
     float w[4];
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(256) void stoi_select_kernel(const float* __restric
     __shared__ float wm[4];
     __shared__ int wt[4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int F = si_frames(min(max(lengths[b], 0), max_len));
+    const int F = si_frames(st_len(lengths, b, max_len));
     const float* eb = e + (long)b * F_max;
     int* kb = klist + (long)b * F_max;
     float m = 0.f;                                           // (energies are >= 0)
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(32 * SI_S_GROUPS) void stoi_spectra_kernel(const fl
     __shared__ cf tw1s[15][32];
     __shared__ cf tw2s[2][16];
     const int b = blockIdx.y, g = threadIdx.x >> 5, l = threadIdx.x & 31;
-    const int F = si_frames(min(max(lengths[b], 0), max_len));
+    const int F = si_frames(st_len(lengths, b, max_len));
     const int T = min(max(kept[b], 0), F) - 1;               // spectral frames: K - 1
     const int t0 = blockIdx.x * (SI_S_GROUPS * SI_S_ITER);
     if (t0 >= T) return;                                     // (uniform) nothing of this item here
@@ -154,8 +155,9 @@ __global__ __launch_bounds__(32 * SI_S_GROUPS) void stoi_spectra_kernel(const fl
         float acc = 0.f;
         for (int f = si_lo[j]; f < si_hi[j]; ++f) {
             const cf zf = zw[si_plan::slot(f)], zn = zw[si_plan::slot(512 - f)];
-            const float re = second ? 0.5f * (zf.y + zn.y) : 0.5f * (zf.x + zn.x);
-            const float im = second ? 0.5f * (zn.x - zf.x) : 0.5f * (zf.y - zn.y);
+            float ar, ai, br, bi;
+            st_split(zf, zn, ar, ai, br, bi);
+            const float re = second ? br : ar, im = second ? bi : ai;
             acc += fmaf(re, re, im * im);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the next transform overwrites zw
@@ -252,8 +254,6 @@ __global__ __launch_bounds__(64) void stoi_reduce_kernel(const double* __restric
     }
 }
 
-static inline int64_t si_round16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 struct si_layout { int64_t F_max, T_max, M_max, e, klist, X, Y, seg, bytes; };
 
 static si_layout si_make_layout(int32_t B, int32_t max_len) {
@@ -262,19 +262,13 @@ static si_layout si_make_layout(int32_t B, int32_t max_len) {
     L.T_max = L.F_max > 1 ? L.F_max - 1 : 0;
     L.M_max = L.T_max > SI_SEG - 1 ? L.T_max - (SI_SEG - 1) : 0;
     int64_t at = 0;
-    L.e = at;     at += si_round16((int64_t)B * L.F_max * 4);
-    L.klist = at; at += si_round16((int64_t)B * L.F_max * 4);
-    L.X = at;     at += si_round16((int64_t)B * L.T_max * SI_ROW * 4);
-    L.Y = at;     at += si_round16((int64_t)B * L.T_max * SI_ROW * 4);
-    L.seg = at;   at += si_round16((int64_t)B * L.M_max * 2 * 8);
+    L.e = at;     at += efts_round16((int64_t)B * L.F_max * 4);
+    L.klist = at; at += efts_round16((int64_t)B * L.F_max * 4);
+    L.X = at;     at += efts_round16((int64_t)B * L.T_max * SI_ROW * 4);
+    L.Y = at;     at += efts_round16((int64_t)B * L.T_max * SI_ROW * 4);
+    L.seg = at;   at += efts_round16((int64_t)B * L.M_max * 2 * 8);
     L.bytes = at > 16 ? at : 16;
     return L;
-}
-
-static const char* si_bad_shape(int32_t B, int32_t max_len) {
-    if (B < 1 || B > 65535) return "1 .. 65535 items per launch";
-    if (max_len < 1 || max_len > 0x7fffffff - 4 * 2048) return "max_len must lie in 1 .. 2^31 - 8193";
-    return nullptr;
 }
 
 }  // namespace efts
@@ -282,14 +276,14 @@ static const char* si_bad_shape(int32_t B, int32_t max_len) {
 using namespace efts;
 
 extern "C" int64_t efts_stoi_workspace_bytes(int32_t B, int32_t max_len) {
-    if (si_bad_shape(B, max_len)) return 0;
+    if (efts_audio_bad_shape(B, max_len)) return 0;
     return si_make_layout(B, max_len).bytes;
 }
 
 extern "C" int efts_stoi(const float* x, int64_t ldx, const float* y, int64_t ldy, const int32_t* lengths, int32_t max_len, const float* window,
                          double* stoi, double* estoi, int32_t* frames, int32_t* kept, int32_t* segments, void* workspace, int64_t workspace_bytes,
                          int32_t B, void* stream) {
-    if (const char* why = si_bad_shape(B, max_len)) return efts_fail(EFTS_EINVAL, "efts_stoi: %s", why);
+    if (const char* why = efts_audio_bad_shape(B, max_len)) return efts_fail(EFTS_EINVAL, "efts_stoi: %s", why);
     if (ldx < max_len || ldy < max_len) return efts_fail(EFTS_EINVAL, "efts_stoi: a leading dimension is smaller than the longest item");
     const si_layout L = si_make_layout(B, max_len);
     if (workspace_bytes < L.bytes) return efts_fail(EFTS_EINVAL, "efts_stoi: the workspace is smaller than efts_stoi_workspace_bytes asks for");

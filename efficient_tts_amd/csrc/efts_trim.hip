@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "efts_internal.h"
+#include "efts_stft_frame.h"
 
 namespace efts {
 
@@ -34,7 +35,6 @@ template <> struct tr_traits<short> {
     static constexpr int V = 8;                           // samples per 16 bytes
     __device__ static __forceinline__ energy_t sq(energy_t acc, short v) { const int x = v; return acc + (energy_t)(unsigned)(x * x); }
     __device__ static __forceinline__ peak_t mag(short v) { const int x = v; return x < 0 ? -x : x; }
-    __device__ static __forceinline__ float tofloat(short v) { return (float)v; }
 };
 template <> struct tr_traits<float> {
     typedef float energy_t;
@@ -42,32 +42,7 @@ template <> struct tr_traits<float> {
     static constexpr int V = 4;
     __device__ static __forceinline__ energy_t sq(energy_t acc, float v) { return fmaf(v, v, acc); }
     __device__ static __forceinline__ peak_t mag(float v) { return fabsf(v); }
-    __device__ static __forceinline__ float tofloat(float v) { return v; }
 };
-
-__device__ __forceinline__ unsigned long long tr_shfl_xor(unsigned long long v, int o) {
-    const unsigned lo = __shfl_xor((unsigned)v, o), hi = __shfl_xor((unsigned)(v >> 32), o);
-    return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ float tr_shfl_xor(float v, int o) { return __shfl_xor(v, o); }
-__device__ __forceinline__ int tr_shfl_xor(int v, int o) { return __shfl_xor(v, o); }
-
-// the documented order of a wave's sum: v = v + (the value 32, 16, 8, 4, 2, 1 lanes across); every lane ends with the same bits
-template <typename T> __device__ __forceinline__ T tr_wave_sum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + tr_shfl_xor(v, o);
-    return v;
-}
-template <typename T> __device__ __forceinline__ T tr_wave_max(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const T w = tr_shfl_xor(v, o); v = w > v ? w : v; }
-    return v;
-}
-template <typename T> __device__ __forceinline__ T tr_wave_min(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const T w = tr_shfl_xor(v, o); v = w < v ? w : v; }
-    return v;
-}
 
 // Samples s_lo .. s_lo + n_span - 1 of the row into xs[sh + i] (xs 16-byte aligned, room for n_span + V); 0 outside [0, len).
 // Only [0, len) of the row is read.  Returns sh.  Ends WITHOUT a barrier.
@@ -116,14 +91,14 @@ __global__ __launch_bounds__(TR_THREADS) void trim_energy_kernel(const S* __rest
             const S* p = x + w * H;
             E acc = 0;
             for (int i = lane; i < seg; i += 64) acc = tr_traits<S>::sq(acc, p[i]);
-            acc = tr_wave_sum(acc);
+            acc = wave_sum(acc);
             if (lane == 0) part[w] = acc;
         } else {
             const int k = w - nseg;
             const S* p = x + pad + k * H;
             P m = 0;
             for (int i = lane; i < H; i += 64) { const P v = tr_traits<S>::mag(p[i]); m = v > m ? v : m; }
-            m = tr_wave_max(m);
+            m = wave_max_cmp(m);
             if (lane == 0) chunk_peak[(long)b * T_max + f0 + k] = m;
         }
     }
@@ -152,7 +127,7 @@ __global__ __launch_bounds__(TR_THREADS) void trim_bounds_kernel(const int* __re
     const E* e = energy + (long)b * T_max;
     E m = 0;
     for (int t = tid; t < T; t += TR_THREADS) { const E v = e[t]; m = v > m ? v : m; }
-    m = tr_wave_max(m);
+    m = wave_max_cmp(m);
     if (lane == 0) s_e[wave] = m;
     __syncthreads();
     E e_max = s_e[0];
@@ -165,8 +140,8 @@ __global__ __launch_bounds__(TR_THREADS) void trim_bounds_kernel(const int* __re
         int lo = T, hi = -1;
         for (int t = tid; t < T; t += TR_THREADS)
             if ((double)e[t] * r > dmax) { lo = min(lo, t); hi = max(hi, t); }
-        lo = tr_wave_min(lo);
-        hi = tr_wave_max(hi);
+        lo = wave_min_cmp(lo);
+        hi = wave_max_cmp(hi);
         if (lane == 0) { s_lo[wave] = lo; s_hi[wave] = hi; }
         __syncthreads();
         lo = s_lo[0], hi = s_hi[0];
@@ -183,7 +158,7 @@ __global__ __launch_bounds__(TR_THREADS) void trim_bounds_kernel(const int* __re
             const P* cp = chunk_peak + (long)b * T_max;
             P p = 0;
             for (int c = start / H + tid; c < (end + H - 1) / H; c += TR_THREADS) { const P v = cp[c]; p = v > p ? v : p; }
-            p = tr_wave_max(p);
+            p = wave_max_cmp(p);
             if (lane == 0) s_p[wave] = p;
             __syncthreads();
             p = s_p[0];
@@ -225,19 +200,17 @@ __global__ __launch_bounds__(TR_THREADS) void trim_copy_kernel(const S* __restri
         for (int q = tid; q < n4; q += TR_THREADS) {
             const int j = 4 * q;
             float4 v;
-            v.x = j + 0 < n_valid ? tr_traits<S>::tofloat(x[j + 0]) * g : 0.f;
-            v.y = j + 1 < n_valid ? tr_traits<S>::tofloat(x[j + 1]) * g : 0.f;
-            v.z = j + 2 < n_valid ? tr_traits<S>::tofloat(x[j + 2]) * g : 0.f;
-            v.w = j + 3 < n_valid ? tr_traits<S>::tofloat(x[j + 3]) * g : 0.f;
+            v.x = j + 0 < n_valid ? pcm_sample(x, j + 0, 1.f) * g : 0.f;
+            v.y = j + 1 < n_valid ? pcm_sample(x, j + 1, 1.f) * g : 0.f;
+            v.z = j + 2 < n_valid ? pcm_sample(x, j + 2, 1.f) * g : 0.f;
+            v.w = j + 3 < n_valid ? pcm_sample(x, j + 3, 1.f) * g : 0.f;
             *(float4*)(orow + j) = v;
         }
-        for (int j = 4 * n4 + tid; j < n_row; j += TR_THREADS) orow[j] = j < n_valid ? tr_traits<S>::tofloat(x[j]) * g : 0.f;
+        for (int j = 4 * n4 + tid; j < n_row; j += TR_THREADS) orow[j] = j < n_valid ? pcm_sample(x, j, 1.f) * g : 0.f;
     } else {
-        for (int j = tid; j < n_row; j += TR_THREADS) orow[j] = j < n_valid ? tr_traits<S>::tofloat(x[j]) * g : 0.f;
+        for (int j = tid; j < n_row; j += TR_THREADS) orow[j] = j < n_valid ? pcm_sample(x, j, 1.f) * g : 0.f;
     }
 }
-
-static inline int64_t tr_round16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 }  // namespace efts
 
@@ -246,7 +219,7 @@ using namespace efts;
 extern "C" int64_t efts_trim_workspace_bytes(int32_t B, int64_t max_len, int32_t H, int32_t pcm16) {
     if (B <= 0 || max_len <= 0 || H <= 0) return 0;
     const int64_t T_max = (max_len + H - 1) / H;
-    return tr_round16((int64_t)B * T_max * (pcm16 ? 8 : 4)) + tr_round16((int64_t)B * T_max * 4);
+    return efts_round16((int64_t)B * T_max * (pcm16 ? 8 : 4)) + efts_round16((int64_t)B * T_max * 4);
 }
 
 template <typename S>
@@ -266,7 +239,7 @@ static int trim_launch(const S* in, int64_t ld_in, const int32_t* lengths, int32
     if (!(r > 1.0)) return efts_fail(EFTS_EINVAL, "%s: the threshold ratio r = 10^(top_db / 10) must be > 1", who);
     const int T_max = (int)((ld_in + H - 1) / H);
     E* energy = (E*)workspace;
-    P* chunk_peak = (P*)((char*)workspace + tr_round16((int64_t)B * T_max * (int64_t)sizeof(E)));
+    P* chunk_peak = (P*)((char*)workspace + efts_round16((int64_t)B * T_max * (int64_t)sizeof(E)));
     // a frame as W / H hop segments when that divides and a wave has work per segment; else one segment per frame (the frame itself)
     const bool hops = W % H == 0 && H >= 64;
     const int seg = hops ? H : W, R = hops ? W / H : 1;

@@ -1,6 +1,6 @@
 """efts_logmel_fft alone in a loop (64 x 800 frames): us per launch -- the launch itself (ctypes call, events around 50 launches) and the
 LogMelFrontend call around it (host-side length checks + two small H2D copies + the output allocation).
-EFTS_LIB selects a lab build (FF_ABL ablations: tools/r06_fft_abl.sh)"""
+EFTS_LIB selects another build of the library"""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
