@@ -143,6 +143,11 @@ static int rc_check(const efts_resconv5_args* a, const char* who) {
     if (a->split == 2 && a->x_lo) return efts_fail(EFTS_EINVAL, "%s: x_lo is for split-1 planes (split 2 carries lo inside x)", who);
     if (a->y_split == 2 && a->y_lo) return efts_fail(EFTS_EINVAL, "%s: y_lo is for split-1 output planes", who);
     if (!(a->taps == 0 || a->taps == 3 || a->taps == 5)) return efts_fail(EFTS_EINVAL, "%s: taps must be 5 (0 = default) or 3", who);
+    // the epilogue addresses residual columns 0 .. n - 1 of whichever stream carries the residual: a plane holds nchunk * 64 (bf16) or
+    // nchunk * 32 (bf16x3) of them, and a narrower one would be read past its last column (the row's padding or the next row)
+    if (!a->x_f32 && !a->no_residual && (int64_t)a->nchunk * (a->split == 1 ? 64 : 32) < a->n)
+        return efts_fail(EFTS_ESHAPE, "%s: residual from the planes, which hold nchunk * %d = %lld columns, fewer than n = %d (give x_f32 or no_residual)",
+                         who, a->split == 1 ? 64 : 32, (long long)a->nchunk * (a->split == 1 ? 64 : 32), a->n);
     return 0;
 }
 

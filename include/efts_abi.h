@@ -214,8 +214,10 @@ int efts_gemm(const efts_gemm_args* a, void* stream);
  * on a padded row space, for long row spaces (the mel-length stacks).  The contraction runs on the operand plane `x`
  * (format `split`); the RESIDUAL x is taken, in this order, from x_f32 (fp32 [m][ldr]) if given, else from the
  * planes as hi + lo: split 2 planes carry lo inside x; a split 1 plane may come with a separate lo plane x_lo of the
- * same layout (NULL: the residual is the bf16 value itself).  Outputs, any combination: y (operand plane of format
- * y_split; with y_split 1 an optional lo plane y_lo so that the next layer can rebuild its residual), y_f32.
+ * same layout (NULL: the residual is the bf16 value itself).  A residual from the planes needs planes of at least
+ * n columns: nchunk * 64 (split 1) or nchunk * 32 (split 2) < n without x_f32 and without no_residual is EFTS_ESHAPE.
+ * Outputs, any combination: y (operand plane of format y_split; with y_split 1 an optional lo plane y_lo so that the
+ * next layer can rebuild its residual), y_f32.
  * Bit-identical to efts_gemm(taps 5, LeakyReLU, resid, rowmask) on the same operands.
  * n (= cout) must be a multiple of 256; x is read from 2 rows before row 0 to 144 rows after row m - 1 (the guard rows).
  * ---------------------------------------------------------------------------------- */

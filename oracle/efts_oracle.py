@@ -205,9 +205,10 @@ def scaled_dot_attention(q: torch.Tensor, k: torch.Tensor, key_mask: torch.Tenso
     return a.transpose(1, 2)
 
 
-def index_vector(text_mask: torch.Tensor) -> torch.Tensor:
-    """p[b,i] = i * text_mask[b,i]  (efficient_tts.py:287-297)."""
-    return torch.arange(text_mask.shape[1], dtype=torch.float32)[None, :] * text_mask
+def index_vector(text_mask: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """p[b,i] = i * text_mask[b,i]  (efficient_tts.py:287-297); dtype: that of the parameters (float64 when the oracle is evaluated
+    in double precision)."""
+    return torch.arange(text_mask.shape[1], dtype=dtype)[None, :] * text_mask
 
 
 def imv_generator(alpha: torch.Tensor, p: torch.Tensor, mel_mask: torch.Tensor,
@@ -218,9 +219,9 @@ def imv_generator(alpha: torch.Tensor, p: torch.Tensor, mel_mask: torch.Tensor,
     soft_idx = torch.einsum("bij,bi->bj", alpha, p)
     d = torch.relu(soft_idx[:, 1:] - soft_idx[:, :-1])
     d = torch.cat([torch.zeros_like(soft_idx[:, :1]), d], dim=1)
-    pi = torch.cumsum(d, dim=1) * mel_mask.float()
+    pi = torch.cumsum(d, dim=1) * mel_mask.to(d.dtype)
     top = pi.max(dim=1).values.clamp(min=1e-8)
-    return pi / top[:, None] * (text_lengths.float()[:, None] - 1.0)
+    return pi / top[:, None] * (text_lengths.to(pi.dtype)[:, None] - 1.0)
 
 
 def aligned_positions(pi: torch.Tensor, p: torch.Tensor, mel_mask: torch.Tensor,
@@ -231,8 +232,8 @@ def aligned_positions(pi: torch.Tensor, p: torch.Tensor, mel_mask: torch.Tensor,
     en = -sigma_e * (pi[:, None, :] - p[:, :, None]) ** 2
     en = en.masked_fill(~mel_mask[:, None, :], -float("inf"))
     beta = torch.softmax(en, dim=2)
-    q = torch.arange(mel_mask.shape[1], dtype=torch.float32)[None, :] * mel_mask.float()
-    return torch.einsum("bij,bj->bi", beta, q) * text_mask.float()
+    q = torch.arange(mel_mask.shape[1], dtype=pi.dtype)[None, :] * mel_mask.to(pi.dtype)
+    return torch.einsum("bij,bj->bi", beta, q) * text_mask.to(pi.dtype)
 
 
 def reconstruct_alignment(e: torch.Tensor, sigma: float, mel_mask: Optional[torch.Tensor],
@@ -241,9 +242,9 @@ def reconstruct_alignment(e: torch.Tensor, sigma: float, mel_mask: Optional[torc
     (padded columns use q=0) and padded text rows get -inf  (efficient_tts.py:347-375)."""
     if mel_mask is not None:
         t2 = mel_mask.shape[1]
-    q = torch.arange(t2, dtype=torch.float32)[None, :].expand(e.shape[0], t2)
+    q = torch.arange(t2, dtype=e.dtype)[None, :].expand(e.shape[0], t2)
     if mel_mask is not None:
-        q = q * mel_mask.float()
+        q = q * mel_mask.to(e.dtype)
     en = -sigma * (q[:, None, :] - e[:, :, None]) ** 2
     if text_mask is not None:
         en = en.masked_fill(~text_mask[:, :, None], -float("inf"))
@@ -292,7 +293,7 @@ def forward(P: Params, text: torch.Tensor, text_lengths: torch.Tensor, speech: t
         mel_h = F.linear(mel_h, P["mel_query_fc.weight"], P["mel_query_fc.bias"])
 
     alpha = scaled_dot_attention(mel_h, key, text_mask).masked_fill(~both, 0.0)  # :167-168
-    p = index_vector(text_mask)                                                  # :171
+    p = index_vector(text_mask, alpha.dtype)                                     # :171
     imv = imv_generator(alpha, p, mel_mask, text_lengths)                        # :174
     e = aligned_positions(imv, p, mel_mask, text_mask, hp["sigma_e"])            # :178-180
     ralpha = reconstruct_alignment(e, hp["sigma"], mel_mask, text_mask).masked_fill(~both, 0.0)  # :184-186

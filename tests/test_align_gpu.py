@@ -67,9 +67,13 @@ def _expand_ref64(e, v, tl, ml, sigma, T2):
 @pytest.mark.parametrize("B,T1,T2,masked", [(3, 37, 211, True), (2, 128, 800, True), (2, 200, 333, True), (1, 96, 577, False),
                                             (2, 256, 70, True), (4, 16, 31, True)])
 def test_expand_vs_fp64_and_the_unfused_chain(B, T1, T2, masked, fmt):
+    expand_vs_fp64_and_the_unfused_chain(B, T1, T2, masked, fmt)
+
+
+def expand_vs_fp64_and_the_unfused_chain(B, T1, T2, masked, fmt, C=512, report=False):
+    """the body of test_expand_vs_fp64_and_the_unfused_chain at C channels"""
     from efficient_tts_amd import lib as L, ops as P
     dev = _dev()
-    C = 512
     g = torch.Generator().manual_seed(T1 * 13 + T2)
     tl = _lengths(B, T1, g) if masked else None
     ml = _lengths(B, T2, g) if masked else None
@@ -122,6 +126,10 @@ def test_expand_vs_fp64_and_the_unfused_chain(B, T1, T2, masked, fmt):
     a64, h64 = _expand_ref64(e, v, tl, ml, 0.01, T2)
     scale = float(h64.abs().max())
     tol = 2e-5 * scale + (0.0 if fmt == "f32" else 2.0 ** -16 * scale)      # + the 16-bit hi/lo stream format
+    if report:
+        print(f"expand C {C} {B}x{T1}x{T2} {fmt}: |fused - fp64| {float((got.double() - h64).abs().max()):.3e} (bound {tol:.3e}), "
+              f"|alpha - fp64| {float((ra1.cpu().double() - a64).abs().max()):.3e} (bound 2e-6), "
+              f"|fused - chain| {float((got - h0.view().cpu()).abs().max()):.3e} (bound {tol:.3e})")
     assert float((got.double() - h64).abs().max()) <= tol
     assert float((ra1.cpu().double() - a64).abs().max()) <= 2e-6
     # against the chain: same maths in the same operand format, different summation order of the softmax only

@@ -107,6 +107,15 @@ def test_fused_and_training_entry_points_refuse_format3(lib):
     assert lib.efts_expand(e, None) == -1 and b"split" in lib.efts_last_error()
     assert lib.efts_embed_conv(4096, None, 8192, 16384, None, 0.1, 32768, 65536, 128, 1, 4, 6, 128, 76, 5, 3, None) == -1
     assert b"split" in lib.efts_last_error()
+    # efts_resconv5 with the residual taken from planes that hold fewer than n columns (nchunk * 64 in bf16, nchunk * 32 in bf16x3): EFTS_ESHAPE,
+    # while the same shape with an fp32 residual stream or without the residual term passes the checks (tests/test_resconv_gpu.py runs those)
+    for split, nchunk in ((1, 3), (2, 6), (1, 1), (2, 7)):
+        r = L.ResConv5Args()
+        r.x, r.ldx, r.w, r.ldw, r.w_tap_stride = 4096, nchunk * 128, 8192, nchunk * 128, 256 * nchunk * 128
+        r.split, r.m, r.n, r.nchunk, r.slope = split, 256, 256, nchunk, 0.1
+        r.y_f32, r.ldo = 16384, 256
+        for rc in (lib.efts_resconv5(r, None), lib.efts_resconv5_multi((L.ResConv5Args * 1)(r), 1, None)):
+            assert rc == -2 and b"residual from the planes" in lib.efts_last_error() and b"fewer than n = 256" in lib.efts_last_error()
     assert lib.efts_pack_weight_t(4096, 8192, 2048, 512, 512, 5, 3, None) == -1 and b"split" in lib.efts_last_error()
     assert lib.efts_pack_weights_grouped(4096, 1, None, 2048, 2048, 512, 512, 5, 3, 1, None) == -1 and b"split" in lib.efts_last_error()
     assert lib.efts_pack_t(4096, 512, 8192, 256, 0, 3, 64, 512, -2, 5, 64, None) == -1 and b"split" in lib.efts_last_error()

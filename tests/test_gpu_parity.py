@@ -510,9 +510,13 @@ def test_soft_index_in_the_gemm_epilogue_equals_the_two_kernel_path(shape):
 def test_frame_linear_equals_pack_rows_plus_gemm(split, shape):
     """efts_frame_linear (the prenet straight from the caller's fp32 frames) against efts_pack_rows + efts_gemm on the same weights:
     bit for bit (same operand rounding, same k order), fp32 output, operand plane and remainder plane; gap rows stay zero."""
+    frame_linear_equals_pack_rows_plus_gemm(split, shape)
+
+
+def frame_linear_equals_pack_rows_plus_gemm(split, shape, C=512, max_workgroups=0):
+    """the body of test_frame_linear_equals_pack_rows_plus_gemm for n = C output channels and a workgroup cap"""
     from efficient_tts_amd import lib as L, ops as P
     B, T, cin = shape
-    C = 512
     dev = torch.device("cuda:0")
     torch.manual_seed(T + cin)
     rs = P.Rows(B, T)
@@ -531,7 +535,7 @@ def test_frame_linear_equals_pack_rows_plus_gemm(split, shape):
                    out_plane=P.Plane.for_rows(rs, C, 1, dev), out_plane_lo=l_ref)
         o = P.F32Rows(rs, C, dev); y = P.Plane.for_rows(rs, C, split, dev)
         yl = P.Plane.for_rows(rs, C, 1, dev) if split == 1 else None
-        P.frame_linear(x=x, w=pw, bias=bias, act=L.ACT_LEAKY, slope=0.1, rs=rs, y=y, y_lo=yl, y_f32=o)
+        P.frame_linear(x=x, w=pw, bias=bias, act=L.ACT_LEAKY, slope=0.1, rs=rs, y=y, y_lo=yl, y_f32=o, max_workgroups=max_workgroups)
         torch.cuda.synchronize()
     assert torch.equal(o.buf, o_ref.buf), float((o.buf - o_ref.buf).abs().max())
     bf = lambda pl: pl.buf.view(torch.bfloat16)            # compared as numbers: the masked gap rows of efts_gemm are -0 where the value was negative

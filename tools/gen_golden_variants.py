@@ -6,7 +6,8 @@
 
 use_masking=False (the ctor default), share_text_encoder_key_value=True, use_mel_query_fc=True, delta_e_method_1=False, each on
 the ragged (2, 16, 64) case of gen_golden.py with parameter gradients (strided samples + norms); share_text_encoder_key_value and
-delta_e_method_1=False also on one free-running utterance.  Writes tests/golden/variant_<name>.npz; only data is stored."""
+delta_e_method_1=False also on one free-running utterance; likewise the widths n_channels = symbol_embedding_dim = 256 / 768 / 1024.
+Writes tests/golden/variant_<name>.npz; only data is stored."""
 import os
 import sys
 
@@ -29,9 +30,15 @@ VARIANTS = dict(
     k11=dict(k_size=11),                                            # the stacks on efts_gemm's 7- / 11-tap forms
     gelu=dict(nonlinear_activation="GELU", nonlinear_activation_params={}),                 # any other torch.nn activation (efts_modules.py:32-35):
     elu=dict(nonlinear_activation="ELU", nonlinear_activation_params={"alpha": 0.7}),       # a smooth one and one with a parameter
+    c256=dict(n_channels=256, symbol_embedding_dim=256),            # widths other than the shipped 512 (efficient_tts.py:30-31): 1 / 3 / 4
+    c768=dict(n_channels=768, symbol_embedding_dim=768),            # column tiles of 256 in the persistent residual-layer kernel
+    c1024=dict(n_channels=1024, symbol_embedding_dim=1024),
+    # (no odim other than 80: the reference's training forward masks mel_pred with a mask repeated 80 times, efficient_tts.py:199)
 )
 # what the oracle's hyper-parameter dict calls an option, where it differs from the reference ctor's keyword
-ORACLE_HP = dict(relu=dict(leaky_slope=0.0), gelu=dict(activation=("GELU", {})), elu=dict(activation=("ELU", {"alpha": 0.7})))
+ORACLE_HP = dict(relu=dict(leaky_slope=0.0), gelu=dict(activation=("GELU", {})), elu=dict(activation=("ELU", {"alpha": 0.7})),
+                 c256=dict(n_channels=256), c768=dict(n_channels=768), c1024=dict(n_channels=1024))
+FREE_RUNNING = ("sharekv", "delta2", "k3", "k7", "k11", "gelu", "elu", "c256", "c768", "c1024")
 
 
 def main():
@@ -83,7 +90,7 @@ def main():
             d["gradnorm:" + k] = np.float64(g.double().norm())
         print(f"  [{name}] oracle vs reference param-grad worst rel-to-max {worst:.3e}"
               + "".join(f"; {k}: zero in exact arithmetic (|grad| max: reference {a:.1e}, oracle {b:.1e}), not in the figure" for k, a, b in zero_like))
-        if name in ("sharekv", "delta2", "k3", "k7", "k11", "gelu", "elu"):                # free-running path: value = key (:252-253) / positions from 0 (:261-265) / k3 stacks
+        if name in FREE_RUNNING:                # free-running path: value = key (:252-253) / positions from 0 (:261-265) / k3 stacks
             ids = torch.randint(1, 76, (1, 23), generator=torch.Generator().manual_seed(5))
             m.remove_weight_norm()
             with torch.no_grad():
