@@ -28,7 +28,12 @@ HiFi-GAN V1 generator (efficient_tts_amd.vocoder).  Differences from the referen
   * `--denoise S` (S > 0, for example 0.01) removes the vocoder's bias noise on the device (efficient_tts_amd.denoise): the magnitude spectrum
     of the vocoder's answer to a blank mel is measured once after the vocoder is built, and S times it is subtracted from every frame of
     every utterance (1024-point STFT, hop 256, phases kept) -- behind the vocoder, in front of `--loudness` and `--sampling_rate`;
-    `--write_f0` then tracks the denoised signal.  Without the flag the wav files are byte for byte what they were.
+    `--write_f0` then tracks the denoised signal.  Without the flag the wav files are byte for byte what they were;
+  * `--limit_true_peak DBTP` (at most 0, for example -1) holds every utterance under that true-peak ceiling on the device
+    (efficient_tts_amd.limiter): a look-ahead limiter built for the OUTPUT rate, the last step in front of the 16-bit quantisation, behind
+    `--sampling_rate`, so it sees the samples that are written.  Together with `--loudness` the normaliser runs without its own ceiling --
+    the target is reached and the limiter takes the peaks -- and an explicit `--loudness_peak_ceiling` is refused.  Without the flag the
+    wav files are byte for byte what they were.
 """
 from __future__ import annotations
 
@@ -47,6 +52,7 @@ import yaml
 from efficient_tts_amd import models
 from efficient_tts_amd.denoise import BiasDenoiser
 from efficient_tts_amd.griffinlim import GriffinLimVocoder
+from efficient_tts_amd.limiter import PeakLimiter
 from efficient_tts_amd.loudness import LoudnessNormalizer
 from efficient_tts_amd.pitch import PitchTracker
 from efficient_tts_amd.resample import QUALITIES, Resampler
@@ -55,6 +61,14 @@ from efficient_tts_amd.vocoder import HiFiGANGenerator, load_hifigan_generator
 _V1 = dict(resblock="1", upsample_rates=[8, 8, 2, 2], upsample_kernel_sizes=[16, 16, 4, 4], upsample_initial_channel=512,
            resblock_kernel_sizes=[3, 7, 11], resblock_dilation_sizes=[[1, 3, 5], [1, 3, 5], [1, 3, 5]], num_mels=80)
 SAMPLING_RATE = 22050
+
+
+class _Explicit(argparse.Action):
+    """stores the value and notes that the argument was given, so that its default can be told from the same value spelled out"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        setattr(namespace, self.dest + "_given", True)
 
 
 def get_parser() -> argparse.ArgumentParser:
@@ -83,7 +97,10 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--f0_smooth", action="store_true", help="--write_f0: smooth the contour across frames (the cheapest path over the lags of all frames)")
     p.add_argument("--loudness", type=float, default=None,
                    help="bring every utterance to this integrated loudness in LUFS (ITU-R BS.1770), for example -23 (default: leave the level)")
-    p.add_argument("--loudness_peak_ceiling", type=float, default=0.99, help="--loudness: no sample may exceed this (default 0.99; <= 0: no ceiling)")
+    p.add_argument("--loudness_peak_ceiling", type=float, default=0.99, action=_Explicit,
+                   help="--loudness: no sample may exceed this (default 0.99; <= 0: no ceiling; not together with --limit_true_peak)")
+    p.add_argument("--limit_true_peak", type=float, default=None,
+                   help="hold every utterance under this true-peak ceiling in dBTP, for example -1 (default: no limiter)")
     p.add_argument("--denoise", type=float, default=None,
                    help="subtract this many times the vocoder's bias spectrum from every frame's magnitudes, for example 0.01 (default: no denoiser)")
     p.add_argument("--verbose", type=int, default=1)
@@ -170,7 +187,24 @@ def build_loudness(args, device=None):
     if args.no_vocoder:
         raise ValueError("--loudness sets the level of the vocoder's output: it cannot be combined with --no_vocoder")
     ceiling = args.loudness_peak_ceiling
+    if getattr(args, "limit_true_peak", None) is not None:       # the limiter behind it takes the peaks: the target is reached
+        ceiling = 0.0
     return LoudnessNormalizer(device, SAMPLING_RATE, target_lufs=args.loudness, peak_ceiling=ceiling if ceiling > 0 else None)
+
+
+def build_limiter(args, out_rate: int = SAMPLING_RATE, device=None):
+    """the PeakLimiter for the samples that are written, at their rate, or None without --limit_true_peak (checked on the host, before
+    anything is loaded)"""
+    if args.limit_true_peak is None:
+        return None
+    if args.no_vocoder:
+        raise ValueError("--limit_true_peak limits the vocoder's output: it cannot be combined with --no_vocoder")
+    if not (math.isfinite(args.limit_true_peak) and args.limit_true_peak <= 0.0):
+        raise ValueError("--limit_true_peak must be a finite ceiling of at most 0 dBTP, for example -1")
+    if getattr(args, "loudness_peak_ceiling_given", False):
+        raise ValueError("--limit_true_peak takes the peaks behind --loudness, which then runs without a ceiling of its own: "
+                         "leave --loudness_peak_ceiling out")
+    return PeakLimiter(device, int(out_rate), ceiling_dbtp=args.limit_true_peak)
 
 
 def build_denoiser(args, vocoder=None, device=None):
@@ -191,6 +225,7 @@ def run_tts(args) -> float:
     check_f0_smooth(args)
     build_loudness(args)
     build_denoiser(args)
+    build_limiter(args, SAMPLING_RATE if args.sampling_rate is None else int(args.sampling_rate))
     level = {0: logging.WARNING, 1: logging.INFO}.get(args.verbose, logging.DEBUG)
     logging.basicConfig(level=level, stream=sys.stdout, force=True, format="%(asctime)s %(levelname)s %(name)s:%(lineno)d  %(message)s")
     if not torch.cuda.is_available():
@@ -220,6 +255,7 @@ def run_tts(args) -> float:
     resampler = None
     if vocoder is not None and out_rate != SAMPLING_RATE:
         resampler = Resampler(device, SAMPLING_RATE, out_rate, quality=args.resample_quality)
+    limiter = build_limiter(args, out_rate, device)
 
     total_rtf, done = 0.0, 0
     bs = max(1, int(args.batch_size))
@@ -251,6 +287,8 @@ def run_tts(args) -> float:
                     outs = [loudness(outs[0][None].float())[0]]
                 if resampler is not None:
                     outs = [resampler(outs[0][None].float())[0][0]]
+                if limiter is not None:
+                    outs = [limiter(outs[0][None].float())[0]]
             else:                                       # one batched generator pass; every item equals its single-utterance result
                 audio = vocoder(mel.transpose(1, 2).contiguous(), mel_lens)
                 if denoiser is not None:                # ragged: every item is framed and reflected at its own ends
@@ -263,6 +301,10 @@ def run_tts(args) -> float:
                 else:                                   # ragged: every item is converted from its own samples only
                     audio, audio_lens = resampler(audio[:, 0].float(), mel_lens.to(audio.device) * 256)
                     outs = [audio[n, :int(audio_lens[n])] for n in range(len(chunk))]
+                if limiter is not None:                 # the last step, on the samples that are written; ragged like the others
+                    lens_out = torch.tensor([o.shape[0] for o in outs], device=audio.device)
+                    limited = limiter(torch.nn.utils.rnn.pad_sequence([o.float() for o in outs], batch_first=True), lens_out)
+                    outs = [limited[n, :o.shape[0]] for n, o in enumerate(outs)]
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - start
         seconds = sum(m.shape[0] for m in mels) * 256 / SAMPLING_RATE

@@ -1,7 +1,7 @@
 """`python -m efficient_tts_amd.bin.loudness` -- how loud every recording of a corpus is, and what normalising it would do, before training on it.
 
     python -m efficient_tts_amd.bin.loudness --filelist train.txt --wav_path wavs --outdir exp/loudness \\
-        [--target -23] [--peak_ceiling 0.99] [--batch_size 16]
+        [--target -23] [--peak_ceiling 0.99] [--batch_size 16] [--true_peak]
 
 Reads a training file list (`audiopath|...`, one recording per line; the file name is looked up under --wav_path, 16-bit mono wav files),
 runs the recordings through `efficient_tts_amd.loudness.LoudnessNormalizer` in batches -- the object that `normalize_loudness` in the
@@ -12,7 +12,9 @@ training recipe puts in front of the log-mel front-end, so --target and --peak_c
 
 one line per recording under a header line (lufs: the integrated loudness after ITU-R BS.1770, `-inf` for a recording without a 400 ms
 block over the absolute gate; gain_db: what reaching the target takes, after the ceiling; limited: 1 when the ceiling cut the gain back),
-and prints the spread.  Recordings of one batch must share one sampling rate.  There is no CPU mode.
+and prints the spread.  With --true_peak every line also gets `sample_peak_db` and `true_peak_dbtp`, the largest sample and the largest value
+of the 4x oversampled signal (`efficient_tts_amd.limiter.TruePeakMeter`, BS.1770 Annex 2) of the recording as it is, in dB re full scale,
+`-inf` for silence.  Recordings of one batch must share one sampling rate.  There is no CPU mode.
 """
 from __future__ import annotations
 
@@ -24,9 +26,15 @@ import sys
 import torch
 
 from efficient_tts_amd.bin._io import read_wav
+from efficient_tts_amd.limiter import TruePeakMeter
 from efficient_tts_amd.loudness import FLAG_CEILING, FLAG_NO_LOUDNESS, LoudnessNormalizer
 
 COLUMNS = ("id", "seconds", "lufs", "gain_db", "limited")
+PEAK_COLUMNS = ("sample_peak_db", "true_peak_dbtp")
+
+
+def _db(value: float) -> float:
+    return 20.0 * math.log10(value) if value > 0.0 else float("-inf")
 
 
 def get_parser() -> argparse.ArgumentParser:
@@ -37,6 +45,7 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--target", type=float, default=-23.0, help="the integrated loudness to reach, in LUFS (default -23)")
     p.add_argument("--peak_ceiling", type=float, default=0.99, help="no sample may exceed this after the gain (default 0.99; <= 0: no ceiling)")
     p.add_argument("--batch_size", type=int, default=16, help="recordings per call (default 16; every item is treated as if alone)")
+    p.add_argument("--true_peak", action="store_true", help="append sample_peak_db and true_peak_dbtp (4x oversampled) to every line")
     return p
 
 
@@ -56,8 +65,9 @@ def run_loudness(args):
     bs = max(1, int(args.batch_size))
     meters = {}                                 # one normaliser per sampling rate met
     measured = []
+    peaks = TruePeakMeter(device) if args.true_peak else None
     with open(os.path.join(args.outdir, "loudness.tsv"), "w") as handle:
-        handle.write("\t".join(COLUMNS) + "\n")
+        handle.write("\t".join(COLUMNS + (PEAK_COLUMNS if peaks is not None else ())) + "\n")
         for lo in range(0, len(names), bs):
             chunk = names[lo:lo + bs]
             wavs, rates = zip(*(read_wav(os.path.join(args.wav_path, os.path.basename(name))) for name in chunk))
@@ -70,13 +80,16 @@ def run_loudness(args):
             audio = torch.nn.utils.rnn.pad_sequence(list(wavs), batch_first=True).to(device)
             _, lufs, gains, flags, _ = meters[rate](audio, torch.tensor([w.shape[0] for w in wavs]), return_stats=True)
             lufs, gains, flags = lufs.tolist(), gains.tolist(), flags.tolist()
+            if peaks is not None:
+                tp, sp = (v.tolist() for v in peaks(audio, torch.tensor([w.shape[0] for w in wavs])))
             for i, name in enumerate(chunk):
                 utt = os.path.splitext(os.path.basename(name))[0]
                 scale = meters[rate].max_wav_value if wavs[i].dtype == torch.int16 else 1.0        # the gain of int16 PCM includes 1 / max_wav_value
                 gain_db = 20.0 * math.log10(gains[i] * scale)
                 if not flags[i] & FLAG_NO_LOUDNESS:
                     measured.append(lufs[i])
-                handle.write(f"{utt}\t{wavs[i].shape[0] / rate:.4f}\t{lufs[i]:.3f}\t{gain_db:.3f}\t{int(bool(flags[i] & FLAG_CEILING))}\n")
+                tail = f"\t{_db(sp[i]):.3f}\t{_db(tp[i]):.3f}" if peaks is not None else ""
+                handle.write(f"{utt}\t{wavs[i].shape[0] / rate:.4f}\t{lufs[i]:.3f}\t{gain_db:.3f}\t{int(bool(flags[i] & FLAG_CEILING))}{tail}\n")
     if measured:
         print(f"{len(names)} recordings: {min(measured):.2f} .. {max(measured):.2f} LUFS, mean {sum(measured) / len(measured):.2f}; "
               f"{len(names) - len(measured)} without a loudness")

@@ -233,6 +233,12 @@ _SIGS = {
     # a linear map of every frame's log power spectrum (waveform mel-cepstra) and the distance between frames paired one to one
     "efts_logspec_project": (i32, [vp, i32, f32, i64, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp]),
     "efts_frame_dist": (i32, [vp, i64, i64, vp, i32, vp, i64, i64, vp, i32, i32, vp, vp, i32, vp]),
+    # true-peak metering and the look-ahead peak limiter
+    "efts_limiter_workspace_bytes": (i64, [i32, i64]),
+    "efts_true_peak": (i32, [vp, i64, vp, C.POINTER(C.c_float), vp, vp, vp, i32, vp]),
+    "efts_true_peak_pcm16": (i32, [vp, i64, vp, C.POINTER(C.c_float), f32, vp, vp, vp, i32, vp]),
+    "efts_peak_limit": (i32, [vp, i64, vp, C.POINTER(C.c_float), f32, i32, i32, vp, i64, vp, vp, vp, vp, i32, vp]),
+    "efts_peak_limit_pcm16": (i32, [vp, i64, vp, C.POINTER(C.c_float), f32, f32, i32, i32, vp, i64, vp, vp, vp, vp, i32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -100,7 +100,9 @@ extern "C" {
  *        + efts_logspec_project, efts_frame_dist (waveform mel-cepstra and the distance between frames paired one to one): exports added,
  *          the revision stays by the same rule
  *        + efts_noise_profile, efts_noise_profile_workspace_bytes, efts_spectral_gate (a noise profile per recording and the spectral gate
- *          that uses it): exports added, the revision stays by the same rule */
+ *          that uses it): exports added, the revision stays by the same rule
+ *        + efts_true_peak, efts_true_peak_pcm16, efts_peak_limit, efts_peak_limit_pcm16, efts_limiter_workspace_bytes (true-peak metering
+ *          and the look-ahead peak limiter): exports added, the revision stays by the same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -1263,6 +1265,58 @@ int efts_noise_profile(const void* audio, int32_t pcm16, float pcm_scale, int64_
 int efts_spectral_gate(const void* audio, int32_t pcm16, float pcm_scale, int64_t ld, const int32_t* lengths, int32_t max_len, const float* window,
                        const float* profile, int64_t ld_profile, float strength, float floor, const int32_t* bypass, float* out, int64_t ld_out,
                        int32_t* frames, int32_t B, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * True-peak metering after ITU-R BS.1770 Annex 2 / EBU R 128 (4x oversampling) of a padded batch, and a look-ahead peak limiter that holds
+ * every item under a true-peak ceiling.  Samples fp32, or int16 PCM on the _pcm16 entries, taken as x = fl32((float) sample * pcm_scale)
+ * (pcm_scale = 1 / max_wav_value) at the load.  Item b is row b of in [B][ld_in] with len = lengths[b], clamped to 0 .. ld_in; x = 0 outside
+ * [0, len); nothing at or behind len is read.
+ *   interpolator: table, HOST memory, [4][25] fp32, read during the call: a 4-phase Kaiser-windowed sinc at the Nyquist cutoff with 12 zero
+ *               crossings per side and beta = 8.  With t = q / 4 - k for q = 0 .. 3 and k = -12 .. 12:
+ *               h[q][k + 12] = sinc(t) I0(8 sqrt(1 - (t / 12)^2)) / I0(8) for |t| < 12 and 0 otherwise, sinc(t) = sin(pi t) / (pi t),
+ *               sinc(0) = 1 and sinc of any other integer EXACTLY 0, built in float64 by the caller and rounded once to fp32.  Phase 0 is
+ *               therefore the identity to the bit (h[0][12] = 1, every other entry +0.0); a table whose phase 0 is anything else is refused.
+ *   oversampled : xo[i][q] = sum over k = -12 .. 12 of x[i + k] h[q][k + 12]: fp32, acc = fmaf(x[i + k], h[q][k + 12], acc) from +0.0 in
+ *               ascending k, for q = 1 .. 3; xo[i][0] = x[i].  p[i] = max over q of |xo[i][q]| (a maximum has no order).  As
+ *               p[i] >= |x[i]|, true peak >= sample peak holds exactly.
+ * efts_true_peak / efts_true_peak_pcm16:
+ *   true_peak[b] = max of p[i] and sample_peak[b] = max of |x[i]| over i = 0 .. len - 1, both fp32, both 0 for an empty item.
+ * efts_peak_limit / efts_peak_limit_pcm16, with the ceiling c > 0 by value, hold H and smooth S, 1 <= S <= H <= EFTS_LIMITER_MAX_HOLD:
+ *   needed gain: r[i] = c / p[i] (one fp32 division, rounded to nearest) if p[i] > c, otherwise 1; r[i] = 1 for i outside [0, len).
+ *   hold       : m[i] = min of r[j] over |j - i| <= H.
+ *   smoothing  : g[i] = min(r[i], s[i] / (float) (2 S + 1)), s[i] = the m[j] with |j - i| <= S added in fp32 from +0.0 in ascending j,
+ *               one fp32 division.  S <= H makes every m[j] of the mean <= r[i], so g <= r and |x[i] g[i]| <= c in real arithmetic; in fp32
+ *               the division and the product round once each: |out[i]| <= c (1 + 2^-23).
+ *   out[b * ld_out + i] = x[i] * g[i] for i < len and +0.0 for len <= i < ld_out.  Where every p <= c, every g is exactly 1 and the item
+ *               comes back bit for bit.
+ *   gain_min[b] (fp32) = min of g[i], limited[b] (int32) = the count of g[i] < 1, true_peak[b] (fp32) = max of p[i], all over i < len; an
+ *               empty item has 1, 0 and 0.
+ *   What bounds the TRUE peak of the output is how smooth g is: the sample peak is bounded as above, the signal between the samples of the
+ *   output only as far as g moves little over the interpolator's 25 taps.
+ * Two launches each, whatever the data.  A workgroup owns a chunk of EFTS_LIMITER_CHUNK samples, chunk origins at multiples of the chunk
+ * size from the item's start, stages it with its halo (12 samples per side; the limiter: 12 + H + S) and writes one partial (16 bytes) per
+ * chunk; p, r, m and g never leave the workgroup.  The second launch takes the maximum, the minimum and the integer sum of the partials per
+ * item.  No atomics, nothing read back, no launch geometry from device data: the calls can be captured.  An item gives the same bits alone,
+ * at any batch position, in any run and whatever lies behind its samples.
+ * workspace : device memory, 16-byte aligned, efts_limiter_workspace_bytes(B, max_len = ld_in) bytes: [B][ceil(ld_in / CHUNK)] partials.
+ *             Contents afterwards: unspecified.  The size entry returns 0 for arguments the calls would refuse.
+ * EFTS_ESHAPE, nothing launched: B outside 1 .. 65535, ld_in outside 1 .. 2^31 - 8193, ld_out below ld_in or above 2^31 - 8193, H or S
+ * outside 1 <= S <= H <= EFTS_LIMITER_MAX_HOLD.  EFTS_EINVAL: a null pointer, a pointer not aligned to its element (the workspace: to 16
+ * bytes), a table entry that is not finite or a phase 0 that is not the identity, a ceiling that is not a finite number > 0, pcm_scale not a
+ * positive number, out [B][ld_out] overlapping in (a chunk reads its neighbours' samples: the limiter does not work in place).
+ * ---------------------------------------------------------------------------------- */
+#define EFTS_LIMITER_CHUNK 2048
+#define EFTS_LIMITER_MAX_HOLD 128
+int64_t efts_limiter_workspace_bytes(int32_t B, int64_t max_len);
+int efts_true_peak(const float* in, int64_t ld_in, const int32_t* lengths, const float* table, float* true_peak, float* sample_peak, void* workspace,
+                   int32_t B, void* stream);
+int efts_true_peak_pcm16(const int16_t* in, int64_t ld_in, const int32_t* lengths, const float* table, float pcm_scale, float* true_peak,
+                         float* sample_peak, void* workspace, int32_t B, void* stream);
+int efts_peak_limit(const float* in, int64_t ld_in, const int32_t* lengths, const float* table, float ceiling, int32_t hold, int32_t smooth, float* out,
+                    int64_t ld_out, float* gain_min, int32_t* limited, float* true_peak, void* workspace, int32_t B, void* stream);
+int efts_peak_limit_pcm16(const int16_t* in, int64_t ld_in, const int32_t* lengths, const float* table, float pcm_scale, float ceiling, int32_t hold,
+                          int32_t smooth, float* out, int64_t ld_out, float* gain_min, int32_t* limited, float* true_peak, void* workspace, int32_t B,
+                          void* stream);
 
 #ifdef __cplusplus
 }
