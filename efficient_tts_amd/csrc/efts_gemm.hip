@@ -142,6 +142,9 @@ extern "C" int efts_gemm(const efts_gemm_args* a, void* stream) {
     const bool fp32 = a->split == EFTS_SPLIT_FP32;
     if (fp32 && tiling > EFTS_TILING_GENERIC)
         return efts_fail(EFTS_EINVAL, "efts_gemm: split 3 (fp32) runs on the generic tiling only (tiling %d requested)", tiling);
+    // train-mode dropout: EPI_DROP exists in the 128-column ring tiles and conv5_kernel only (AUTO keeps such a launch there: `no_narrow`)
+    if (k.drop_thresh && tiling > EFTS_TILING_WIDE)
+        return efts_fail(EFTS_EINVAL, "efts_gemm: dropout needs the generic or wide tiling (tiling %d requested)", tiling);
     // (0) short row spaces on request (never AUTO: the K dimension is split across the waves, so the summation order -- not the
     //     operand rounding -- differs from the ring kernels): 64 x 32 tiles, fragments straight from global memory
     if (tiling == EFTS_TILING_SMALLM) {
