@@ -33,7 +33,10 @@ HiFi-GAN V1 generator (efficient_tts_amd.vocoder).  Differences from the referen
     (efficient_tts_amd.limiter): a look-ahead limiter built for the OUTPUT rate, the last step in front of the 16-bit quantisation, behind
     `--sampling_rate`, so it sees the samples that are written.  Together with `--loudness` the normaliser runs without its own ceiling --
     the target is reached and the limiter takes the peaks -- and an explicit `--loudness_peak_ceiling` is refused.  Without the flag the
-    wav files are byte for byte what they were.
+    wav files are byte for byte what they were;
+  * `--use_ema` loads the averaged weights of the checkpoint (its "ema" entry: a run with `ema_decay` in its YAML writes one,
+    efficient_tts_amd.ema) instead of the raw ones; a checkpoint without that entry is refused at start-up.  Without the flag every byte
+    written is what it was.
 """
 from __future__ import annotations
 
@@ -103,6 +106,7 @@ def get_parser() -> argparse.ArgumentParser:
                    help="hold every utterance under this true-peak ceiling in dBTP, for example -1 (default: no limiter)")
     p.add_argument("--denoise", type=float, default=None,
                    help="subtract this many times the vocoder's bias spectrum from every frame's magnitudes, for example 0.01 (default: no denoiser)")
+    p.add_argument("--use_ema", action="store_true", help=USE_EMA_HELP)
     p.add_argument("--verbose", type=int, default=1)
     return p
 
@@ -122,8 +126,20 @@ def _read_list(path: str, phn2idx, with_paths: bool = False) -> List[Tuple[str, 
     return items
 
 
+USE_EMA_HELP = 'synthesise with the averaged weights of the checkpoint (its "ema" entry, written by a run with ema_decay) instead of the raw ones'
+
+
+def averaged_weights(state: dict, path: str = "the checkpoint") -> dict:
+    """--use_ema: the "model" entry of a checkpoint's "ema" entry; a checkpoint without one is refused"""
+    ema = state.get("ema")
+    if not isinstance(ema, dict) or "model" not in ema:
+        raise ValueError(f'--use_ema: {path} holds no "ema" entry: it was trained without `ema_decay` in its YAML (for example ema_decay: 0.999), '
+                         f"so there are no averaged weights to load")
+    return ema["model"]
+
+
 def load_acoustic_model(args, device):
-    """(config, phn2idx, model) of --checkpoint / --config / --precision: the model in eval mode, weight norm removed"""
+    """(config, phn2idx, model) of --checkpoint / --config / --precision [/ --use_ema]: the model in eval mode, weight norm removed"""
     config_path = args.config or os.path.join(os.path.dirname(args.checkpoint), "config.yml")
     with open(config_path) as handle:
         config = yaml.safe_load(handle)
@@ -134,7 +150,7 @@ def load_acoustic_model(args, device):
         phn2idx = {p.strip(): i for i, p in enumerate(handle)}
     model = getattr(models, config["model_name"])(precision=args.precision, **config["model_params"])
     state = torch.load(args.checkpoint, map_location="cpu")
-    model.load_state_dict(state["model"])
+    model.load_state_dict(averaged_weights(state, args.checkpoint) if getattr(args, "use_ema", False) else state["model"])
     model = model.to(device).eval()
     model.remove_weight_norm()
     return config, phn2idx, model

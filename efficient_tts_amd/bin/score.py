@@ -3,7 +3,7 @@
     python -m efficient_tts_amd.bin.score --checkpoint exp/efts/checkpoint-100000steps.pkl --test_fid_scp test.txt --outdir exp/efts/score \\
         [--config exp/efts/config.yml] [--batch_size 16] [--precision bf16x3] [--length_scale 1.0]
         [--f0 --vocoder griffinlim|hifigan [--vocoder_config c.json --vocoder_checkpoint g.pt] [--gl_iters 32] [--f0_min 60] [--f0_max 600] [--f0_threshold 0.15] [--f0_smooth]]
-        [--trim_silence [--trim_top_db 40]] [--normalize_peak 0.95] [--mcd_wave]
+        [--trim_silence [--trim_top_db 40]] [--normalize_peak 0.95] [--mcd_wave] [--use_ema]
 
 Reads the `wav_path|phonemes` list of `efficient_tts_amd.bin.inference` (16-bit wav files at the front-end's rate; a path that does not
 exist is looked up by its file name under dataset_params.wav_path).  Per batch, on the device: the recordings' log-mels (`LogMelFrontend`
@@ -29,6 +29,9 @@ warping path, behind `--trim_silence` / `--normalize_peak` where those are given
 ends with two more columns, mcd_wave_db and mcd_wave_path_len, the last line with the mean of the first (and `-`).  Without the flag nothing
 changes.
 
+`--use_ema` scores the averaged weights of the checkpoint (its "ema" entry: a run with `ema_decay` in its YAML writes one) instead of the
+raw ones; a checkpoint without that entry is refused at start-up.  Without the flag nothing changes.
+
 The numbers of the first column compare checkpoints of this project with each other (natural-log mels of this front-end); they are not
 comparable to MCDs computed from SPTK cepstra of waveforms.  The `--mcd_wave` column is the literature's definition by the periodogram route.
 """
@@ -42,7 +45,7 @@ import numpy as np
 import torch
 
 from efficient_tts_amd.bin._io import read_wav
-from efficient_tts_amd.bin.inference import SAMPLING_RATE, _read_list, build_vocoder, load_acoustic_model
+from efficient_tts_amd.bin.inference import SAMPLING_RATE, USE_EMA_HELP, _read_list, build_vocoder, load_acoustic_model
 from efficient_tts_amd.frontend import LogMelFrontend
 from efficient_tts_amd.pitch import PitchTracker, lag_range
 from efficient_tts_amd.mcep import WaveformMCD
@@ -74,6 +77,7 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--normalize_peak", type=float, default=None, help="bring every recording to this peak, in (0, 1], before it is scored against")
     p.add_argument("--mcd_wave", action="store_true",
                    help="also score mel-cepstral distortion between the vocoded synthesis and the recording (needs the --vocoder switches, as --f0 does)")
+    p.add_argument("--use_ema", action="store_true", help=USE_EMA_HELP.replace("synthesise", "score"))
     return p
 
 

@@ -30,6 +30,8 @@ from torch.utils.data.distributed import DistributedSampler
 import efficient_tts_amd as pkg
 from efficient_tts_amd import datasets, models, optimizers, schedulers, trainers
 from efficient_tts_amd.dist import DistributedEFTS
+from efficient_tts_amd.ema import ParamEMA
+from efficient_tts_amd.optim import FlatOptimizer
 from efficient_tts_amd.frontend import LogMelFrontend
 from efficient_tts_amd.resample import Resampler
 from efficient_tts_amd.denoise import SpectralGate
@@ -176,11 +178,38 @@ def build_loudness(config: Dict[str, Any], device=None) -> Optional[LoudnessNorm
                               max_wav_value=float(front.get("max_wav_value", 32768.0)))
 
 
+def build_ema(config: Dict[str, Any], optimizer=None) -> Optional[ParamEMA]:
+    """the ParamEMA that the recipe asks for, attached to `optimizer`; None without `ema_decay`.  `ema_decay: 0.999` keeps an exponential
+    moving average of the parameters beside the optimizer state, `ema_warmup` (default true) lets the decay ramp up as (1 + n) / (10 + n).
+    It needs one of the fused optimizers of the registry: together with any other optimizer the key is refused.  Without an optimizer
+    only the keys are checked."""
+    decay, warmup = config.get("ema_decay"), config.get("ema_warmup", True)
+    if decay is None:
+        if "ema_warmup" in config:
+            raise ValueError("ema_warmup: set without ema_decay")
+        return None
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 < float(decay) < 1.0:
+        raise ValueError(f"ema_decay must be a number in (0, 1), got {decay!r}")
+    if not isinstance(warmup, bool):
+        raise ValueError(f"ema_warmup must be true or false, got {warmup!r}")
+    if optimizer is None:
+        return None
+    if not isinstance(optimizer, FlatOptimizer):
+        raise ValueError(f"ema_decay needs one of the fused optimizers (optimizer_type Adam, AdamW or RAdam of efficient_tts_amd.optimizers), "
+                         f"whose parameters live in one flat buffer: optimizer_type {config.get('optimizer_type', 'Adam')!r} built a "
+                         f"{type(optimizer).__module__}.{type(optimizer).__name__}")
+    return ParamEMA(optimizer, decay=float(decay), warmup=warmup)
+
+
 def _build_trainer(config: Dict[str, Any], loaders, samplers, proc: _Process):
     device = proc.device
     net = getattr(models, config["model_name"])(**config["model_params"]).to(device)
     optimizer = getattr(optimizers, config.get("optimizer_type", "Adam"))(
         net, grad_norm=float(config.get("grad_norm", 1.0)), **config["optimizer_params"])
+    ema = build_ema(config, optimizer)
+    if ema is not None:
+        logging.info(f"exponential moving average of the parameters: decay {ema.decay}" + (", warming up as (1 + n) / (10 + n)" if ema.warmup else "")
+                     + "; checkpoints carry it as \"ema\", evaluations run on it")
     scheduler = None
     if config.get("scheduler_type"):
         scheduler = getattr(schedulers, config["scheduler_type"])(optimizer=optimizer, **(config.get("scheduler_params") or {}))
@@ -229,6 +258,7 @@ def main(argv=None) -> int:
     config = _load_config(args, proc)
     build_loudness(config)                     # a recipe that sets the level twice is refused here, before any data is read
     build_gate(config)                         # likewise a gate key that is out of range or stands without `denoise_corpus`
+    build_ema(config)                          # likewise an `ema_decay` outside (0, 1)
     loaders, samplers = _build_data(config, args, proc)
     trainer = _build_trainer(config, loaders, samplers, proc)
     if args.pretrain:

@@ -17,6 +17,10 @@
 // HBM-bound: 7 words per element (p, g, m, v read; p, m, v written), 9 with amsgrad.  16-byte accesses, 256-thread blocks, at most 2048
 // blocks that grid-stride (cdna_hip_programming.md Guideline 11 / 13); amsgrad and the algorithm are template parameters, so the 7-word
 // variants hold no load or store of vmax.  No atomics: two runs give the same bits.
+//
+// Beside them, the exponential moving average of the parameters (efts_ema_update): e = fmaf(w, p - e, e) over the same flat buffer, in the
+// same shape, 3 words per element (p, e read; e written), with its one per-update word w = 1 - decay from the host (efts_ema_hyper).  A
+// launch of its own, not a fourth template parameter of optim_kernel: see DESIGN.md "The parameter EMA stays a launch of its own".
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -75,6 +79,27 @@ __global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, const
                 p[j] = pp; m[j] = mm; v[j] = vv;
                 if (AMS) vmax[j] = vm;
             }
+        }
+    }
+}
+
+// e += w (p - e): d = fl(p - e), one fp32 subtraction, then e' = fl(w d + e), one fma.  The two ends mean what they say rather than what
+// the formula rounds to: w == 0 writes nothing, w == 1 stores p (fl(fl(p - e) + e) is not p where |p| is far below |e|).
+__device__ __forceinline__ float ema_apply(float e, float p, float w) { return w == 1.f ? p : fmaf(w, p - e, e); }
+
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ e, const float* __restrict__ p, long n, float w) {
+    if (w == 0.f) return;
+    for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (long)gridDim.x * 1024) {
+        if (i + 3 < n) {
+            const float4 pp = *(const float4*)(p + i);
+            float4 ee = *(const float4*)(e + i);
+            ee.x = ema_apply(ee.x, pp.x, w);
+            ee.y = ema_apply(ee.y, pp.y, w);
+            ee.z = ema_apply(ee.z, pp.z, w);
+            ee.w = ema_apply(ee.w, pp.w, w);
+            *(float4*)(e + i) = ee;
+        } else {
+            for (long j = i; j < n; ++j) e[j] = ema_apply(e[j], p[j], w);
         }
     }
 }
@@ -138,4 +163,27 @@ extern "C" int efts_optim_step(const efts_optim_args* a, void* stream) {
         default: optim_launch<EFTS_OPTIM_RADAM, false>(a, k, w4, stream); break;
     }
     return efts_check_launch("efts_optim_step");
+}
+
+// the per-update word of the parameter EMA, in double as Python floats, rounded to fp32 once
+extern "C" int efts_ema_hyper(double decay, int32_t warmup, int64_t updates, float* out1) {
+    if (!out1 || !(decay >= 0.0 && decay < 1.0) || updates < 0)
+        return efts_fail(EFTS_EINVAL, "efts_ema_hyper: out1 NULL, decay outside [0, 1) or updates < 0");
+    double d = decay;
+    if (warmup) {
+        const double ramp = (1.0 + (double)updates) / (10.0 + (double)updates);
+        if (ramp < d) d = ramp;
+    }
+    out1[0] = (float)(1.0 - d);
+    return EFTS_OK;
+}
+
+extern "C" int efts_ema_update(float* ema, const float* p, int64_t n, float one_minus_decay, void* stream) {
+    if (!ema || !p || n <= 0) return efts_fail(EFTS_EINVAL, "efts_ema_update: null pointer or n <= 0");
+    if (!(one_minus_decay >= 0.f && one_minus_decay <= 1.f))
+        return efts_fail(EFTS_EINVAL, "efts_ema_update: one_minus_decay must lie in [0, 1] (got %g)", (double)one_minus_decay);
+    if (((uintptr_t)ema | (uintptr_t)p) & 15) return efts_fail(EFTS_EALIGN, "efts_ema_update: buffers must be 16-byte aligned");
+    const long blocks = ((long)n + 1023) / 1024;
+    hipLaunchKernelGGL(ema_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, ST, ema, p, (long)n, one_minus_decay);
+    return efts_check_launch("efts_ema_update");
 }

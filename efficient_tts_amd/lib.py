@@ -178,6 +178,9 @@ _SIGS = {
     "efts_store_words": (i32, [vp, C.POINTER(C.c_uint32), i32, vp]),
     "efts_optim_step": (i32, [C.POINTER(OptimArgs), vp]),
     "efts_optim_hyper": (i32, [i32, C.c_double, C.c_double, C.c_double, C.c_double, i32, C.POINTER(f32)]),
+    # exponential moving average of the parameters
+    "efts_ema_hyper": (i32, [C.c_double, i32, i64, C.POINTER(f32)]),
+    "efts_ema_update": (i32, [vp, vp, i64, f32, vp]),
     # log-mel front-end
     "efts_frame_pack": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
     "efts_logmel": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

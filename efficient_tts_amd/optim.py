@@ -105,6 +105,7 @@ class FlatOptimizer(torch.optim.Optimizer):
         self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self.sumsq_ws = torch.zeros(L.load().efts_sumsq_workspace_bytes() // 4, dtype=torch.float32, device=dev)
         self.t = 0
+        self.ema = None                         # an attached ema.ParamEMA: updated behind every step's launch
         super().__init__([p for _, p in eng.layout], defaults)
 
     @torch.no_grad()
@@ -112,6 +113,8 @@ class FlatOptimizer(torch.optim.Optimizer):
         """clip (global norm of grad_scale * flat grads) + update, all on the device."""
         self.t += 1
         self.launch(grad_scale)
+        if self.ema is not None:
+            self.ema.update()
         self.model.planes.invalidate()          # parameters changed in place through the flat view
 
     def hyper_words(self, step: int):

@@ -16,7 +16,10 @@ a replay contains forward, backward, the RCCL exchanges overlapped with the back
 one launch per step instead of ~190.
 
 Not captured (the step then runs eagerly, same results): conv / prenet Dropout (dropout_rate > 0: their seeds are by-value launch
-arguments), optimizers other than the fused ones (optim.FlatOptimizer)."""
+arguments), optimizers other than the fused ones (optim.FlatOptimizer).
+
+An attached parameter average (ema.ParamEMA, `optimizer.ema`) is not part of the graph either: its one launch is issued eagerly behind
+every replay, on the same stream, with its word by value -- the call `optimizer.step()` makes in the eager loop."""
 from __future__ import annotations
 
 import logging
@@ -151,6 +154,8 @@ class GraphedStep:
                         s_.copy_(t, non_blocking=True)
             self._refresh(eng)
         ent["graph"].replay()
+        if self.opt.ema is not None:             # the parameter average: an eager by-value launch behind the replay, on the same stream,
+            self.opt.ema.update()               # the call opt.step() makes in the eager loop -- the captured graph does not hold it
         self.replays += 1
         # what the eager loop's Python does around its launches
         m.dropout_calls = int(m.dropout_calls) + 1

@@ -22,6 +22,11 @@ Everything inside is organised for this engine rather than copied from the refer
     `bucket_frames` / `bucket_phones` pad shapes up to multiples so the engine's per-shape workspaces are re-used across ragged batches;
   * `eval_mcd: true` (YAML, default false) adds the free-running pass to every evaluation and publishes its mel-cepstral distortion
     against the dev recordings (efficient_tts_amd.score) -- the only figure here that sees the duration predictor;
+  * `ema_decay: 0.999` (YAML; `ema_warmup`, default true) keeps an exponential moving average of the parameters beside the optimizer
+    state (efficient_tts_amd.ema.ParamEMA, attached to the optimizer as `optimizer.ema`).  A checkpoint then carries one more key, "ema"
+    ({"decay", "warmup", "updates", "model"}: "model" loads as any "model" entry does), and every evaluation runs on the AVERAGED weights:
+    `eval/*` describe what will be synthesised, under the same names.  Training goes on with the raw weights, bit for bit.  Without the
+    key, nothing here differs;
   * tensorboardX / tqdm are used when importable, silently skipped otherwise.
 """
 from __future__ import annotations
@@ -96,6 +101,11 @@ class EfficientTTSTrainer:
         """the bare model (DistributedEFTS / DDP keep it under .module)"""
         return self.model.module if hasattr(self.model, "module") else self.model
 
+    @property
+    def ema(self):
+        """the ParamEMA attached to the optimizer (`ema_decay` in the YAML), or None"""
+        return getattr(self.optimizer, "ema", None)
+
     def _due(self, key: str) -> bool:
         every = int(self.config[key])
         return every > 0 and self.steps % every == 0
@@ -158,6 +168,8 @@ class EfficientTTSTrainer:
         }
         if self.scheduler is not None:
             payload["scheduler"] = self.scheduler.state_dict()
+        if self.ema is not None:               # (only then: without `ema_decay` the key set is the reference's five)
+            payload["ema"] = self.ema.state_dict()
         folder = os.path.dirname(checkpoint_path)
         if folder:
             os.makedirs(folder, exist_ok=True)
@@ -169,6 +181,8 @@ class EfficientTTSTrainer:
         net.load_state_dict(payload["model"])
         net.planes.invalidate()                # operand planes are re-packed from the new parameters
         if load_only_params:
+            if self.ema is not None:           # the average starts from the parameters the run starts from
+                self.ema.reset()
             return
         self.steps, self.epochs = payload["steps"], payload["epochs"]
         net.dropout_calls = int(self.steps)       # position in the counter-based dropout mask sequence: one draw per training step,
@@ -176,6 +190,13 @@ class EfficientTTSTrainer:
         self.optimizer.load_state_dict(payload["optimizer"])
         if self.scheduler is not None and "scheduler" in payload:
             self.scheduler.load_state_dict(payload["scheduler"])
+        if self.ema is not None:               # (an "ema" entry that this run did not ask for is ignored)
+            if "ema" in payload:
+                self.ema.load_state_dict(payload["ema"])
+            else:
+                log.warning(f"{checkpoint_path} holds no \"ema\" entry (it was written without ema_decay): the average starts over from the "
+                            f"loaded parameters, updates = 0")
+                self.ema.reset()
 
     # ------------------------------------------------------------------------------------------ one optimisation step
     def _graphed_step(self):
@@ -250,6 +271,15 @@ class EfficientTTSTrainer:
     # ------------------------------------------------------------------------------------------ evaluation
     @torch.no_grad()
     def _evaluate(self) -> None:
+        """the dev set under the published `eval/*` names.  With an attached ParamEMA the pass runs on the averaged weights
+        (`ema.applied()`): the numbers describe the weights that will be synthesised; behind it the model holds the raw weights
+        again, bit for bit, and training goes on with them."""
+        if self.ema is None:
+            return self._evaluate_current()
+        with self.ema.applied():
+            return self._evaluate_current()
+
+    def _evaluate_current(self) -> None:
         net = self._net
         net.eval()
         batches = 0

@@ -102,7 +102,9 @@ extern "C" {
  *        + efts_noise_profile, efts_noise_profile_workspace_bytes, efts_spectral_gate (a noise profile per recording and the spectral gate
  *          that uses it): exports added, the revision stays by the same rule
  *        + efts_true_peak, efts_true_peak_pcm16, efts_peak_limit, efts_peak_limit_pcm16, efts_limiter_workspace_bytes (true-peak metering
- *          and the look-ahead peak limiter): exports added, the revision stays by the same rule */
+ *          and the look-ahead peak limiter): exports added, the revision stays by the same rule
+ *        + efts_ema_update, efts_ema_hyper (exponential moving average of the parameters): exports added, the revision stays by the same
+ *          rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -712,6 +714,24 @@ typedef struct efts_optim_args {
 } efts_optim_args;
 int efts_optim_step(const efts_optim_args* a, void* stream);
 int efts_optim_hyper(int32_t algo, double lr, double beta1, double beta2, double weight_decay, int32_t step, float* out4 /* host */);
+
+/* The exponential moving average of the parameters, kept beside the optimizer state on the same flat fp32 buffer, as a launch of its own
+ * behind the optimizer's (efts_optim_args, efts_optim_step and efts_adam_amsgrad are untouched by it):
+ *   efts_ema_update : ema[i] = fmaf(w, p[i] - ema[i], ema[i]) for i < n, w = one_minus_decay.  In roundings: d = fl(p - e), one fp32
+ *                     subtraction; e' = fl(w d + e), one fused multiply-add, rounded once.  So |e' - exact| <= 2^-24 |p - e| + 2^-24 |e'|
+ *                     <= 2^-23 (|p| + |e|) for w in (0, 1).  The two ends are defined by what they mean, not by the formula: w == 0 writes
+ *                     nothing (ema stays bit for bit, a -0 included), w == 1 stores p itself (fl(fl(p - e) + e) is not p where |p| is far
+ *                     below |e|: the subtraction has already lost p).  3 words per element (p, ema read; ema written), 16-byte
+ *                     accesses, 256-thread blocks, at most 2048 blocks that grid-stride, a scalar tail for n % 4; no atomics: two runs give
+ *                     the same bits.  w travels by value, the launch can be captured.
+ *   efts_ema_hyper  : the ONE definition of the per-update word, on the host in double, rounded to fp32 once:
+ *                       d = warmup ? min(decay, (1 + updates) / (10 + updates)) : decay;    out1[0] = (float)(1.0 - d)
+ *                     `updates`: the updates already made (0 for the first).  With warm-up the first update takes 9/10 of p, and the ramp
+ *                     crosses decay = 0.999 between updates 8990 and 8991.
+ * EFTS_EINVAL: NULL ema / p / out1, n <= 0, one_minus_decay outside [0, 1] (NaN included), decay outside [0, 1), updates < 0.
+ * EFTS_EALIGN: ema or p not 16-byte aligned. */
+int efts_ema_hyper(double decay, int32_t warmup, int64_t updates, float* out1 /* host */);
+int efts_ema_update(float* ema, const float* p, int64_t n, float one_minus_decay, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Log-mel front-end: the data format right before the path.
