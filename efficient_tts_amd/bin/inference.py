@@ -56,6 +56,7 @@ from efficient_tts_amd import models
 from efficient_tts_amd.denoise import BiasDenoiser
 from efficient_tts_amd.griffinlim import GriffinLimVocoder
 from efficient_tts_amd.limiter import PeakLimiter
+from efficient_tts_amd.iir import build_chain
 from efficient_tts_amd.loudness import LoudnessNormalizer
 from efficient_tts_amd.pitch import PitchTracker
 from efficient_tts_amd.resample import QUALITIES, Resampler
@@ -106,6 +107,11 @@ def get_parser() -> argparse.ArgumentParser:
                    help="hold every utterance under this true-peak ceiling in dBTP, for example -1 (default: no limiter)")
     p.add_argument("--denoise", type=float, default=None,
                    help="subtract this many times the vocoder's bias spectrum from every frame's magnitudes, for example 0.01 (default: no denoiser)")
+    p.add_argument("--highpass_hz", type=float, default=None,
+                   help="run a Butterworth high-pass at this cutoff over the vocoder's output, for example 60 (default: no filter)")
+    p.add_argument("--highpass_order", type=int, default=None, help="--highpass_hz: 2 (default) or 4")
+    p.add_argument("--deemphasis", type=float, default=None,
+                   help="undo a pre-emphasis of this coefficient on the vocoder's output, for example 0.97, behind --highpass_hz (default: none)")
     p.add_argument("--use_ema", action="store_true", help=USE_EMA_HELP)
     p.add_argument("--verbose", type=int, default=1)
     return p
@@ -223,6 +229,17 @@ def build_limiter(args, out_rate: int = SAMPLING_RATE, device=None):
     return PeakLimiter(device, int(out_rate), ceiling_dbtp=args.limit_true_peak)
 
 
+def build_filter(args, device=None):
+    """the IIRFilter for the vocoder's output -- the high-pass of --highpass_hz, then the de-emphasis of --deemphasis -- or None without
+    either (checked on the host, before anything is loaded)"""
+    hz, order, coef = getattr(args, "highpass_hz", None), getattr(args, "highpass_order", None), getattr(args, "deemphasis", None)
+    if hz is None and order is None and coef is None:
+        return None
+    if args.no_vocoder:
+        raise ValueError("--highpass_hz and --deemphasis filter the vocoder's output: they cannot be combined with --no_vocoder")
+    return build_chain(device, SAMPLING_RATE, hz, order, coef)
+
+
 def build_denoiser(args, vocoder=None, device=None):
     """the BiasDenoiser for the vocoder's output, its bias measured from `vocoder`, or None without --denoise.  Without a vocoder: only the
     checks (on the host, before anything is loaded)"""
@@ -241,6 +258,7 @@ def run_tts(args) -> float:
     check_f0_smooth(args)
     build_loudness(args)
     build_denoiser(args)
+    build_filter(args)
     build_limiter(args, SAMPLING_RATE if args.sampling_rate is None else int(args.sampling_rate))
     level = {0: logging.WARNING, 1: logging.INFO}.get(args.verbose, logging.DEBUG)
     logging.basicConfig(level=level, stream=sys.stdout, force=True, format="%(asctime)s %(levelname)s %(name)s:%(lineno)d  %(message)s")
@@ -267,6 +285,7 @@ def run_tts(args) -> float:
     vocoder = None if args.no_vocoder else build_vocoder(args, device)
     tracker = PitchTracker(device, sampling_rate=SAMPLING_RATE, n_fft=1024, hop_size=256, smooth=args.f0_smooth) if args.write_f0 else None
     denoiser = build_denoiser(args, vocoder, device)
+    iir = build_filter(args, device)
     loudness = build_loudness(args, device)
     resampler = None
     if vocoder is not None and out_rate != SAMPLING_RATE:
@@ -299,6 +318,8 @@ def run_tts(args) -> float:
                 outs = raw = [vocoder(mels[0].t()[None].contiguous())[0, 0]]
                 if denoiser is not None:
                     outs = raw = [denoiser(outs[0][None].float())[0]]
+                if iir is not None:
+                    outs = [iir(outs[0][None].float())[0]]
                 if loudness is not None:
                     outs = [loudness(outs[0][None].float())[0]]
                 if resampler is not None:
@@ -310,6 +331,8 @@ def run_tts(args) -> float:
                 if denoiser is not None:                # ragged: every item is framed and reflected at its own ends
                     audio = denoiser(audio[:, 0].float(), mel_lens.to(audio.device) * 256)[:, None]
                 raw = [audio[n, 0, :int(mel_lens[n]) * 256] for n in range(len(chunk))]
+                if iir is not None:                     # ragged: every item is filtered from zero state over its own samples
+                    audio = iir(audio[:, 0].float(), mel_lens.to(audio.device) * 256)[:, None]
                 if loudness is not None:                # ragged as well: every item is measured over its own samples only
                     audio = loudness(audio[:, 0].float(), mel_lens.to(audio.device) * 256)[:, None]
                 if resampler is None:

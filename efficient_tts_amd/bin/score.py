@@ -47,6 +47,7 @@ import torch
 from efficient_tts_amd.bin._io import read_wav
 from efficient_tts_amd.bin.inference import SAMPLING_RATE, USE_EMA_HELP, _read_list, build_vocoder, load_acoustic_model
 from efficient_tts_amd.frontend import LogMelFrontend
+from efficient_tts_amd.iir import build_chain
 from efficient_tts_amd.pitch import PitchTracker, lag_range
 from efficient_tts_amd.mcep import WaveformMCD
 from efficient_tts_amd.score import F0Error, MelCepstralDistortion
@@ -75,6 +76,9 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--trim_silence", action="store_true", help="cut the silence at both ends of every recording before it is scored against")
     p.add_argument("--trim_top_db", type=float, default=40.0, help="--trim_silence: a frame this far under the loudest one is silence (default 40)")
     p.add_argument("--normalize_peak", type=float, default=None, help="bring every recording to this peak, in (0, 1], before it is scored against")
+    p.add_argument("--highpass_hz", type=float, default=None,
+                   help="run a Butterworth high-pass at this cutoff over every recording before it is scored against, as `highpass_hz` in a recipe does")
+    p.add_argument("--highpass_order", type=int, default=None, help="--highpass_hz: 2 (default) or 4")
     p.add_argument("--mcd_wave", action="store_true",
                    help="also score mel-cepstral distortion between the vocoded synthesis and the recording (needs the --vocoder switches, as --f0 does)")
     p.add_argument("--use_ema", action="store_true", help=USE_EMA_HELP.replace("synthesise", "score"))
@@ -86,6 +90,11 @@ def build_trimmer(args, hop: int, max_wav_value: float, device=None):
     if not args.trim_silence and args.normalize_peak is None:
         return None
     return SilenceTrimmer(device, hop_size=hop, top_db=args.trim_top_db, peak=args.normalize_peak, max_wav_value=max_wav_value, trim=args.trim_silence)
+
+
+def build_highpass(args, rate: int = SAMPLING_RATE, max_wav_value: float = 32768.0, device=None):
+    """the IIRFilter for the recordings, in front of the trimmer as in training, or None without --highpass_hz (checked on the host)"""
+    return build_chain(device, rate, getattr(args, "highpass_hz", None), getattr(args, "highpass_order", None), max_wav_value=max_wav_value)
 
 
 def check_f0_args(args, front=None) -> None:
@@ -141,6 +150,7 @@ def format_lines(rows, extra=None, cuts=None, wave=None):
 
 def run_score(args) -> float:
     check_f0_args(args)
+    build_highpass(args)
     if not torch.cuda.is_available():
         raise RuntimeError("no MI355X (gfx950) device visible: efficient_tts_amd has no CPU path")
     if not args.length_scale > 0:
@@ -153,6 +163,7 @@ def run_score(args) -> float:
     rate = int(front.get("sampling_rate", 22050))
     scorer = MelCepstralDistortion(device, num_mels=frontend.n_mels)
     check_f0_args(args, front)
+    highpass = build_highpass(args, rate, frontend.max_wav_value, device)
     trimmer = build_trimmer(args, frontend.hop, frontend.max_wav_value, device)
     if args.f0 or args.mcd_wave:
         vocoder = build_vocoder(args, device)
@@ -173,6 +184,8 @@ def run_score(args) -> float:
         ids = torch.nn.utils.rnn.pad_sequence([t for _, t, _ in chunk], batch_first=True)
         wav_len = torch.tensor([w.shape[0] for w in wavs])
         with torch.no_grad():
+            if highpass is not None:               # DC and rumble out of the recordings, from zero state over each one's own samples: fp32 on the device
+                audio = highpass(audio.to(device), wav_len)
             if trimmer is not None:                # the recordings as a run with these options trains on them: fp32 on the device, new lengths
                 audio, wav_len, cut_start, _ = trimmer(audio.to(device), wav_len, return_bounds=True)
                 cuts.extend(zip(cut_start.tolist(), wav_len.tolist()))

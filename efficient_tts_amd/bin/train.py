@@ -35,6 +35,7 @@ from efficient_tts_amd.optim import FlatOptimizer
 from efficient_tts_amd.frontend import LogMelFrontend
 from efficient_tts_amd.resample import Resampler
 from efficient_tts_amd.denoise import SpectralGate
+from efficient_tts_amd.iir import IIRFilter, highpass_sos, preemphasis_sos
 from efficient_tts_amd.loudness import LoudnessNormalizer
 from efficient_tts_amd.trim import SilenceTrimmer
 
@@ -178,6 +179,37 @@ def build_loudness(config: Dict[str, Any], device=None) -> Optional[LoudnessNorm
                               max_wav_value=float(front.get("max_wav_value", 32768.0)))
 
 
+def _front_rate(config: Dict[str, Any]) -> int:
+    front = config.get("frontend_params") or {}
+    data = config.get("dataset_params") or {}
+    return int(front.get("sampling_rate", data.get("sampling_rate", 22050)))
+
+
+def build_highpass(config: Dict[str, Any], device=None) -> Optional[IIRFilter]:
+    """the IIRFilter that `highpass_hz` asks for, at the front-end's rate; None without the key.  `highpass_hz: 60` runs a Butterworth
+    high-pass of `highpass_order` 2 (the default) or 4 over every recording, behind the resampler and in front of the spectral gate, so that
+    the noise profile, the trim threshold and the loudness see no DC offset and no rumble.  A cutoff outside (0, rate / 2), another order, or
+    an order without a cutoff is refused."""
+    cutoff = config.get("highpass_hz")
+    if cutoff is None:
+        if "highpass_order" in config:
+            raise ValueError("highpass_order: set without highpass_hz")
+        return None
+    front = config.get("frontend_params") or {}
+    return IIRFilter(device, highpass_sos(_front_rate(config), cutoff, config.get("highpass_order", 2)),
+                     max_wav_value=float(front.get("max_wav_value", 32768.0)))
+
+
+def build_preemphasis(config: Dict[str, Any], device=None) -> Optional[IIRFilter]:
+    """the IIRFilter that `preemphasis` asks for; None without the key.  `preemphasis: 0.97` runs y[n] = x[n] - 0.97 x[n - 1] over every
+    recording as the last step in front of the log-mel front-end.  A coefficient outside [0, 1) is refused."""
+    coef = config.get("preemphasis")
+    if coef is None:
+        return None
+    front = config.get("frontend_params") or {}
+    return IIRFilter(device, preemphasis_sos(coef), max_wav_value=float(front.get("max_wav_value", 32768.0)))
+
+
 def build_ema(config: Dict[str, Any], optimizer=None) -> Optional[ParamEMA]:
     """the ParamEMA that the recipe asks for, attached to `optimizer`; None without `ema_decay`.  `ema_decay: 0.999` keeps an exponential
     moving average of the parameters beside the optimizer state, `ema_warmup` (default true) lets the decay ramp up as (1 + n) / (10 + n).
@@ -228,6 +260,9 @@ def _build_trainer(config: Dict[str, Any], loaders, samplers, proc: _Process):
         trainer.resampler = Resampler(device, int(source_rate), front_rate, quality=config.get("resample_quality", "best"),
                                       max_wav_value=float(front.get("max_wav_value", 32768.0)))
         logging.info(f"resampling {source_rate} -> {front_rate} Hz on the device ({trainer.resampler.quality})")
+    trainer.highpass = build_highpass(config, device)
+    if trainer.highpass is not None:
+        logging.info(f"on the device, per recording: Butterworth high-pass of order {2 * trainer.highpass.sections} at {config['highpass_hz']} Hz")
     trainer.gate = build_gate(config, device)
     if trainer.gate is not None:
         g = trainer.gate
@@ -243,6 +278,9 @@ def _build_trainer(config: Dict[str, Any], loaders, samplers, proc: _Process):
         n = trainer.loudness
         logging.info(f"on the device, per recording: integrated loudness set to {n.target_lufs} LUFS at {n.sampling_rate} Hz"
                      + (f", peak held under {n.peak_ceiling}" if n.peak_ceiling is not None else ""))
+    trainer.preemphasis = build_preemphasis(config, device)
+    if trainer.preemphasis is not None:
+        logging.info(f"on the device, per recording: pre-emphasis {config['preemphasis']} in front of the log-mel front-end")
     return trainer
 
 
@@ -259,6 +297,8 @@ def main(argv=None) -> int:
     build_loudness(config)                     # a recipe that sets the level twice is refused here, before any data is read
     build_gate(config)                         # likewise a gate key that is out of range or stands without `denoise_corpus`
     build_ema(config)                          # likewise an `ema_decay` outside (0, 1)
+    build_highpass(config)                     # likewise a `highpass_hz` outside (0, rate / 2) or an order that is not 2 or 4
+    build_preemphasis(config)                  # likewise a `preemphasis` outside [0, 1)
     loaders, samplers = _build_data(config, args, proc)
     trainer = _build_trainer(config, loaders, samplers, proc)
     if args.pretrain:

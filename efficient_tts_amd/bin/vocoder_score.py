@@ -56,6 +56,9 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--wav_path", type=str, default=None, help="directory searched, by file name, for a wav path that does not exist")
     p.add_argument("--denoise", type=float, default=None,
                    help="denoise the copy-synthesis before scoring: subtract this many times the vocoder's bias spectrum, for example 0.01 (default: off)")
+    p.add_argument("--highpass_hz", type=float, default=None,
+                   help="run a Butterworth high-pass at this cutoff over every recording before anything else, as `highpass_hz` in a recipe does")
+    p.add_argument("--highpass_order", type=int, default=None, help="--highpass_hz: 2 (default) or 4")
     p.add_argument("--stoi", action="store_true", help="also score STOI and ESTOI of the copy-synthesis against the recording (columns stoi, estoi, stoi_kept_frames)")
     p.add_argument("--mcd", action="store_true", help="also score the mel-cepstral distortion of the copy-synthesis against the recording, frame by frame (columns mcd_db, mcd_frames)")
     return p
@@ -70,6 +73,13 @@ def check_args(args) -> None:
         raise ValueError("--batch_size must be >= 1")
     if args.denoise is not None and not (args.denoise > 0 and np.isfinite(args.denoise)):
         raise ValueError("--denoise must be a finite strength > 0 (leave the flag out for no denoiser)")
+    build_highpass(args)
+
+
+def build_highpass(args, max_wav_value: float = 32768.0, device=None):
+    """the IIRFilter for the recordings, or None without --highpass_hz (checked on the host)"""
+    from efficient_tts_amd.iir import build_chain
+    return build_chain(device, SAMPLING_RATE, getattr(args, "highpass_hz", None), getattr(args, "highpass_order", None), max_wav_value=max_wav_value)
 
 
 STOI_COLUMNS = ("stoi", "estoi", "stoi_kept_frames")
@@ -151,6 +161,7 @@ def run_score(args):
     if args.denoise is not None:
         from efficient_tts_amd.denoise import BiasDenoiser
         denoiser = BiasDenoiser.from_vocoder(vocoder, device, strength=args.denoise)
+    highpass = build_highpass(args, frontend.max_wav_value, device)
     scorer = MultiResolutionSTFTDistance(device, max_wav_value=frontend.max_wav_value)
     intelligibility = None
     if args.stoi:
@@ -168,6 +179,8 @@ def run_score(args):
         audio = torch.nn.utils.rnn.pad_sequence(wavs, batch_first=True).to(device)
         wav_len = torch.tensor([w.shape[0] for w in wavs], device=device)
         with torch.no_grad():
+            if highpass is not None:                         # the recordings as a run with `highpass_hz` trains on them: fp32 from here on
+                audio = highpass(audio, wav_len)
             mel, mel_len = frontend(audio, wav_len)
             syn = vocoder(mel.transpose(1, 2).contiguous(), mel_len)[:, 0].float()
             if denoiser is not None:

@@ -242,6 +242,10 @@ _SIGS = {
     "efts_true_peak_pcm16": (i32, [vp, i64, vp, C.POINTER(C.c_float), f32, vp, vp, vp, i32, vp]),
     "efts_peak_limit": (i32, [vp, i64, vp, C.POINTER(C.c_float), f32, i32, i32, vp, i64, vp, vp, vp, vp, i32, vp]),
     "efts_peak_limit_pcm16": (i32, [vp, i64, vp, C.POINTER(C.c_float), f32, f32, i32, i32, vp, i64, vp, vp, vp, vp, i32, vp]),
+    # a cascade of second-order sections with exact state carry
+    "efts_iir_workspace_bytes": (i64, [i32, i64]),
+    "efts_iir": (i32, [vp, i64, vp, C.POINTER(C.c_double), i32, vp, vp, i64, vp, i32, vp]),
+    "efts_iir_pcm16": (i32, [vp, i64, vp, C.POINTER(C.c_double), i32, vp, f32, vp, i64, vp, i32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -85,6 +85,8 @@ class EfficientTTSTrainer:
         self.device = device
         self.frontend = None                   # optional LogMelFrontend (set by efficient_tts_amd.bin.train)
         self.resampler = None                  # optional Resampler in front of it: corpus rate -> front-end rate (set by efficient_tts_amd.bin.train)
+        self.highpass = None                   # optional IIRFilter behind the resampler: `highpass_hz` (set by efficient_tts_amd.bin.train)
+        self.preemphasis = None                # optional IIRFilter, the last step in front of the front-end: `preemphasis` (set by efficient_tts_amd.bin.train)
         self.gate = None                       # optional SpectralGate behind the resampler: `denoise_corpus` (set by efficient_tts_amd.bin.train)
         self.trimmer = None                    # optional SilenceTrimmer between the two: `trim_silence` / `normalize_peak` (set by efficient_tts_amd.bin.train)
         self.loudness = None                   # optional LoudnessNormalizer behind the trimmer: `normalize_loudness` (set by efficient_tts_amd.bin.train)
@@ -133,6 +135,10 @@ class EfficientTTSTrainer:
         if self.resampler is not None:
             # the padded int16 batch at the corpus' rate -> a padded fp32 batch at the front-end's rate, with the converted lengths
             third, third_lengths = self.resampler(third, third_lengths)
+        if self.highpass is not None:
+            # DC and rumble taken out, item by item from zero state: a padded fp32 batch, the lengths stay; in front of the gate, the trimmer and
+            # the loudness, so that the profile, the threshold and the level see the filtered signal
+            third = self.highpass(third, third_lengths)
         if self.gate is not None:
             # the stationary floor under the speech taken out, item by item, with the profile of the item's own quiet frames: a padded fp32 batch,
             # the lengths stay; in front of the trimmer, so that its threshold sees the cleaned signal
@@ -143,6 +149,9 @@ class EfficientTTSTrainer:
         if self.loudness is not None:
             # every item brought to one integrated loudness (BS.1770) over its own samples: a padded fp32 batch, the lengths stay
             third = self.loudness(third, third_lengths)
+        if self.preemphasis is not None:
+            # y[n] = x[n] - c x[n - 1] on what the steps above left: a padded fp32 batch, the lengths stay
+            third = self.preemphasis(third, third_lengths)
         n_frames = int(self.frontend.frames_of(third_lengths).max())
         # default buckets: ragged LJSpeech batches otherwise bring a new (B, T1, T2) almost every step, and every new shape
         # allocates and zero-fills a multi-GB activation workspace (4 are cached); 0 in the YAML turns the padding off

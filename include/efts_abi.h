@@ -104,7 +104,9 @@ extern "C" {
  *        + efts_true_peak, efts_true_peak_pcm16, efts_peak_limit, efts_peak_limit_pcm16, efts_limiter_workspace_bytes (true-peak metering
  *          and the look-ahead peak limiter): exports added, the revision stays by the same rule
  *        + efts_ema_update, efts_ema_hyper (exponential moving average of the parameters): exports added, the revision stays by the same
- *          rule */
+ *          rule
+ *        + efts_iir, efts_iir_pcm16, efts_iir_workspace_bytes (a cascade of second-order sections with exact state carry): exports added,
+ *          the revision stays by the same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -1337,6 +1339,55 @@ int efts_peak_limit(const float* in, int64_t ld_in, const int32_t* lengths, cons
 int efts_peak_limit_pcm16(const int16_t* in, int64_t ld_in, const int32_t* lengths, const float* table, float pcm_scale, float ceiling, int32_t hold,
                           int32_t smooth, float* out, int64_t ld_out, float* gain_min, int32_t* limited, float* true_peak, void* workspace, int32_t B,
                           void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * IIR filtering of a padded batch: a cascade of K second-order sections, 1 <= K <= EFTS_IIR_MAX_SECTIONS, in fp64 with the exact filter
+ * state carried from segment to segment.  Samples fp32, or int16 PCM on the _pcm16 entry, taken as x = fl32((float) sample * pcm_scale)
+ * (pcm_scale = 1 / max_wav_value) at the load and widened to fp64 without rounding.  Item b is row b of in [B][ld_in] with len =
+ * lengths[b], clamped to 0 .. ld_in; nothing at or behind len is read.
+ *   filter     : sos, HOST memory, double [K][5], read during the call: (b0, b1, b2, a1, a2) of every section, a0 = 1.  A first-order section
+ *                has b2 = a2 = 0.  Every section must satisfy |a2| < 1 and |a1| < 1 + a2 (both poles inside the unit circle).
+ *   recurrence : the sections run in order on every sample, section q on the y of section q - 1, each in transposed direct form II with
+ *                every product folded into an fma:
+ *                    y  = fma(b0, x, s1)
+ *                    s1 = fma(-a1, y, fma(b1, x, s2))
+ *                    s2 = fma(-a2, y, b2 * x)
+ *                Every item starts from s1 = s2 = 0 in every section at its sample 0.  In real arithmetic this is y = b0 x + s1,
+ *                s1 = b1 x - a1 y + s2, s2 = b2 x - a2 y.
+ *   output     : out[b * ld_out + i] = fl32(y of the last section at sample i) for i < len, one rounding, and +0.0 for len <= i < ld_out.
+ * State carry.  S = (s1, s2 of section 0, s1, s2 of section 1, ...) is the cascade's state, N = 2 K doubles.  The segments of an item are
+ * its samples [s L, (s + 1) L) with L = EFTS_IIR_SEGMENT, counted from its sample 0.  Over a segment S_end = M S_start + Z: Z is the end
+ * state of the run from zero state over the segment's samples, M the N x N matrix whose column i is the end state after L steps with x = 0
+ * from the unit state e_i.
+ *   powers     : DEVICE memory, double [6][N][N] row-major, read by launch B: M^(2^k) for k = 0 .. 5, entry [k] being the end states after
+ *                2^k L zero-input steps of the recurrence above, built by the caller in float64 (numpy has no fma: it runs the real-arithmetic
+ *                form, rounding every operation).
+ *   launch A   : one thread per segment s with (s + 1) L < len (a full segment that has a successor) computes Z_s by the recurrence.
+ *   launch B   : one wave per item takes the segments 64 at a time, lane l on segment c + l of the chunk that begins at segment c, and keeps
+ *                P, the end state of its segment.  With C the state at the chunk's start (0 for the first chunk):
+ *                    P_l = Z_(c + l), or 0 where launch A wrote none;
+ *                    lane 0: P_0[i] = the chain acc = P_0[i], acc = fma(M[i][j], C[j], acc) for j = 0 .. N - 1 ascending;
+ *                    for k = 0 .. 5 in turn, every lane l >= 2^k at once from the values before the step:
+ *                        P_l[i] = the chain acc = P_l[i], acc = fma(M^(2^k)[i][j], P_(l - 2^k)[j], acc) for j ascending;
+ *                    the start state of segment c + l is P_(l - 1), and C for lane 0; the next chunk's C is P_63.
+ *   launch C   : one thread per segment runs the recurrence from its start state over its samples and writes the output.
+ * The result differs from the sample-by-sample run from sample 0 only by the fp64 rounding of this reassociation.  Three launches, whatever
+ * the data: no atomics, nothing read back, no launch geometry from device data, so the calls can be captured.  The segment grid is per item,
+ * so an item gives the same bits alone, at any batch position, in any run and whatever lies behind its samples.
+ * workspace : device memory, 16-byte aligned, efts_iir_workspace_bytes(B, max_len = ld_in) bytes: [B][ceil(ld_in / L)] slots of 8 doubles.
+ *             Contents afterwards: unspecified.  The size entry returns 0 for arguments the calls would refuse.
+ * EFTS_ESHAPE, nothing launched: B outside 1 .. 65535, ld_in outside 1 .. 2^31 - 8193, ld_out below ld_in or above 2^31 - 8193, sections
+ * outside 1 .. EFTS_IIR_MAX_SECTIONS.  EFTS_EINVAL: a null pointer, a pointer not aligned to its element (the workspace: to 16 bytes), a
+ * coefficient that is not finite, a section with a pole on or outside the unit circle, pcm_scale not a positive number,
+ * out [B][ld_out] overlapping in (the input is read twice: the filter does not work in place).
+ * ---------------------------------------------------------------------------------- */
+#define EFTS_IIR_SEGMENT 256
+#define EFTS_IIR_MAX_SECTIONS 4
+int64_t efts_iir_workspace_bytes(int32_t B, int64_t max_len);
+int efts_iir(const float* in, int64_t ld_in, const int32_t* lengths, const double* sos, int32_t sections, const double* powers, float* out,
+             int64_t ld_out, void* workspace, int32_t B, void* stream);
+int efts_iir_pcm16(const int16_t* in, int64_t ld_in, const int32_t* lengths, const double* sos, int32_t sections, const double* powers,
+                   float pcm_scale, float* out, int64_t ld_out, void* workspace, int32_t B, void* stream);
 
 #ifdef __cplusplus
 }
