@@ -3,7 +3,7 @@
     python -m efficient_tts_amd.bin.score --checkpoint exp/efts/checkpoint-100000steps.pkl --test_fid_scp test.txt --outdir exp/efts/score \\
         [--config exp/efts/config.yml] [--batch_size 16] [--precision bf16x3] [--length_scale 1.0]
         [--f0 --vocoder griffinlim|hifigan [--vocoder_config c.json --vocoder_checkpoint g.pt] [--gl_iters 32] [--f0_min 60] [--f0_max 600] [--f0_threshold 0.15] [--f0_smooth]]
-        [--trim_silence [--trim_top_db 40]] [--normalize_peak 0.95] [--mcd_wave] [--use_ema]
+        [--trim_silence [--trim_top_db 40]] [--normalize_peak 0.95] [--max_pause_ms 300 [--pause_top_db 40]] [--mcd_wave] [--use_ema]
 
 Reads the `wav_path|phonemes` list of `efficient_tts_amd.bin.inference` (16-bit wav files at the front-end's rate; a path that does not
 exist is looked up by its file name under dataset_params.wav_path).  Per batch, on the device: the recordings' log-mels (`LogMelFrontend`
@@ -22,6 +22,10 @@ instead of YIN's frame-by-frame rule, whose octave errors of 1200 cents each oth
 (`efficient_tts_amd.trim.SilenceTrimmer` on the front-end's hop), before their log-mel and F0: the synthesis of a model trained on trimmed
 recordings carries no silence at its ends, and the recordings it is scored against should not either.  mcd.tsv then ends every line with two
 more columns, ref_trim_start and ref_trim_len (samples), and "-" in them on the line of the means.  Without the flags nothing changes.
+
+`--max_pause_ms MS` (with `--pause_top_db`) cuts the pauses inside the RECORDINGS that are longer than MS down to it, as `max_pause_ms` in a
+recipe does (`efficient_tts_amd.pauses.PauseShortener` at the front-end's rate and hop), behind `--trim_silence` and before their log-mel and F0.
+It adds no column.  Without the flag nothing changes.
 
 `--mcd_wave` adds the number that papers report: the synthesis is vocoded (the same `--vocoder` switches, required as for `--f0`) and
 `efficient_tts_amd.mcep.WaveformMCD` scores it against the recording -- order-24 all-pass-warped mel-cepstra of the two waveforms along their own
@@ -50,6 +54,7 @@ from efficient_tts_amd.frontend import LogMelFrontend
 from efficient_tts_amd.iir import build_chain
 from efficient_tts_amd.pitch import PitchTracker, lag_range
 from efficient_tts_amd.mcep import WaveformMCD
+from efficient_tts_amd.pauses import PauseShortener
 from efficient_tts_amd.score import F0Error, MelCepstralDistortion
 from efficient_tts_amd.trim import SilenceTrimmer
 
@@ -76,6 +81,9 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--trim_silence", action="store_true", help="cut the silence at both ends of every recording before it is scored against")
     p.add_argument("--trim_top_db", type=float, default=40.0, help="--trim_silence: a frame this far under the loudest one is silence (default 40)")
     p.add_argument("--normalize_peak", type=float, default=None, help="bring every recording to this peak, in (0, 1], before it is scored against")
+    p.add_argument("--max_pause_ms", type=float, default=None,
+                   help="cut every pause inside a recording that is longer than this down to it before it is scored against, as `max_pause_ms` in a recipe does")
+    p.add_argument("--pause_top_db", type=float, default=40.0, help="--max_pause_ms: a frame this far under the loudest one is quiet (default 40)")
     p.add_argument("--highpass_hz", type=float, default=None,
                    help="run a Butterworth high-pass at this cutoff over every recording before it is scored against, as `highpass_hz` in a recipe does")
     p.add_argument("--highpass_order", type=int, default=None, help="--highpass_hz: 2 (default) or 4")
@@ -90,6 +98,13 @@ def build_trimmer(args, hop: int, max_wav_value: float, device=None):
     if not args.trim_silence and args.normalize_peak is None:
         return None
     return SilenceTrimmer(device, hop_size=hop, top_db=args.trim_top_db, peak=args.normalize_peak, max_wav_value=max_wav_value, trim=args.trim_silence)
+
+
+def build_pauses(args, rate: int, hop: int, max_wav_value: float, device=None):
+    """the PauseShortener for the recordings, behind the trimmer as in training, or None without --max_pause_ms (checked on the host)"""
+    if getattr(args, "max_pause_ms", None) is None:
+        return None
+    return PauseShortener(device, rate, max_pause_ms=args.max_pause_ms, hop_size=hop, top_db=args.pause_top_db, max_wav_value=max_wav_value)
 
 
 def build_highpass(args, rate: int = SAMPLING_RATE, max_wav_value: float = 32768.0, device=None):
@@ -151,6 +166,7 @@ def format_lines(rows, extra=None, cuts=None, wave=None):
 def run_score(args) -> float:
     check_f0_args(args)
     build_highpass(args)
+    build_pauses(args, SAMPLING_RATE, 256, 32768.0)   # a --max_pause_ms <= 0 is refused here, before anything is loaded
     if not torch.cuda.is_available():
         raise RuntimeError("no MI355X (gfx950) device visible: efficient_tts_amd has no CPU path")
     if not args.length_scale > 0:
@@ -165,6 +181,7 @@ def run_score(args) -> float:
     check_f0_args(args, front)
     highpass = build_highpass(args, rate, frontend.max_wav_value, device)
     trimmer = build_trimmer(args, frontend.hop, frontend.max_wav_value, device)
+    pauses = build_pauses(args, rate, frontend.hop, frontend.max_wav_value, device)
     if args.f0 or args.mcd_wave:
         vocoder = build_vocoder(args, device)
     if args.mcd_wave:
@@ -189,6 +206,8 @@ def run_score(args) -> float:
             if trimmer is not None:                # the recordings as a run with these options trains on them: fp32 on the device, new lengths
                 audio, wav_len, cut_start, _ = trimmer(audio.to(device), wav_len, return_bounds=True)
                 cuts.extend(zip(cut_start.tolist(), wav_len.tolist()))
+            if pauses is not None:                 # the long pauses inside the recordings cut down, as a run with `max_pause_ms` trains on them
+                audio, wav_len = pauses(audio.to(device), wav_len)
             rec, rec_len = frontend(audio, wav_len)
             syn, syn_len = model.inference_batch(ids.to(device), torch.tensor([len(t) for _, t, _ in chunk], device=device),
                                                  length_scale=args.length_scale)[:2]

@@ -37,6 +37,7 @@ from efficient_tts_amd.resample import Resampler
 from efficient_tts_amd.denoise import SpectralGate
 from efficient_tts_amd.iir import IIRFilter, highpass_sos, preemphasis_sos
 from efficient_tts_amd.loudness import LoudnessNormalizer
+from efficient_tts_amd.pauses import PauseShortener
 from efficient_tts_amd.trim import SilenceTrimmer
 
 # (flags, kwargs) of the reference command line, kept as data so the parser and the docs cannot drift apart
@@ -136,6 +137,28 @@ def build_trimmer(config: Dict[str, Any], device=None) -> Optional[SilenceTrimme
     return SilenceTrimmer(device, frame_length=int(config.get("trim_frame_length", 1024)), hop_size=int(front.get("hop_size", 256)),
                           top_db=float(config.get("trim_top_db", 40.0)), keep_frames=int(config.get("trim_keep_frames", 2)),
                           peak=None if peak is None else float(peak), max_wav_value=float(front.get("max_wav_value", 32768.0)), trim=trim)
+
+
+_PAUSE_KEYS = ("pause_top_db", "pause_frame_length", "pause_fade")
+
+
+def build_pauses(config: Dict[str, Any], device=None) -> Optional[PauseShortener]:
+    """the PauseShortener that the recipe asks for, at the front-end's rate and hop; None without `max_pause_ms`.  `max_pause_ms: 300` cuts
+    every pause inside a recording that is longer than that down to it, behind the trimmer and in front of the level; `pause_top_db`
+    (default 40.0) under the loudest frame is quiet, `pause_frame_length` (default 1024) is the energy frame and `pause_fade` (default 64)
+    the samples of the linear fade into a joint.  A value <= 0, or one of the other keys without `max_pause_ms`, is refused."""
+    limit = config.get("max_pause_ms")
+    if limit is None:
+        stray = [k for k in _PAUSE_KEYS if k in config]
+        if stray:
+            raise ValueError(f"{', '.join(stray)}: set without max_pause_ms")
+        return None
+    if isinstance(limit, bool) or not isinstance(limit, (int, float)) or not float(limit) > 0.0:
+        raise ValueError(f"max_pause_ms must be a number > 0, got {limit!r}")
+    front = config.get("frontend_params") or {}
+    return PauseShortener(device, _front_rate(config), max_pause_ms=float(limit), frame_length=config.get("pause_frame_length", 1024),
+                          hop_size=int(front.get("hop_size", 256)), top_db=float(config.get("pause_top_db", 40.0)),
+                          fade=config.get("pause_fade", 64), max_wav_value=float(front.get("max_wav_value", 32768.0)))
 
 
 _GATE_KEYS = ("denoise_strength", "denoise_floor", "denoise_top_db", "denoise_min_frames")
@@ -273,6 +296,11 @@ def _build_trainer(config: Dict[str, Any], loaders, samplers, proc: _Process):
         t = trainer.trimmer
         logging.info(f"on the device, per recording: " + (f"silence trimmed at {t.top_db} dB under the loudest frame, {t.keep_frames} frames kept" if t.trim
                                                            else "no trimming") + (f", peak set to {t.peak}" if t.peak is not None else ""))
+    trainer.pauses = build_pauses(config, device)
+    if trainer.pauses is not None:
+        q = trainer.pauses
+        logging.info(f"on the device, per recording: pauses over {q.max_pause_ms} ms ({q.chunks} hops, {q.top_db} dB under the loudest frame) cut "
+                     f"down to that, {q.fade} samples of fade into the joint")
     trainer.loudness = build_loudness(config, device)
     if trainer.loudness is not None:
         n = trainer.loudness
@@ -299,6 +327,7 @@ def main(argv=None) -> int:
     build_ema(config)                          # likewise an `ema_decay` outside (0, 1)
     build_highpass(config)                     # likewise a `highpass_hz` outside (0, rate / 2) or an order that is not 2 or 4
     build_preemphasis(config)                  # likewise a `preemphasis` outside [0, 1)
+    build_pauses(config)                       # likewise a `max_pause_ms` <= 0 or a pause key that stands without it
     loaders, samplers = _build_data(config, args, proc)
     trainer = _build_trainer(config, loaders, samplers, proc)
     if args.pretrain:

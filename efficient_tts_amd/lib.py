@@ -215,6 +215,10 @@ _SIGS = {
     "efts_trim_workspace_bytes": (i64, [i32, i64, i32, i32]),
     "efts_trim": (i32, [vp, i64, vp, i32, i32, C.c_double, i32, f32, vp, i64, vp, vp, vp, vp, i32, vp]),
     "efts_trim_pcm16": (i32, [vp, i64, vp, i32, i32, C.c_double, i32, f32, f32, vp, i64, vp, vp, vp, vp, i32, vp]),
+    # shortening the long pauses inside a recording
+    "efts_pauses_workspace_bytes": (i64, [i32, i64, i32, i32]),
+    "efts_pauses": (i32, [vp, i64, vp, i32, i32, C.c_double, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, i32, vp]),
+    "efts_pauses_pcm16": (i32, [vp, i64, vp, i32, i32, C.c_double, i32, i32, vp, f32, vp, i64, vp, vp, vp, vp, vp, i32, vp]),
     # STFT magnitudes and the STFT distance at one resolution
     "efts_stft_mag": (i32, [vp, i32, f32, i64, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "efts_stft_dist_workspace_bytes": (i64, [i32, i32, i32, i32]),

@@ -17,7 +17,7 @@ Everything inside is organised for this engine rather than copied from the refer
   * with `EftsAdam` the gradient clip is part of the fused optimizer kernel; with `DistributedEFTS` the
     bucketed RCCL all-reduce launched during backward is joined right before the optimizer step;
   * an optional `frontend` (efficient_tts_amd.frontend.LogMelFrontend) turns waveform batches into
-    log-mels on the GPU, behind an optional `resampler`, an optional `trimmer` (efficient_tts_amd.trim.SilenceTrimmer) and an optional
+    log-mels on the GPU, behind an optional `resampler`, an optional `trimmer` (efficient_tts_amd.trim.SilenceTrimmer), optional `pauses` (efficient_tts_amd.pauses.PauseShortener) and an optional
     `loudness` (efficient_tts_amd.loudness.LoudnessNormalizer);
     `bucket_frames` / `bucket_phones` pad shapes up to multiples so the engine's per-shape workspaces are re-used across ragged batches;
   * `eval_mcd: true` (YAML, default false) adds the free-running pass to every evaluation and publishes its mel-cepstral distortion
@@ -89,6 +89,7 @@ class EfficientTTSTrainer:
         self.preemphasis = None                # optional IIRFilter, the last step in front of the front-end: `preemphasis` (set by efficient_tts_amd.bin.train)
         self.gate = None                       # optional SpectralGate behind the resampler: `denoise_corpus` (set by efficient_tts_amd.bin.train)
         self.trimmer = None                    # optional SilenceTrimmer between the two: `trim_silence` / `normalize_peak` (set by efficient_tts_amd.bin.train)
+        self.pauses = None                     # optional PauseShortener behind the trimmer: `max_pause_ms` (set by efficient_tts_amd.bin.train)
         self.loudness = None                   # optional LoudnessNormalizer behind the trimmer: `normalize_loudness` (set by efficient_tts_amd.bin.train)
         self.finish_train = False
         self._tb = _TBWriter(config["outdir"]) if _TBWriter is not None else None
@@ -146,6 +147,10 @@ class EfficientTTSTrainer:
         if self.trimmer is not None:
             # the quiet ends cut off and / or the level set, item by item: a padded fp32 batch with the new lengths, so the frame count below shrinks
             third, third_lengths = self.trimmer(third, third_lengths)
+        if self.pauses is not None:
+            # the long pauses inside every item cut down to `max_pause_ms`: a padded fp32 batch with the new lengths; in front of the level, which
+            # is then set on what will be trained on
+            third, third_lengths = self.pauses(third, third_lengths)
         if self.loudness is not None:
             # every item brought to one integrated loudness (BS.1770) over its own samples: a padded fp32 batch, the lengths stay
             third = self.loudness(third, third_lengths)

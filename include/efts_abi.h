@@ -106,7 +106,9 @@ extern "C" {
  *        + efts_ema_update, efts_ema_hyper (exponential moving average of the parameters): exports added, the revision stays by the same
  *          rule
  *        + efts_iir, efts_iir_pcm16, efts_iir_workspace_bytes (a cascade of second-order sections with exact state carry): exports added,
- *          the revision stays by the same rule */
+ *          the revision stays by the same rule
+ *        + efts_pauses, efts_pauses_pcm16, efts_pauses_workspace_bytes (shortening the long pauses inside a recording): exports added, the
+ *          revision stays by the same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -1022,6 +1024,55 @@ int efts_trim(const float* in, int64_t ld_in, const int32_t* lengths, int32_t W,
               int64_t ld_out, int32_t* new_len, int32_t* start, float* gain, void* workspace, int32_t B, void* stream);
 int efts_trim_pcm16(const int16_t* in, int64_t ld_in, const int32_t* lengths, int32_t W, int32_t H, double r, int32_t keep_frames, float peak,
                     float pcm_scale, float* out, int64_t ld_out, int32_t* new_len, int32_t* start, float* gain, void* workspace, int32_t B, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Shortening the long pauses INSIDE the items of a padded batch: every run of quiet hop chunks between two sound frames that is longer than
+ * M chunks is cut down to M chunks, and what is kept is moved together, with a linear fade into the joint.
+ * Parameters: W, H, pad = (W - H) / 2 and r = 10^(top_db / 10) > 1 as for efts_trim; M >= 1, the longest pause in chunks that is kept whole
+ * (the caller computes M = max(1, round(max_pause_ms * sampling_rate / (1000 H))) and passes it by value); the fade length 0 <= F <= H and
+ * the fade table w[0 .. F), w_k = (k + 0.5) / F computed in double and rounded once to fp32 by the caller; on the int16 entry pcm_scale
+ * (1 / max_wav_value).  For item b with len = lengths[b] (clamped to 0 .. ld_in) samples x, x = 0 outside [0, len):
+ *   frames    : T, the frame energies E_t, E_max and the SOUND rule, (double) E_t * r > (double) E_max, are those of efts_trim above, word for
+ *               word: int16 energies are exact 64-bit integers, fp32 energies are summed in the one order stated there.
+ *   chunks    : chunk c is samples c H .. c H + H - 1 (the last one ends at len); it is QUIET iff frame c is not sound.  t_first / t_last are
+ *               the first / last sound frame.  No sound frame: the item comes back as it is (int16: scaled), removed = 0, pauses = 0.
+ *   pauses    : a PAUSE is a maximal run of quiet chunks [c0, c1) with t_first < c0 and c1 <= t_last.  The quiet chunks in front of t_first
+ *               and behind t_last are no pauses and stay where they are (efts_trim cuts those).  Every pause lies between two sound
+ *               chunks, so every chunk of it is a whole chunk.
+ *   plan      : a pause of n = c1 - c0 <= M chunks is kept whole.  A pause of n > M chunks keeps its first head = (M + 1) / 2 and its last
+ *               tail = M / 2 chunks (integer division) and loses the n - M chunks between them: with a = (c0 + head) H and
+ *               b = (c1 - tail) H, samples [a, b) are removed.  removed = the sum of (n - M) H over these pauses (a multiple of H),
+ *               pauses = their number, new_len = len - removed.
+ *   chunk_src : the kept chunks in ascending order: chunk_src[j] is the source chunk of output chunk j, for j < T - removed / H, and -1 for
+ *               every j behind, up to T_max = ceil(ld_in / H).  It maps positions in the shortened signal back onto the recording.
+ *   samples   : out[j H + k] = (float) x[chunk_src[j] H + k] for j H + k < new_len: the bits of the sample (int16: one correctly rounded
+ *               fp32 multiply, (float) sample * pcm_scale), except on the last F samples in front of a joint: there, for k = 0 .. F - 1,
+ *               the output sample at the position of x[a - F + k] is fmaf(w_k, x[b - F + k] - x[a - F + k], x[a - F + k]) -- one correctly
+ *               rounded fp32 subtraction and one fused multiply-add, every x the fp32 value (int16: (float) sample * pcm_scale).  Both
+ *               operand ranges lie inside the pause (F <= H and head >= 1 on the left, one removed chunk on the right), and the output runs
+ *               continuously into x[b].  F = 0 is a plain cut.  Exactly 0.0f for new_len <= i < ld_out.
+ *   new_len, removed, pauses (int32 [B]) and chunk_src (int32 [B][T_max]) are written by the kernels.
+ * No sample at or beyond len and no other row is read or influences anything; an item gives the same bits alone, at any batch position and
+ * in any run (no atomics).  lengths[b] == 0 is legal: zeros, new_len 0.
+ * workspace : device memory, 16-byte aligned, of the size that the workspace-size entry returns for (B, max_len = ld_in, H, pcm16 = 0 for
+ *             the fp32 entry and 1 for the int16 entry): the frame energies [B][T_max] (uint64 or fp32) and two int32 [B][T_max] arrays of the
+ *             plan.  Contents afterwards: unspecified.  The size entry returns 0 for a non-positive argument.
+ * Three launches on the caller's stream: the energies (efts_trim's launch without the chunk peaks), the plan (one workgroup per item, which
+ * walks the T chunks in tiles of EFTS_PAUSES_TILE and carries its scans from tile to tile: an item of any length below 2^31 samples), and the
+ * compacting copy over (item, output chunk), 16 bytes per access where both rows are 16-byte aligned and the hop is a multiple of the
+ * samples in 16 bytes.  No host synchronisation, no allocation, no launch geometry from device data.
+ * EFTS_ESHAPE, nothing launched: B outside 1 .. 65535, ld_in < 1, ld_out < ld_in, either near 2^31, W other than 512, 1024, 2048, H outside
+ * 1 .. W or W - H odd, M outside 1 .. 2^30, F outside 0 .. H.  EFTS_EINVAL: null pointer (the fade table only with F > 0), a pointer not
+ * aligned to its element (the workspace: to 16 bytes), r <= 1.
+ * ---------------------------------------------------------------------------------- */
+#define EFTS_PAUSES_TILE 256
+int64_t efts_pauses_workspace_bytes(int32_t B, int64_t max_len, int32_t H, int32_t pcm16);
+int efts_pauses(const float* in, int64_t ld_in, const int32_t* lengths, int32_t W, int32_t H, double r, int32_t M, int32_t F, const float* fade,
+                float* out, int64_t ld_out, int32_t* new_len, int32_t* removed, int32_t* pauses, int32_t* chunk_src, void* workspace, int32_t B,
+                void* stream);
+int efts_pauses_pcm16(const int16_t* in, int64_t ld_in, const int32_t* lengths, int32_t W, int32_t H, double r, int32_t M, int32_t F,
+                      const float* fade, float pcm_scale, float* out, int64_t ld_out, int32_t* new_len, int32_t* removed, int32_t* pauses,
+                      int32_t* chunk_src, void* workspace, int32_t B, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * STFT magnitudes and the STFT distance between two signals at one resolution (N, H, W): FFT size N (256, 512, 1024 or 2048), hop
