@@ -105,6 +105,13 @@ class WgradItem(C.Structure):
                 ("bias_part", vp), ("dbias", vp), ("nparts", i32), ("reserved", i32)]
 
 
+class ResBlock2Args(C.Structure):
+    """mirror of `struct efts_resblock2_args` (include/efts_abi.h)"""
+    _fields_ = [("x", vp), ("ldx", i64), ("p0", vp), ("ldp", i64), ("w0", vp), ("w1", vp), ("ldw", i64), ("w_tap_stride", i64),
+                ("bias0", vp), ("bias1", vp), ("rowmask", vp), ("out", vp), ("ldo", i64),
+                ("split", i32), ("m", i32), ("c", i32), ("k", i32), ("d0", i32), ("d1", i32), ("slope", f32), ("reserved", i32)]
+
+
 WGRAD_MAX_ITEMS = 8
 
 OPTIM_ADAM, OPTIM_ADAMW, OPTIM_RADAM = 0, 1, 2      # EFTS_OPTIM_*
@@ -250,6 +257,8 @@ _SIGS = {
     "efts_iir_workspace_bytes": (i64, [i32, i64]),
     "efts_iir": (i32, [vp, i64, vp, C.POINTER(C.c_double), i32, vp, vp, i64, vp, i32, vp]),
     "efts_iir_pcm16": (i32, [vp, i64, vp, C.POINTER(C.c_double), i32, vp, f32, vp, i64, vp, i32, vp]),
+    # one HiFi-GAN ResBlock2 (two dilated convolutions, the intermediate in LDS)
+    "efts_resblock2": (i32, [C.POINTER(ResBlock2Args), vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -16,6 +16,12 @@ Every Conv1d / ConvTranspose1d is one `efts_gemm` launch on channel-last rows (o
     space of the next stage (a pointer offset of u/2 rows);
   * the multi-receptive-field mean and the LeakyReLU of the next layer's input: `efts_mean_act_rows`;
   * conv_post + tanh: the kernel's tanh epilogue.
+`resblock: "2"` (ResBlock2, hifigan_model.py:71-93; the V3 configuration): a block is two turns x <- x + conv_{k,d}(leaky(x)), d =
+dilation[0], dilation[1].  Two ways to run one, chosen per block by `fused_resblock2`: ONE `efts_resblock2` launch
+(csrc/efts_resblock2.hip: the intermediate and its operand plane stay in LDS; c <= 128, (k - 1) / 2 * (d0 + d1) <= 64 rows), or two
+`efts_gemm` launches ((k - 1) * d <= 64 rows each).  V3's third block (k = 7, d = 12: a 72-row window) runs on the fused launch only.
+The measured default composes where it can (tools/micro/vocoder_rb2_timing.py); what neither can run is refused in the constructor.
+`resblock: "1"` generators issue exactly the launches they issued before.
 Batches: the B utterances share one row space per stage, item b at rows b * P .. b * P + T_b * up with a pitch of
 P = (T + gap) * up rows.  `gap` spare mel frames (`gap_frames`) come from the configuration: at the first upsampled
 stage they are gap * upsample_rates[0] zero rows, and that must be no less than the largest halo of a residual
@@ -30,6 +36,7 @@ There is no CPU path.
 from __future__ import annotations
 
 import contextlib
+import ctypes
 from typing import Dict, List, Optional
 
 import torch
@@ -47,6 +54,9 @@ _MIN_GAP_FRAMES = 4    # spare mel frames between the items of a batch, at least
 _MAX_RES_KERNELS = 3   # efts_mean_act_rows adds up to three streams
 _GEMM_TAPS = (1, 3, 5, 7, 9, 11)       # what efts_gemm takes as `taps`
 _GEMM_MAX_SPAN = 64    # efts_gemm: (taps - 1) * dilation rows of window at the most
+_RB2_TAPS = (3, 5, 7, 9, 11)           # what efts_resblock2 takes as `k`
+_RB2_MAX_C = 128       # efts_resblock2: channels at the most
+_RB2_MAX_HALO = _GUARD  # efts_resblock2: (k - 1) / 2 * (d0 + d1) rows at the most
 
 
 def _cfg(h, key, default=None):
@@ -60,8 +70,20 @@ def gap_frames(upsample_rates, res_kernels, res_dilations) -> int:
     return max(_MIN_GAP_FRAMES, -(-halo // upsample_rates[0]))
 
 
-def _refusal(rates, kernels, res_kernels, res_dilations, c0, num_mels) -> Optional[str]:
+def _rb2_fusable(c: int, k: int, ds) -> bool:
+    """one efts_resblock2 launch can run this ResBlock2"""
+    return c <= _RB2_MAX_C and k in _RB2_TAPS and (k - 1) // 2 * (ds[0] + ds[1]) <= _RB2_MAX_HALO
+
+
+def _rb2_composable(k: int, ds) -> bool:
+    """two efts_gemm launches can run this ResBlock2"""
+    return k in _GEMM_TAPS and all((k - 1) * d <= _GEMM_MAX_SPAN for d in ds)
+
+
+def _refusal(rates, kernels, res_kernels, res_dilations, c0, num_mels, resblock: str = "1") -> Optional[str]:
     """why the launches of `_run` cannot compute this configuration (None: they can)"""
+    if resblock not in ("1", "2"):
+        return f"resblock {resblock!r}: the reference has ResBlock1 ('1') and ResBlock2 ('2')"
     if not rates or len(rates) != len(kernels):
         return "upsample_rates and upsample_kernel_sizes must be non-empty lists of one length"
     for u, k in zip(rates, kernels):
@@ -77,9 +99,21 @@ def _refusal(rates, kernels, res_kernels, res_dilations, c0, num_mels) -> Option
             return f"residual kernel size {k}: efts_gemm takes {', '.join(map(str, _GEMM_TAPS))} taps"
         if not ds:
             return "an empty dilation list (a residual block without convolutions) is not implemented"
+        if resblock == "2" and len(ds) != 2:
+            return (f"resblock '2' with {len(ds)} dilations for kernel size {k}: the reference's ResBlock2 uses exactly dilation[0] and "
+                    "dilation[1] (a list of three is a ResBlock1 configuration)")
         for d in ds:
-            if d < 1 or (k - 1) * d > _GEMM_MAX_SPAN:
+            if d < 1 or (resblock == "1" and (k - 1) * d > _GEMM_MAX_SPAN):
                 return f"residual kernel size {k} with dilation {d}: efts_gemm takes (k - 1) * d <= {_GEMM_MAX_SPAN} rows, d >= 1"
+        if resblock == "2" and not _rb2_composable(k, ds):
+            # a window span above 64 rows: only the fused launch can run it, in every stage
+            c_max = c0 // 2 if c0 > 0 else 0
+            if c_max > _RB2_MAX_C:
+                return (f"ResBlock2 with kernel size {k} and dilations {list(ds)} at {c_max} channels: (k - 1) * d above {_GEMM_MAX_SPAN} rows "
+                        f"is beyond efts_gemm, and efts_resblock2 takes c <= {_RB2_MAX_C}")
+            if k not in _RB2_TAPS or (k - 1) // 2 * (ds[0] + ds[1]) > _RB2_MAX_HALO:
+                return (f"ResBlock2 with kernel size {k} and dilations {list(ds)}: (k - 1) * d above {_GEMM_MAX_SPAN} rows is beyond efts_gemm, "
+                        f"and efts_resblock2 takes (k - 1) / 2 * (d0 + d1) <= {_RB2_MAX_HALO} rows")
     c_last = c0 // 2 ** len(rates)
     if c0 <= 0 or c0 % 2 ** len(rates) or c_last % 4:
         return (f"upsample_initial_channel {c0} over {len(rates)} stages: every stage needs a whole channel count that is a multiple "
@@ -102,6 +136,17 @@ class _ResBlock1(nn.Module):
         self.kernel_size, self.dilation = kernel_size, tuple(dilation)
 
 
+class _ResBlock2(nn.Module):
+    """parameter container with the reference's names (hifigan_model.py:71-79); never called"""
+
+    def __init__(self, channels: int, kernel_size: int, dilation):
+        super().__init__()
+        pad = lambda d: (kernel_size * d - d) // 2
+        self.convs = nn.ModuleList([weight_norm(nn.Conv1d(channels, channels, kernel_size, 1, dilation=d, padding=pad(d)))
+                                    for d in dilation[:2]])
+        self.kernel_size, self.dilation = kernel_size, tuple(dilation[:2])
+
+
 class _Rows:
     """fp32 [rows][c] stream + its operand plane, both with zero guard rows"""
 
@@ -119,8 +164,7 @@ class _Rows:
 class HiFiGANGenerator(nn.Module):
     def __init__(self, h, precision: str = "bf16x3"):
         super().__init__()
-        if str(_cfg(h, "resblock", "1")) != "1":
-            raise NotImplementedError("only ResBlock1 (the HiFiGAN_LJ_V1 configuration) is implemented")
+        self.resblock = str(_cfg(h, "resblock", "1"))
         splits = {"bf16": L.SPLIT_BF16, "bf16x3": L.SPLIT_BF16X3, "fp32": L.SPLIT_FP32}     # fp32: exact operands, generic efts_gemm tiling
         if precision not in splits:
             raise ValueError("precision must be 'bf16x3', 'bf16' or 'fp32'")
@@ -131,7 +175,8 @@ class HiFiGANGenerator(nn.Module):
         self.res_dilations = tuple(tuple(d) for d in _cfg(h, "resblock_dilation_sizes"))
         c0 = int(_cfg(h, "upsample_initial_channel"))
         self.num_mels = int(_cfg(h, "num_mels", 80))
-        why = _refusal(self.upsample_rates, self.upsample_kernel_sizes, self.res_kernels, self.res_dilations, c0, self.num_mels)
+        why = _refusal(self.upsample_rates, self.upsample_kernel_sizes, self.res_kernels, self.res_dilations, c0, self.num_mels,
+                       self.resblock)
         if why is not None:
             raise NotImplementedError(why)
         self.gap_frames = gap_frames(self.upsample_rates, self.res_kernels, self.res_dilations)
@@ -143,7 +188,7 @@ class HiFiGANGenerator(nn.Module):
         for i in range(len(self.ups)):
             ch = c0 // 2 ** (i + 1)
             for k, d in zip(self.res_kernels, self.res_dilations):
-                self.resblocks.append(_ResBlock1(ch, k, d))
+                self.resblocks.append((_ResBlock2 if self.resblock == "2" else _ResBlock1)(ch, k, d))
         self.conv_post = weight_norm(nn.Conv1d(ch, 1, 7, 1, padding=3))
         self._packed: Optional[Dict[str, PackedWeight]] = None
         self._packed_dev = None
@@ -152,6 +197,12 @@ class HiFiGANGenerator(nn.Module):
         # per-shape hipGraph of the ~85 launches of a call (round 6; efficient_tts_amd/graphs.py, the acoustic model's cache): one utterance is
         # 2 ms of device work issued by a host that needs about as long for the launches; `graphs = False`: every launch issued eagerly
         self.graphs = True
+        # resblock "2": True = every ResBlock2 that efts_resblock2 can run is ONE launch (the intermediate stays in LDS) and two efts_gemm
+        # launches run the others (more than 128 channels); False = two efts_gemm launches wherever they can run (window spans up to 64
+        # rows) and the fused launch for the rest.  Measured (tools/micro/vocoder_rb2_timing.py, profiles/vocoder_rb2_timing.json): V3 at one
+        # 800-frame utterance 0.87 ms fused against 0.74 ms composed, 4.79 against 3.95 ms at a batch of 8 -- so the default composes and the
+        # fused launch runs the blocks only it can run (V3: k = 7, d = 12)
+        self.fused_resblock2 = False
         self.branch_streams = True          # the residual blocks of a stage on streams of their own (False: one after the other, A/B)
         from .graphs import GraphCache
         object.__setattr__(self, "_graph_cache", GraphCache(capacity=4))
@@ -162,7 +213,7 @@ class HiFiGANGenerator(nn.Module):
         for m in [self.conv_pre, self.conv_post, *self.ups]:
             remove_weight_norm(m)
         for rb in self.resblocks:
-            for m in [*rb.convs1, *rb.convs2]:
+            for m in ([*rb.convs] if self.resblock == "2" else [*rb.convs1, *rb.convs2]):
                 remove_weight_norm(m)
         self._packed = None
 
@@ -206,6 +257,9 @@ class HiFiGANGenerator(nn.Module):
                 self._bias[f"ups.{i}"] = m.bias.detach().float().repeat(u).contiguous()
             for n, rb in enumerate(self.resblocks):
                 for d in range(len(rb.dilation)):
+                    if self.resblock == "2":
+                        conv(f"rb{n}.c.{d}", rb.convs[d])
+                        continue
                     conv(f"rb{n}.c1.{d}", rb.convs1[d])
                     conv(f"rb{n}.c2.{d}", rb.convs2[d])
         self._packed = pk
@@ -226,7 +280,8 @@ class HiFiGANGenerator(nn.Module):
             n_i = rows * u
             b[f"up{i}"] = _Rows((rows + 1) * u, cout, sp, dev, plane=False)  # the [rows + 1][u * cout] GEMM result, seen as rows of cout
             b[f"x{i}"] = _Rows(n_i, cout, sp, dev, f32=False)                # plane of leaky(x_i)
-            b[f"t{i}"] = [_Rows(n_i, cout, sp, dev, f32=False) for _ in self.res_kernels]   # plane of leaky(xt), one per residual block (they run side by side)
+            if self.resblock == "1":
+                b[f"t{i}"] = [_Rows(n_i, cout, sp, dev, f32=False) for _ in self.res_kernels]   # plane of leaky(xt), one per residual block (they run side by side)
             b[f"r{i}"] = [[_Rows(n_i, cout, sp, dev) for _ in range(2)] for _ in self.res_kernels]   # ping-pong per residual block
             b[f"s{i}"] = _Rows(n_i, cout, sp, dev, f32=False)                # plane of leaky(mean)
             b["mask"].append(torch.zeros(n_i + 1, dtype=torch.float32, device=dev))
@@ -282,7 +337,7 @@ class HiFiGANGenerator(nn.Module):
             return body(mel, lens)[0]
         ws = self._workspace_for(B, T, dev)
         # the graph is valid while the buffers its launches point at live: this workspace and the packed planes
-        tag = (id(ws), tuple(w.ptr for w in pk.values()), self.split)
+        tag = (id(ws), tuple(w.ptr for w in pk.values()), self.split, self.fused_resblock2)
         return self._graph_cache.run(("voc", B, T), tag, (mel, lens), body, keepalive=(ws, pk), adaptive=True)[0]
 
     def _conv(self, pk, name, a: Plane, rows, taps, dil, *, mask=None, out_f=None, ldo=0, out_p=None, plane_slope=None, resid=None,
@@ -292,11 +347,37 @@ class HiFiGANGenerator(nn.Module):
                resid_ptr=resid, ldr=ldr, rowmask_ptr=None if mask is None else mask.data_ptr(), out_f32_ptr=out_f, ldo=ldo,
                out_plane=out_p, dilation=dil, plane_act=plane_slope is not None, plane_slope=0.0 if plane_slope is None else plane_slope)
 
+    def _rb2_fused(self, c: int, k: int, ds) -> bool:
+        """which launches run a ResBlock2 of this geometry (`fused_resblock2`; the constructor refused what neither can)"""
+        if self.fused_resblock2:
+            return _rb2_fusable(c, k, ds)
+        return not _rb2_composable(k, ds)
+
+    def _resblock2(self, pk, n: int, x_f: int, x_p: Plane, pp, rows: int, c: int, k: int, ds, mask: torch.Tensor) -> int:
+        """ResBlock2 n (hifigan_model.py:81-88) on the current stream: x <- x + conv_{k,d}(leaky(x)) for d = ds[0], ds[1]; returns the
+        pointer of the fp32 result (pp[1])"""
+        if self._rb2_fused(c, k, ds):
+            w0, w1 = pk[f"rb{n}.c.0"], pk[f"rb{n}.c.1"]
+            g = L.ResBlock2Args()
+            g.x, g.ldx, g.p0, g.ldp = x_f, c, x_p.ptr, x_p.ld
+            g.w0, g.w1, g.ldw, g.w_tap_stride = w0.ptr, w1.ptr, w0.ld, w0.tap_stride
+            g.bias0, g.bias1 = self._bias[f"rb{n}.c.0"].data_ptr(), self._bias[f"rb{n}.c.1"].data_ptr()
+            g.rowmask, g.out, g.ldo = mask.data_ptr(), pp[1].fptr, c
+            g.split, g.m, g.c, g.k, g.d0, g.d1, g.slope = self.split, rows, c, k, ds[0], ds[1], LRELU_SLOPE
+            L.check(L.load().efts_resblock2(ctypes.byref(g), O._stream()), "efts_resblock2")
+            return pp[1].fptr
+        # one efts_gemm launch per turn: the first also writes the operand plane of leaky(y1) for the second
+        self._conv(pk, f"rb{n}.c.0", x_p, rows, k, ds[0], mask=mask, out_f=pp[0].fptr, ldo=c, out_p=pp[0].p, plane_slope=LRELU_SLOPE,
+                   resid=x_f, ldr=c)
+        self._conv(pk, f"rb{n}.c.1", pp[0].p, rows, k, ds[1], mask=mask, out_f=pp[1].fptr, ldo=c, resid=pp[0].fptr, ldr=c)
+        return pp[1].fptr
+
     def _run(self, pk, mel_btc: torch.Tensor, lens: torch.Tensor, audio: torch.Tensor, B: int, T: int, hop: int, dev,
              keep: Optional[dict] = None) -> None:
         """keep (None: nothing happens): after each step a clone of what it wrote, made on the stream of the step's launch and complete
         when `_run` returns (it ends with a device synchronisation then).  Whole buffers, guard rows included: "pre", "x{i}", "s{i}"
-        operand planes (uint8 [alloc][ld], row 0 at _GUARD); "r{i}.{j}.{d}" fp32 [alloc][c] of residual block j after pair d;
+        operand planes (uint8 [alloc][ld], row 0 at _GUARD); "r{i}.{j}.{d}" fp32 [alloc][c] of residual block j after pair d (resblock "2":
+        "r{i}.{j}", the block's fp32 output);
         "up{i}" fp32 [rows][c] behind the u / 2-row offset; "out" fp32 [rows + 256][1]; "pitch": rows per item at mel rate."""
         b = self._workspace_for(B, T, dev)
         lib = L.load()
@@ -353,8 +434,12 @@ class HiFiGANGenerator(nn.Module):
                     own.wait_event(ev_x)
                 with (O.on_stream(own) if own is not None else contextlib.nullcontext()):
                     r_f, r_p, pp = x_f, x_p, b[f"r{i}"][j]
-                    tp = b[f"t{i}"][j].p
-                    for d_i, d in enumerate(rb.dilation):
+                    if self.resblock == "2":
+                        r_f = self._resblock2(pk, n + j, x_f, x_p, pp, n_i, cout, k, rb.dilation, mask)
+                        if keep is not None:
+                            keep[f"r{i}.{j}"] = pp[1].f.clone()
+                    tp = b[f"t{i}"][j].p if self.resblock == "1" else None
+                    for d_i, d in enumerate(rb.dilation if self.resblock == "1" else ()):
                         self._conv(pk, f"rb{n + j}.c1.{d_i}", r_p, n_i, k, d, mask=mask, out_p=tp, plane_slope=LRELU_SLOPE)  # :47-48 (+ :49)
                         nxt = pp[d_i & 1]
                         self._conv(pk, f"rb{n + j}.c2.{d_i}", tp, n_i, k, 1, mask=mask, out_f=nxt.fptr, ldo=cout, out_p=nxt.p,

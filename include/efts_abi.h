@@ -108,7 +108,9 @@ extern "C" {
  *        + efts_iir, efts_iir_pcm16, efts_iir_workspace_bytes (a cascade of second-order sections with exact state carry): exports added,
  *          the revision stays by the same rule
  *        + efts_pauses, efts_pauses_pcm16, efts_pauses_workspace_bytes (shortening the long pauses inside a recording): exports added, the
- *          revision stays by the same rule */
+ *          revision stays by the same rule
+ *        + efts_resblock2 (one HiFi-GAN ResBlock2, two dilated convolutions fused through LDS): export added, the revision stays by the
+ *          same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -1439,6 +1441,57 @@ int efts_iir(const float* in, int64_t ld_in, const int32_t* lengths, const doubl
              int64_t ld_out, void* workspace, int32_t B, void* stream);
 int efts_iir_pcm16(const int16_t* in, int64_t ld_in, const int32_t* lengths, const double* sos, int32_t sections, const double* powers,
                    float pcm_scale, float* out, int64_t ld_out, void* workspace, int32_t B, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * One HiFi-GAN ResBlock2 (nntts/vocoders/hifigan_model.py:71-93) in ONE launch: two pre-activation turns
+ *     x <- x + conv_{k,d}(LeakyReLU(x))
+ * with dilations d0 and d1 on a row space of m rows and c channels (channel-last, one row per sample).
+ * Inputs : x, the fp32 stream [m][ldx]; p0, the operand plane of LeakyReLU(x) * rowmask as its producer wrote it (format `split`,
+ *          row stride ldp bytes, ceil(c / 64) (split 1) or ceil(c / 32) (split 2, 3) chunks per row); w0, w1, the packed weights of the
+ *          two convolutions ([k][c][ldw] of efts_pack_weight, format `split`, tap stride w_tap_stride bytes); bias0, bias1 [c] or NULL;
+ *          rowmask [m] (or NULL: all ones).
+ * With h0 = (k - 1) / 2 * d0, h1 = (k - 1) / 2 * d1 and P(row) = 0 for every row outside 0 .. m - 1 (the zero guard rows: nothing is read
+ * there), per row r and column j < c:
+ *     a1[r][j] = sum over chunk ascending, tap t = 0 .. k - 1 ascending, k-slice ascending of P0[r + t d0 - h0][.] . W0[t][j][.]
+ *                (fp32 accumulation on the MFMA of the format: one mfma_f32_32x32x16_bf16 per 16 k's for split 1; lo*hi, hi*lo, hi*hi
+ *                per 16 k's for split 2; v_mfma_f32_32x32x2_f32 in the k order of efts_gemm for split 3)
+ *     y1[r][j] = ((a1 + bias0[j]) + x[r][j]) * rowmask[r]                                     -- the epilogue order of efts_gemm
+ *     P1[r][j] = the plane value of v = y1 > 0 ? y1 : y1 * slope, rounded as plane_act of efts_gemm rounds: split 1 bf16(v) (nearest
+ *                even); split 2 hi = bf16(v), lo = bf16(v - hi); split 3 v itself
+ *     a2[r][j] = the same contraction of P1 with W1 at dilation d1
+ *     out[r][j] = ((a2 + bias1[j]) + y1[r][j]) * rowmask[r],  fp32 [m][ldo]; columns j >= c of out are not written.
+ * y1 and P1 never reach memory: a workgroup owns 32 n - 2 h1 rows (n <= 6 blocks of 32, as many as fit the LDS), stages the window of P0
+ * with both halos in LDS, computes y1 on its rows plus the second halo, overwrites the window with P1 and contracts again.  The result of
+ * a row depends on the values of rows r - h0 - h1 .. r + h0 + h1 alone, never on where a tile begins: an item gives the same bits alone
+ * or anywhere in a batch, and the result equals two efts_gemm launches (plane_act, resid, rowmask) up to the summation order inside the
+ * fp32 accumulator.  No atomics, no launch geometry from device data: capturable.
+ * EFTS_EINVAL: null args / operand, split outside 1 .. 3, k outside {3, 5, 7, 9, 11}, reserved != 0.  EFTS_ESHAPE: m <= 0, c outside
+ * 4 .. 128 or c % 4 != 0, d0 or d1 outside 1 .. 64, (k - 1) / 2 * (d0 + d1) > 64, a row stride below the row.  EFTS_EALIGN: x, p0, w0, w1, out or a row / tap stride
+ * not 16-byte aligned.
+ * ---------------------------------------------------------------------------------- */
+typedef struct efts_resblock2_args {
+    const float* x;       /* fp32 [m][ldx] */
+    int64_t ldx;          /* elements, % 4 == 0 */
+    const void* p0;       /* operand plane of LeakyReLU(x) * rowmask, row 0 */
+    int64_t ldp;          /* bytes */
+    const void* w0;       /* packed weights of the two convolutions */
+    const void* w1;
+    int64_t ldw;          /* bytes, both */
+    int64_t w_tap_stride; /* bytes, both */
+    const float* bias0;   /* [c] or NULL */
+    const float* bias1;
+    const float* rowmask; /* [m] or NULL */
+    float* out;           /* fp32 [m][ldo] */
+    int64_t ldo;          /* elements, % 4 == 0 */
+    int32_t split;        /* 1, 2 or 3: format of p0, w0, w1 and of the intermediate plane */
+    int32_t m;            /* rows */
+    int32_t c;            /* channels */
+    int32_t k;            /* kernel size of both convolutions */
+    int32_t d0, d1;       /* their dilations */
+    float slope;          /* LeakyReLU slope of the intermediate */
+    int32_t reserved;     /* 0 */
+} efts_resblock2_args;
+int efts_resblock2(const efts_resblock2_args* a, void* stream);
 
 #ifdef __cplusplus
 }
