@@ -132,6 +132,47 @@ def test_constructor_accepts_what_one_of_the_two_paths_can_run():
     assert HiFiGANGenerator(RR.CASES["limit"]["cfg"]).gap_frames == 12
 
 
+def test_each_block_kind_owns_its_packed_names_and_its_refusals():
+    """what depends on the kind lives in the block classes: the packed names in launch order (`packed`) are the lists the generator
+    used to write out itself, and `_refusal` says about a block exactly what the block's class says (`refusal`)"""
+    import vocoder_reference as VR
+    from efficient_tts_amd.vocoder import HiFiGANGenerator, _refusal, _ResBlock1, _ResBlock2
+
+    def names(m):
+        return [name for n, rb in enumerate(m.resblocks) for name, _ in rb.packed(n)]
+    v1, v3 = HiFiGANGenerator(VR.V1), HiFiGANGenerator(RR.V3)
+    assert names(v1)[:18] == ["rb0.c1.0", "rb0.c2.0", "rb0.c1.1", "rb0.c2.1", "rb0.c1.2", "rb0.c2.2",
+                              "rb1.c1.0", "rb1.c2.0", "rb1.c1.1", "rb1.c2.1", "rb1.c1.2", "rb1.c2.2",
+                              "rb2.c1.0", "rb2.c2.0", "rb2.c1.1", "rb2.c2.1", "rb2.c1.2", "rb2.c2.2"]          # the first stage
+    assert len(names(v1)) == len(set(names(v1))) == 72 and names(v1)[-1] == "rb11.c2.2"                        # 4 stages x 3 blocks x 3 pairs
+    assert names(v3)[:6] == ["rb0.c.0", "rb0.c.1", "rb1.c.0", "rb1.c.1", "rb2.c.0", "rb2.c.1"]                 # the first stage
+    assert len(names(v3)) == len(set(names(v3))) == 18 and names(v3)[-1] == "rb8.c.1"                          # 3 stages x 3 blocks x 2 turns
+    rb = v1.resblocks[4]
+    assert [id(m) for _, m in rb.packed(4)] == [id(m) for d in range(3) for m in (rb.convs1[d], rb.convs2[d])]
+    assert [id(m) for _, m in v3.resblocks[5].packed(5)] == [id(m) for m in v3.resblocks[5].convs]
+
+    def through_the_class(cfg, cls):
+        c_max = cfg["upsample_initial_channel"] // 2
+        return next((w for w in (cls.refusal(k, tuple(ds), c_max) for k, ds in zip(cfg["resblock_kernel_sizes"], cfg["resblock_dilation_sizes"]))
+                     if w is not None), None)
+
+    def whole(cfg):
+        return _refusal(tuple(cfg["upsample_rates"]), tuple(cfg["upsample_kernel_sizes"]), tuple(cfg["resblock_kernel_sizes"]),
+                        tuple(tuple(d) for d in cfg["resblock_dilation_sizes"]), cfg["upsample_initial_channel"], cfg["num_mels"], cfg["resblock"])
+    for what, (change, reason) in REFUSED.items():
+        cfg = dict(_BASE, **change)
+        assert reason in whole(cfg), what
+        if what not in ("residual kernel 13", "resblock 3"):           # (those two are refused before a block class is asked)
+            assert reason in through_the_class(cfg, _ResBlock2) and through_the_class(cfg, _ResBlock2) == whole(cfg), what
+    for cfg in [_BASE] + [cs["cfg"] for cs in RR.CASES.values()]:
+        assert whole(cfg) is None and through_the_class(cfg, _ResBlock2) is None
+    for cfg in [VR.V1] + [cs["cfg"] for cs in VR.CASES.values()]:
+        assert whole(cfg) is None and through_the_class(cfg, _ResBlock1) is None
+    assert _ResBlock2.refusal(11, (6, 6), 32) is None and "(k - 1) / 2 * (d0 + d1) <= 64" in _ResBlock2.refusal(11, (6, 7), 32)
+    assert "(k - 1) * d <= 64 rows" in _ResBlock1.refusal(11, (1, 7), 256) and "d >= 1" in _ResBlock1.refusal(3, (1, 0), 256)
+    assert _ResBlock1.refusal(7, (3, 12), 256) == whole(dict(VR.V1, resblock_kernel_sizes=[7], resblock_dilation_sizes=[[3, 12]]))
+
+
 def test_resblock2_args_layout_and_argument_errors():
     """sizeof / offsets of efts_resblock2_args as compiled by gcc == the ctypes mirror, and the entry refuses bad arguments before any launch"""
     import ctypes

@@ -138,7 +138,7 @@ def test_kernel_alone_vs_fp64(lib, m, c, k, d0, d1, precision):
     w = [torch.randn(c, c, k, generator=g) / (c * k) ** 0.5 for _ in range(2)]
     b = [0.1 * torch.randn(c, generator=g) for _ in range(2)]
     xd, md = x.to(dev), mask.to(dev)
-    # the input plane as its producer writes it: leaky(x) * mask (efts_act_bwd mode 3, HiFiGANGenerator._run)
+    # the input plane as its producer writes it: leaky(x) * mask (efts_act_bwd mode 3, HiFiGANGenerator._stage_upsample)
     p0 = Plane(guard + m + 8, c, sp, dev, guard_lo=guard)
     xc = xd[:, :c].contiguous()
     _call("efts_act_bwd", lib.efts_act_bwd(xc.data_ptr(), xc.data_ptr(), None, md.data_ptr(), slope, 3, None, p0.ptr, p0.ld, sp, None, m, c, _st()))
