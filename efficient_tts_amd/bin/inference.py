@@ -62,6 +62,7 @@ from efficient_tts_amd.pitch import PitchTracker
 from efficient_tts_amd.resample import QUALITIES, Resampler
 from efficient_tts_amd.vocoder import HiFiGANGenerator, load_hifigan_generator
 
+HOP = 256             # samples per mel frame of the acoustic model's and the front-end's frames, and so of every vocoder here
 _V1 = dict(resblock="1", upsample_rates=[8, 8, 2, 2], upsample_kernel_sizes=[16, 16, 4, 4], upsample_initial_channel=512,
            resblock_kernel_sizes=[3, 7, 11], resblock_dilation_sizes=[[1, 3, 5], [1, 3, 5], [1, 3, 5]], num_mels=80)
 SAMPLING_RATE = 22050
@@ -81,7 +82,7 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--test_fid_scp", type=str, required=True, help="utterance list: wav_path|phoneme sequence")
     p.add_argument("--outdir", type=str, required=True, help="where the generated speech goes")
     p.add_argument("--config", type=str, default=None, help="training config.yml (default: next to the checkpoint)")
-    p.add_argument("--vocoder_config", type=str, default=None, help="HiFi-GAN config.json (default: the V1 LJSpeech configuration)")
+    p.add_argument("--vocoder_config", type=str, default=None, help="HiFi-GAN config.json (default: the V1 LJSpeech configuration); with gen_istft_n_fft / gen_istft_hop_size an iSTFTNet one, e.g. C8C8I: upsample_rates [8, 8], upsample_kernel_sizes [16, 16], gen_istft_n_fft 16, gen_istft_hop_size 4")
     p.add_argument("--vocoder_checkpoint", type=str, default=None, help='HiFi-GAN checkpoint with a "generator" state_dict')
     p.add_argument("--vocoder", type=str, default="hifigan", choices=["hifigan", "griffinlim"],
                    help="hifigan (default): the HiFi-GAN V1 generator; griffinlim: phase reconstruction on the device, needs no vocoder checkpoint")
@@ -169,7 +170,11 @@ def build_vocoder(args, device):
     if args.vocoder_checkpoint:
         if not args.vocoder_config:
             raise ValueError("--vocoder_checkpoint needs --vocoder_config")
-        return load_hifigan_generator(device, args.vocoder_config, args.vocoder_checkpoint, precision=args.precision)
+        vocoder = load_hifigan_generator(device, args.vocoder_config, args.vocoder_checkpoint, precision=args.precision)
+        if vocoder.hop != HOP:                  # (an iSTFTNet config counts its head's hop in: C8C8I is 8 * 8 * 4 = 256)
+            raise ValueError(f"--vocoder_config: the generator makes {vocoder.hop} samples per mel frame; the mel frames here are {HOP} samples at "
+                             f"{SAMPLING_RATE} Hz (upsample_rates, times gen_istft_hop_size for an iSTFT head, must multiply to {HOP})")
+        return vocoder
     logging.warning("no --vocoder_checkpoint: the HiFi-GAN generator runs with RANDOM weights (timing / smoke only)")
     vocoder = HiFiGANGenerator(_V1, precision=args.precision).to(device).eval()
     vocoder.remove_weight_norm()

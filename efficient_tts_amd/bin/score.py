@@ -71,7 +71,7 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--f0", action="store_true", help="also score pitch along the MCD's warping path: F0 error in cents and voiced/unvoiced error")
     p.add_argument("--vocoder", type=str, default="hifigan", choices=["hifigan", "griffinlim"],
                    help="--f0: what turns the synthesised mel into audio (as efficient_tts_amd.bin.inference); hifigan needs --vocoder_checkpoint")
-    p.add_argument("--vocoder_config", type=str, default=None, help="--f0: HiFi-GAN config.json")
+    p.add_argument("--vocoder_config", type=str, default=None, help="--f0: HiFi-GAN config.json (or an iSTFTNet one such as C8C8I: gen_istft_n_fft 16, gen_istft_hop_size 4 under upsample_rates [8, 8])")
     p.add_argument("--vocoder_checkpoint", type=str, default=None, help='--f0: HiFi-GAN checkpoint with a "generator" state_dict')
     p.add_argument("--gl_iters", type=int, default=32, help="--f0: Griffin-Lim iterations (--vocoder griffinlim; default 32)")
     p.add_argument("--f0_min", type=float, default=60.0, help="--f0: lowest fundamental searched, Hz (default 60)")

@@ -48,7 +48,7 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--test_fid_scp", type=str, required=True, help="utterance list: wav_path, optionally followed by |anything")
     p.add_argument("--outdir", type=str, required=True, help="where mrstft.tsv goes")
     p.add_argument("--vocoder", type=str, default="hifigan", choices=["hifigan", "griffinlim"], help="what turns the recordings' log-mels back into audio")
-    p.add_argument("--vocoder_config", type=str, default=None, help="HiFi-GAN config.json")
+    p.add_argument("--vocoder_config", type=str, default=None, help="HiFi-GAN config.json (or an iSTFTNet one such as C8C8I: gen_istft_n_fft 16, gen_istft_hop_size 4 under upsample_rates [8, 8])")
     p.add_argument("--vocoder_checkpoint", type=str, default=None, help='HiFi-GAN checkpoint with a "generator" state_dict')
     p.add_argument("--gl_iters", type=int, default=32, help="Griffin-Lim iterations (--vocoder griffinlim; default 32)")
     p.add_argument("--precision", type=str, default="bf16x3", choices=["bf16x3", "bf16", "fp32"], help="MFMA operand mode of the vocoder")

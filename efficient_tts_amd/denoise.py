@@ -97,6 +97,9 @@ class BiasDenoiser(torch.nn.Module):
         mel = torch.full((1, A.as_int(num_mels, "num_mels"), A.as_int(frames, "frames")), float(mel_value), dtype=torch.float32, device=device)
         with torch.no_grad():
             audio = vocoder(mel)
+        if audio.numel() <= N_FFT // 2:        # (a generator of few samples per frame: HiFi-GAN V1 and C8C8I make 256, 88 frames are 22528 samples)
+            raise ValueError(f"BiasDenoiser.from_vocoder: {audio.numel()} samples from {frames} frames hold no {N_FFT}-point STFT frame; raise `frames`")
+        with torch.no_grad():
             mag, _ = STFTMagnitude(device, N_FFT, HOP, N_FFT)(audio.reshape(1, -1).float())
         return cls(device, mag[0, 0], strength=strength)
 

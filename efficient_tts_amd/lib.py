@@ -112,6 +112,15 @@ class ResBlock2Args(C.Structure):
                 ("split", i32), ("m", i32), ("c", i32), ("k", i32), ("d0", i32), ("d1", i32), ("slope", f32), ("reserved", i32)]
 
 
+class IstftHeadArgs(C.Structure):
+    """mirror of `struct efts_istft_head_args` (include/efts_abi.h)"""
+    _fields_ = [("z", vp), ("lengths", vp), ("window", vp), ("twiddle", vp), ("audio", vp), ("ld_audio", i64), ("plane", vp), ("ld_plane", i64),
+                ("mode", i32), ("B", i32), ("pitch", i32), ("z_rows", i32), ("len_mul", i32), ("out_len", i32), ("n_fft", i32), ("hop", i32),
+                ("reserved", i32), ("reserved2", i32)]
+
+
+ISTFT_SYNTH, ISTFT_REFLECT = 0, 1       # EFTS_ISTFT_*: the two launches of efts_istft_head
+ISTFT_RUN = 1024                        # EFTS_ISTFT_RUN: samples per workgroup
 WGRAD_MAX_ITEMS = 8
 
 OPTIM_ADAM, OPTIM_ADAMW, OPTIM_RADAM = 0, 1, 2      # EFTS_OPTIM_*
@@ -259,6 +268,8 @@ _SIGS = {
     "efts_iir_pcm16": (i32, [vp, i64, vp, C.POINTER(C.c_double), i32, vp, f32, vp, i64, vp, i32, vp]),
     # one HiFi-GAN ResBlock2 (two dilated convolutions, the intermediate in LDS)
     "efts_resblock2": (i32, [C.POINTER(ResBlock2Args), vp]),
+    # the inverse-STFT head of an iSTFTNet generator (and the reflected row in front of every item of its operand plane)
+    "efts_istft_head": (i32, [C.POINTER(IstftHeadArgs), vp]),
 }
 
 _lib: Optional[C.CDLL] = None

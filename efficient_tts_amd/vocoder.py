@@ -1,8 +1,9 @@
-"""HiFi-GAN generators (ResBlock1: V1 / V2; ResBlock2: V3) on the MI355X contraction kernels.
+"""HiFi-GAN generators (ResBlock1: V1 / V2; ResBlock2: V3) and iSTFTNet generators (the same trunk under an inverse-STFT head: C8C8I, C8C8C2I)
+on the MI355X contraction kernels.
 
 Drop-in for `nntts.vocoders.hifigan_model.Generator` (nntts/vocoders/hifigan_model.py:95-150): same constructor argument (the config object / dict of
 a HiFi-GAN config.json), same parameter names and shapes (`state_dict` of the reference loads unchanged, weight_g / weight_v pairs),
-`forward(mel [B, num_mels, T]) -> audio [B, 1, T * prod(upsample_rates)]`, `remove_weight_norm()`.  Inference only; there is no CPU path.
+`forward(mel [B, num_mels, T]) -> audio [B, 1, T * hop]` (hop = prod(upsample_rates), times N / 4 under an iSTFT head), `remove_weight_norm()`.  Inference only; there is no CPU path.
 
 A forward is a short driver (`_run`) over stages; `_Pass` is what every stage reads, a namedtuple what one hands to the next:
   * `_stage_pre`: the mel as an operand plane, its row mask, conv_pre.  Every Conv1d is one `efts_gemm` launch on channel-last rows (one row per
@@ -14,7 +15,10 @@ A forward is a short driver (`_run`) over stages; `_Pass` is what every stage re
     the last.  WHAT a chain launches belongs to its block class alone: `_ResBlock1` / `_ResBlock2` say what they refuse, which convolutions they
     pack, which buffers a chain needs and which launches run it.  The generator names a kind once, where it picks the class (`_BLOCKS`);
   * `_stage_mean`: the multi-receptive-field mean and the LeakyReLU of the next layer's input, `efts_mean_act_rows`;
-  * `_stage_post`: conv_post with the kernel's tanh epilogue and the copy into the audio -- the only code that knows the head.
+  * `_stage_post`: the head, the only code that knows it.  `_TanhHead` (HiFi-GAN): conv_post with the kernel's tanh epilogue and the copy into the
+    audio.  `_IstftHead` (config keys `gen_istft_n_fft` = N, `gen_istft_hop_size` = N / 4; Kaneko et al., ICASSP 2022): the reflected row in front
+    of every item, conv_post as an `efts_gemm` launch with N + 2 fp32 columns, and `efts_istft_head` (csrc/efts_istft_head.hip), which writes the
+    audio itself: `hop` = prod(upsample_rates) * N / 4 samples per mel frame.
 Batches: the B utterances share one row space per stage, item b at rows b * P .. b * P + T_b * up with a pitch of P = (T + gap) * up rows.  `gap`
 spare mel frames (`gap_frames`) come from the configuration: at the first upsampled stage they are gap * upsample_rates[0] zero rows, no fewer than
 the largest halo of a residual convolution, max (k - 1) / 2 * d; never fewer than 4 frames, which cover conv_pre (3 rows at mel rate) and the extra
@@ -48,6 +52,7 @@ _GEMM_MAX_SPAN = 64    # efts_gemm: (taps - 1) * dilation rows of window at the 
 _RB2_TAPS = (3, 5, 7, 9, 11)           # what efts_resblock2 takes as `k`
 _RB2_MAX_C = 128       # efts_resblock2: channels at the most
 _RB2_MAX_HALO = _GUARD  # efts_resblock2: (k - 1) / 2 * (d0 + d1) rows at the most
+_ISTFT_N = (8, 16, 32)  # efts_istft_head: transform sizes
 
 
 def _cfg(h, key, default=None):
@@ -77,9 +82,9 @@ class _Rows:
 
 class _Pass:
     """What every stage of one forward reads.  ws: the workspace of the shape (`_Workspace`); pk: `_Conv` by packed name; B, T: the mel
-    batch; pitch: rows per item at mel rate; hop: samples per frame; lens: int32 frames per item on the device; dev; st: the main
+    batch; pitch: rows per item at mel rate; rate: rows per frame at the last stage; lens: int32 frames per item on the device; dev; st: the main
     stream's handle; split: the operand format; fused: `_rb2_fused`, which arm runs a ResBlock2; keep: the dict the stage tests read, or None"""
-    __slots__ = ("ws", "pk", "B", "T", "pitch", "hop", "lens", "dev", "st", "split", "fused", "keep")
+    __slots__ = ("ws", "pk", "B", "T", "pitch", "rate", "lens", "dev", "st", "split", "fused", "keep")
 
     def __init__(self, **fields):
         for k, v in fields.items():
@@ -88,14 +93,14 @@ class _Pass:
 
 _Conv = namedtuple("_Conv", "w bias")                         # one packed convolution: PackedWeight and its fp32 bias, made together
 _Stage = namedtuple("_Stage", "up x chains s mask")           # up: fp32 GEMM result; x, s: planes of leaky(x), leaky(mean); chains: `scratch` per block
-_Workspace = namedtuple("_Workspace", "pitch mel pre stages mask_mel out")
+_Workspace = namedtuple("_Workspace", "pitch mel pre stages mask_mel head")     # head: what the head class's `scratch` made
 _Act = namedtuple("_Act", "p rows")                           # handed on by conv_pre and by a stage's mean: the plane the next contraction reads
 _Up = namedtuple("_Up", "x_f x_p mask rows c")                # handed on by the upsampling: fp32 pointer and plane of leaky(x), row mask, rows, channels
 
 
 def _conv(cv: _Conv, a: Plane, rows, taps, dil, *, mask=None, out_f=None, ldo=0, out_p=None, plane_slope=None, resid=None, ldr=0,
-          act=L.ACT_NONE):
-    O.gemm(a=a, b_ptr=cv.w.ptr, ldb=cv.w.ld, b_tap_stride=cv.w.tap_stride, taps=taps, m=rows, n=cv.w.cout, bias=cv.bias, act=act,
+          act=L.ACT_NONE, a_ptr=None):
+    O.gemm(a=a, a_ptr=a_ptr, b_ptr=cv.w.ptr, ldb=cv.w.ld, b_tap_stride=cv.w.tap_stride, taps=taps, m=rows, n=cv.w.cout, bias=cv.bias, act=act,
            resid_ptr=resid, ldr=ldr, rowmask_ptr=None if mask is None else mask.data_ptr(), out_f32_ptr=out_f, ldo=ldo,
            out_plane=out_p, dilation=dil, plane_act=plane_slope is not None, plane_slope=0.0 if plane_slope is None else plane_slope)
 
@@ -207,8 +212,86 @@ class _ResBlock2(nn.Module):
 _BLOCKS = {"1": _ResBlock1, "2": _ResBlock2}
 
 
-def _refusal(rates, kernels, res_kernels, res_dilations, c0, num_mels, resblock: str = "1") -> Optional[str]:
+class _TanhHead:
+    """HiFi-GAN's head (hifigan_model.py:130-131): conv_post to one channel with the kernel's tanh epilogue, the items copied out of the row space"""
+    channels, samples_per_row, writes_silence, tag = 1, 1, False, ()
+
+    @staticmethod
+    def tables(dev) -> None:                    # no constants
+        return None
+
+    @staticmethod
+    def scratch(rows: int, dev):                # the fp32 column of the whole row space
+        return torch.zeros(rows + 256, 1, dtype=torch.float32, device=dev)
+
+    def launch(self, ps: _Pass, cur: _Act, mask: torch.Tensor, audio: torch.Tensor) -> None:
+        out = ps.ws.head
+        _conv(ps.pk["conv_post"], cur.p, cur.rows, 7, 1, mask=mask, out_f=out.data_ptr(), ldo=1, act=L.ACT_TANH)
+        audio[:, 0].copy_(out[:cur.rows, 0].view(ps.B, ps.pitch * ps.rate)[:, :ps.T * ps.rate])
+        if ps.keep is not None:
+            ps.keep["out"] = out.clone()
+
+
+class _IstftHead:
+    """iSTFTNet's head (include/efts_abi.h "The head of an iSTFTNet generator"): conv_post emits a log-magnitude and a phase argument per bin of
+    an N-point STFT for L + 1 frames per item, frame 0 on the reflected row a'[0] = a[1]; the inverse STFT with hop N / 4 makes the samples.
+    Three launches: the reflected row is copied one row in front of every item of the last stage's `s` plane (the guard rows for item 0, the gap
+    rows for the others; nothing but conv_post reads that plane), conv_post reads the plane from one row further up, `efts_istft_head` writes
+    the audio, silence past every length included.  The window and the twiddle table are constants, built in float64; no parameters."""
+    writes_silence = True
+
+    def __init__(self, n_fft: int, hop: int):
+        self.n_fft, self.hop = n_fft, hop
+        self.channels, self.samples_per_row = n_fft + 2, hop
+        self._tables = {}                       # device -> fp32 [3 N]: window, then (cos, sin)(2 pi j / N) interleaved
+
+    @staticmethod
+    def refusal(n_fft, hop) -> Optional[str]:
+        if n_fft is None:
+            return None if hop is None else "gen_istft_hop_size without gen_istft_n_fft: the hop belongs to an iSTFT head, which gen_istft_n_fft asks for"
+        if n_fft not in _ISTFT_N:
+            return f"gen_istft_n_fft {n_fft}: efts_istft_head takes {', '.join(map(str, _ISTFT_N))}"
+        if hop is None or hop * 4 != n_fft:
+            return f"gen_istft_hop_size {hop} with gen_istft_n_fft {n_fft}: efts_istft_head overlaps four frames, hop = n_fft / 4 = {n_fft // 4}"
+        return None
+
+    def tables(self, dev) -> torch.Tensor:
+        if dev not in self._tables:
+            ang = 2.0 * math.pi * torch.arange(self.n_fft, dtype=torch.float64) / self.n_fft
+            self._tables[dev] = torch.cat([0.5 - 0.5 * torch.cos(ang), torch.stack([torch.cos(ang), torch.sin(ang)], 1).flatten()]).float().to(dev)
+        return self._tables[dev]
+
+    @property
+    def tag(self):
+        return ("istft", self.n_fft, self.hop, tuple(t.data_ptr() for t in self._tables.values()))
+
+    def scratch(self, rows: int, dev):          # z: conv_post's fp32 result, frame f of item b at row b * pitch + f; the mask of the L + 1 frames
+        return (torch.zeros(rows + 2, self.channels, dtype=torch.float32, device=dev), torch.zeros(rows + 1, dtype=torch.float32, device=dev))
+
+    def launch(self, ps: _Pass, cur: _Act, mask: torch.Tensor, audio: torch.Tensor) -> None:
+        (z, fmask), tab, lib, rows_item = ps.ws.head, self.tables(ps.dev), L.load(), ps.pitch * ps.rate
+        rows = ps.lens * ps.rate
+        frames = torch.where(rows > 0, rows + 1, rows)
+        L.check(lib.efts_row_masks(frames.data_ptr(), None, fmask.data_ptr(), ps.B, ps.T * ps.rate + 1, rows_item, ps.st), "efts_row_masks")
+        g = L.IstftHeadArgs()
+        g.mode, g.B, g.pitch, g.plane, g.ld_plane = L.ISTFT_REFLECT, ps.B, rows_item, cur.p.ptr, cur.p.ld
+        L.check(lib.efts_istft_head(ctypes.byref(g), ps.st), "efts_istft_head")
+        # row r of z is centred on row r - 1 of the plane: a' of item b begins one row in front of the item
+        _conv(ps.pk["conv_post"], cur.p, cur.rows, 7, 1, mask=fmask, out_f=z.data_ptr(), ldo=self.channels, a_ptr=cur.p.ptr - cur.p.ld)
+        g = L.IstftHeadArgs()
+        g.mode, g.B, g.pitch, g.z, g.z_rows, g.lengths, g.len_mul = L.ISTFT_SYNTH, ps.B, rows_item, z.data_ptr(), cur.rows, ps.lens.data_ptr(), ps.rate
+        g.window, g.twiddle, g.n_fft, g.hop = tab.data_ptr(), tab.data_ptr() + 4 * self.n_fft, self.n_fft, self.hop
+        g.audio, g.ld_audio, g.out_len = audio.data_ptr(), audio.shape[2], audio.shape[2]
+        L.check(lib.efts_istft_head(ctypes.byref(g), ps.st), "efts_istft_head")
+        if ps.keep is not None:
+            ps.keep["z"], ps.keep["out"] = z.clone(), audio.clone()
+
+
+def _refusal(rates, kernels, res_kernels, res_dilations, c0, num_mels, resblock: str = "1", istft_n_fft=None, istft_hop=None) -> Optional[str]:
     """why the launches of the stages cannot compute this configuration (None: they can)"""
+    why = _IstftHead.refusal(istft_n_fft, istft_hop)
+    if why is not None:
+        return why
     if resblock not in _BLOCKS:
         return f"resblock {resblock!r}: the reference has ResBlock1 ('1') and ResBlock2 ('2')"
     if not rates or len(rates) != len(kernels):
@@ -252,20 +335,22 @@ class HiFiGANGenerator(nn.Module):
         self.res_dilations = tuple(tuple(d) for d in _cfg(h, "resblock_dilation_sizes"))
         c0 = int(_cfg(h, "upsample_initial_channel"))
         self.num_mels = int(_cfg(h, "num_mels", 80))
+        n_fft, istft_hop = _cfg(h, "gen_istft_n_fft"), _cfg(h, "gen_istft_hop_size")
         why = _refusal(self.upsample_rates, self.upsample_kernel_sizes, self.res_kernels, self.res_dilations, c0, self.num_mels,
-                       self.resblock)
+                       self.resblock, n_fft, istft_hop)
         if why is not None:
             raise NotImplementedError(why)
         self.gap_frames = gap_frames(self.upsample_rates, self.res_kernels, self.res_dilations)
         self._rates = [math.prod(self.upsample_rates[:i]) for i in range(len(self.upsample_rates) + 1)]    # samples per mel frame in front of stage i
-        self.hop = self._rates[-1]
+        self._head = _TanhHead() if n_fft is None else _IstftHead(int(n_fft), int(istft_hop))       # (no module: a head has no parameters)
+        self.hop = self._rates[-1] * self._head.samples_per_row         # samples per mel frame
         self._chain_order = sorted(range(len(self.res_kernels)), key=lambda j: -self.res_kernels[j])   # the longest chain is issued first
         self.conv_pre = weight_norm(nn.Conv1d(self.num_mels, c0, 7, 1, padding=3))
         self.ups = nn.ModuleList([weight_norm(nn.ConvTranspose1d(c0 // 2 ** i, c0 // 2 ** (i + 1), k, u, padding=(k - u) // 2))
                                   for i, (u, k) in enumerate(zip(self.upsample_rates, self.upsample_kernel_sizes))])
         self.resblocks = nn.ModuleList([_BLOCKS[self.resblock](m.out_channels, k, d) for m in self.ups
                                         for k, d in zip(self.res_kernels, self.res_dilations)])
-        self.conv_post = weight_norm(nn.Conv1d(self.ups[-1].out_channels, 1, 7, 1, padding=3))
+        self.conv_post = weight_norm(nn.Conv1d(self.ups[-1].out_channels, self._head.channels, 7, 1, padding=3))
         self._packed, self._packed_dev = None, None             # Dict[str, _Conv] and the device it was packed for
         self._bufs, self._bstreams = Cache(capacity=3), []      # (B, T) -> _Workspace; the side streams of the residual chains
         # per-shape hipGraph of the ~85 launches of a call (round 6; efficient_tts_amd/graphs.py, the acoustic model's cache): one utterance is
@@ -346,7 +431,7 @@ class HiFiGANGenerator(nn.Module):
                                  mask=torch.zeros(n_i + 1, dtype=torch.float32, device=dev)))
             rows = n_i
         return _Workspace(pitch, mel, pre, stages, mask_mel=torch.zeros(B * pitch + 1, dtype=torch.float32, device=dev),
-                          out=torch.zeros(rows + 256, 1, dtype=torch.float32, device=dev))
+                          head=self._head.scratch(rows, dev))
 
     def _branch_streams(self, dev, count: int):
         if len(self._bstreams) != count or (count and self._bstreams[0].device != dev):
@@ -367,6 +452,7 @@ class HiFiGANGenerator(nn.Module):
         L.require_device()
         dev = x.device
         pk = self._pack(dev)
+        self._head.tables(dev)                  # (constants of the head on the device, made once, outside any capture)
         B, _, T = x.shape
         lens = torch.full((B,), T, dtype=torch.int32, device=dev) if lengths is None else lengths.to(device=dev, dtype=torch.int32).clamp(0, T)
         mel = x.transpose(1, 2).float()
@@ -375,10 +461,10 @@ class HiFiGANGenerator(nn.Module):
         mel = mel.contiguous()
 
         def body(mel_btc, lens_i32):
-            audio = torch.zeros(B, 1, T * self.hop, dtype=torch.float32, device=dev)
+            audio = (torch.empty if self._head.writes_silence else torch.zeros)(B, 1, T * self.hop, dtype=torch.float32, device=dev)
             with O.stream_scope():
                 ws = self._workspace_for(B, T, dev)
-                self._run(_Pass(ws=ws, pk=pk, B=B, T=T, pitch=ws.pitch, hop=self.hop, lens=lens_i32, dev=dev, st=O._stream(),
+                self._run(_Pass(ws=ws, pk=pk, B=B, T=T, pitch=ws.pitch, rate=self._rates[-1], lens=lens_i32, dev=dev, st=O._stream(),
                                 split=self.split, fused=self._rb2_fused, keep=keep), mel_btc, audio)
             return (audio,)
 
@@ -388,8 +474,8 @@ class HiFiGANGenerator(nn.Module):
             return body(mel, lens)[0]
         ws = self._workspace_for(B, T, dev)
         # the graph is valid while the buffers its launches point at live: this workspace and the packed planes
-        tag = (id(ws), tuple(cv.w.ptr for cv in pk.values()), self.split, self.fused_resblock2)
-        return self._graph_cache.run(("voc", B, T), tag, (mel, lens), body, keepalive=(ws, pk), adaptive=True)[0]
+        tag = (id(ws), tuple(cv.w.ptr for cv in pk.values()), self.split, self.fused_resblock2) + self._head.tag
+        return self._graph_cache.run(("voc", B, T), tag, (mel, lens), body, keepalive=(ws, pk, self._head), adaptive=True)[0]
 
     def _rb2_fused(self, c: int, k: int, ds) -> bool:   # which arm runs a ResBlock2 of this geometry (the constructor refused what neither can)
         return _ResBlock2.fusable(c, k, ds) if self.fused_resblock2 else not _ResBlock2.composable(k, ds)
@@ -398,7 +484,8 @@ class HiFiGANGenerator(nn.Module):
         """ps.keep (None: nothing happens): after each step a clone of what it wrote, made on the stream of the step's launch and complete when `_run`
         returns (it ends with a device synchronisation then).  Whole buffers, guard rows included: "pre", "x{i}", "s{i}" operand planes (uint8
         [alloc][ld], row 0 at _GUARD); "r{i}.{j}.{d}" fp32 [alloc][c] of residual block j after pair d (ResBlock2: "r{i}.{j}", the block's fp32
-        output); "up{i}" fp32 [rows][c] behind the u / 2-row offset; "out" fp32 [rows + 256][1]; "pitch": rows per item at mel rate."""
+        output); "up{i}" fp32 [rows][c] behind the u / 2-row offset; "out" fp32 [rows + 256][1]; "pitch": rows per item at mel rate.  An iSTFT
+        head: "z" fp32 [rows + 2][N + 2], conv_post's result with frame f of item b at row b * pitch * rate + f, and "out", the audio."""
         cur = self._stage_pre(ps, mel_btc)
         for i in range(len(self.ups)):
             up = self._stage_upsample(ps, i, cur)
@@ -463,12 +550,8 @@ class HiFiGANGenerator(nn.Module):
             ps.keep[f"s{i}"] = s_p.buf.clone()
         return _Act(s_p, up.rows)
 
-    def _stage_post(self, ps: _Pass, cur: _Act, audio: torch.Tensor) -> None:      # the head: conv_post + tanh (:130-131), the items out of the row space
-        out = ps.ws.out
-        _conv(ps.pk["conv_post"], cur.p, cur.rows, 7, 1, mask=ps.ws.stages[-1].mask, out_f=out.data_ptr(), ldo=1, act=L.ACT_TANH)
-        audio[:, 0].copy_(out[:cur.rows, 0].view(ps.B, ps.pitch * ps.hop)[:, :ps.T * ps.hop])
-        if ps.keep is not None:
-            ps.keep["out"] = out.clone()
+    def _stage_post(self, ps: _Pass, cur: _Act, audio: torch.Tensor) -> None:      # the head: `_TanhHead` (:130-131) or `_IstftHead`
+        self._head.launch(ps, cur, ps.ws.stages[-1].mask, audio)
 
 
 def load_hifigan_generator(device, config_path: str, checkpoint_path: str, precision: str = "bf16x3") -> HiFiGANGenerator:

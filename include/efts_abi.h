@@ -110,7 +110,8 @@ extern "C" {
  *        + efts_pauses, efts_pauses_pcm16, efts_pauses_workspace_bytes (shortening the long pauses inside a recording): exports added, the
  *          revision stays by the same rule
  *        + efts_resblock2 (one HiFi-GAN ResBlock2, two dilated convolutions fused through LDS): export added, the revision stays by the
- *          same rule */
+ *          same rule
+ *        + efts_istft_head (the inverse-STFT head of an iSTFTNet generator): export added, the revision stays by the same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -1492,6 +1493,66 @@ typedef struct efts_resblock2_args {
     int32_t reserved;     /* 0 */
 } efts_resblock2_args;
 int efts_resblock2(const efts_resblock2_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The head of an iSTFTNet generator (Kaneko et al., ICASSP 2022: a HiFi-GAN trunk whose conv_post emits N + 2 channels, a log-magnitude
+ * and a phase argument per bin of an N-point STFT, followed by an inverse STFT with hop h = N / 4).  N in {8, 16, 32}.
+ * Per item: L rows at the last stage (L = lengths[b] * len_mul; 0 or >= 4), a[m] the C-channel row of leaky_relu(mean, 0.01), m < L.
+ *   Reflection pad (1, 0):  a'[0] = a[1], a'[m] = a[m - 1] for m = 1 .. L: the item has L + 1 frames.
+ *   Convolution:            z[f][c] = bias[c] + sum_{j = 0 .. 6} W[c][:, j] . a'[f + j - 3], a' = 0 outside 0 .. L, f = 0 .. L, c = 0 .. N + 1.
+ *                           (an efts_gemm launch of 7 taps on the plane of a', n = N + 2, fp32 output with ldo = N + 2, no activation, a row
+ *                           mask over the L + 1 frames: the operand rounding of the three formats is that launch's)
+ *   Spectrum, K = N / 2 + 1, k < K:  mag = exp(z[f][k]), ph = sin(z[f][K + k]), X_f[k] = mag * (cos ph + i sin ph); the imaginary
+ *                           parts of bins 0 and N / 2 are ignored.
+ *   Frame, n < N:           y_f[n] = (1 / N) * ((Re X[0] + (-1)^n Re X[N/2]) + 2 * sum_{k = 1 .. N/2 - 1} (Re X[k] cos(2 pi k n / N) -
+ *                           Im X[k] sin(2 pi k n / N))), the sum in ascending k, one fused multiply-add per product, the cosines and
+ *                           sines read from `twiddle` at (k n) mod N.
+ *   Window:                 w[n] = 0.5 - 0.5 cos(2 pi n / N) (periodic Hann), built by the host in float64 and rounded to fp32: `window`.
+ *   Output, 0 <= t < h L:   u = t + N / 2, F(u) = { f : 0 <= f <= L, h f <= u < h f + N },
+ *                           out[t] = (sum_{f in F(u)} w[u - h f] * y_f[u - h f]) / (sum_{f in F(u)} w[u - h f]^2), both sums in ascending f
+ *                           (at most four terms; the divisor is the true envelope: 1.5 inside, other values in the first and last N / 2
+ *                           samples, never 0); out[t] = 0 for h L <= t < out_len.
+ * This is torch.istft(mag * exp(1j * ph), N, h, N, window=hann_window(N), center=True) of the published TorchSTFT.inverse.
+ *
+ * mode EFTS_ISTFT_SYNTH: z fp32 [z_rows][N + 2] (row stride N + 2 exactly) in the row space of the batch, frame f of item b at row
+ *   b * pitch + f; lengths int32 [B]; window fp32 [N]; twiddle fp32 [N][2] = (cos, sin)(2 pi j / N); audio fp32 [B][ld_audio], samples
+ *   0 .. out_len - 1 of every item are written (out_len % 4 == 0).  One workgroup owns 1024 consecutive samples of one item (1024 / h
+ *   frames of hops), stages the frames that touch them (one in front, two behind) with 16-byte loads, turns them into windowed frames
+ *   in LDS and overlap-adds from there; 16-byte stores.  L is clipped to out_len / h and to pitch - 1.  Rows of z outside an item's
+ *   frames are never used: an item gives the same bits alone, anywhere in a batch and whatever lies behind it.  No atomics, nothing read
+ *   back, no launch geometry from device data: capturable.
+ * mode EFTS_ISTFT_REFLECT: the reflected row.  plane: row 0 of the operand plane of a (any format, row stride ld_plane bytes, at least one
+ *   row in front of row 0); for every item the whole row b * pitch + 1 is copied to row b * pitch - 1, so that a contraction reading
+ *   the plane from one row further up sees a'.  (The row lies in the guard rows for item 0 and in the gap rows behind the item in front
+ *   for the others; the caller keeps L + 4 <= pitch.)  Only B, pitch, plane and ld_plane are read.
+ * EFTS_EINVAL: null args / operand, n_fft outside {8, 16, 32}, hop != n_fft / 4, mode outside 0 .. 1, reserved != 0.  EFTS_ESHAPE: B outside
+ * 1 .. 65535, pitch < 4 or odd, len_mul < 1, z_rows < 1, out_len < 4 or % 4 != 0, ld_audio < out_len.  EFTS_EALIGN: z, audio or plane not
+ * 16-byte aligned, ld_audio % 4 != 0, ld_plane % 16 != 0.
+ * ---------------------------------------------------------------------------------- */
+#define EFTS_ISTFT_SYNTH 0
+#define EFTS_ISTFT_REFLECT 1
+#define EFTS_ISTFT_RUN 1024 /* samples per workgroup */
+typedef struct efts_istft_head_args {
+    const float* z;         /* fp32 [z_rows][n_fft + 2] */
+    const int32_t* lengths; /* [B] */
+    const float* window;    /* [n_fft] */
+    const float* twiddle;   /* [n_fft][2] */
+    float* audio;           /* fp32 [B][ld_audio] */
+    int64_t ld_audio;       /* elements, % 4 == 0 */
+    void* plane;            /* EFTS_ISTFT_REFLECT: row 0 of the operand plane */
+    int64_t ld_plane;       /* bytes, % 16 == 0 */
+    int32_t mode;           /* EFTS_ISTFT_SYNTH or EFTS_ISTFT_REFLECT */
+    int32_t B;              /* items */
+    int32_t pitch;          /* rows per item in the row space, even */
+    int32_t z_rows;         /* rows of z that may be read */
+    int32_t len_mul;        /* rows per unit of `lengths` */
+    int32_t out_len;        /* samples written per item, % 4 == 0 */
+    int32_t n_fft;          /* 8, 16 or 32 */
+    int32_t hop;            /* n_fft / 4 */
+    int32_t reserved;       /* 0 */
+    int32_t reserved2;      /* 0 */
+} efts_istft_head_args;
+int efts_istft_head(const efts_istft_head_args* a, void* stream);
 
 #ifdef __cplusplus
 }
