@@ -150,3 +150,37 @@ def reference(case, dtype=np.int16):
     """the reference's result for every item of a case, as a list"""
     x = case["x"] if dtype == np.int16 else as_float(case["x"])
     return [measure(x[b, :v], case["fs"], case["target"], case["ceiling"]) for b, v in enumerate(case["lengths"])]
+
+
+# ---- the inputs of tests/test_audio_boundaries_*.py: items past one turn (LD_THREADS = 256, csrc/efts_loudness.hip:24) of the four strided
+# loops of loud_decide_kernel: over the segments' peaks (:122), the sub-blocks (:115) and the 400 ms blocks of both gates (:132, :142)
+DECIDE_TURN = 256
+BOUNDARY_FS = 8000                                                     # the lowest rate: h = 800, the fewest samples per sub-block
+BOUNDARY_NAMES = ("segments_257", "blocks_256", "blocks_257", "blocks_258_late", "short")
+BOUNDARY_LENGTHS = (256 * SEGMENT + 1, 259 * 800, 260 * 800, 261 * 800 + 123, 40000)
+
+
+def boundary_case(ceiling):
+    """dict(fs, x int16 [5, n], lengths, target, ceiling) at 8000 Hz, full scale behind every length.
+    segments_257: 131 073 samples, the smallest item with a segment at index 256; that segment is its last sample, and the item's peak.
+    blocks_256 / blocks_257: 259 and 260 sub-blocks: the gates' loops end with a full first turn, and take one block in a second.
+    blocks_258_late: 261 sub-blocks and 123 samples; quiet bursts, then from sub-block 256 on the loudest stretch of the item, with the peak
+    in it (segment 400 and above): blocks, sub-blocks and peak of the second turn decide loudness and gain.
+    short: 40 000 samples, inside every first turn.
+    `ceiling` None: the target of -23 LUFS decides every gain; 0.5 with a target of -14 LUFS: the peak does."""
+    rng = np.random.default_rng(8000)
+    fs = BOUNDARY_FS
+    x = np.full((len(BOUNDARY_LENGTHS), max(BOUNDARY_LENGTHS)), 32767, dtype=np.int16)
+    for b, n in enumerate(BOUNDARY_LENGTHS):
+        s = _bursts(rng, n, fs, loud=0.1 + 0.02 * b, quiet_db=-50.0)
+        if b == 0:
+            s[-1] = 0.9
+        elif b == 3:
+            late = 256 * (fs // 10)
+            s[late:] = rng.uniform(-0.4, 0.4, size=n - late)
+            s[late + 1234] = 0.95
+        else:
+            s[n // 3] = 0.8
+        x[b, :n] = _quantise(s)
+    x.setflags(write=False)
+    return dict(fs=fs, x=x, lengths=list(BOUNDARY_LENGTHS), target=-23.0 if ceiling is None else -14.0, ceiling=ceiling)

@@ -142,3 +142,80 @@ def yardstick(pcm16=False, H=256, W=1024):
             worst = max(worst, float(np.abs(yardstick_item(x[b, :L], H, W, table32).astype(np.float64) - ref[b][0]).max()))
     zero = np.zeros(2049, dtype=x.dtype)
     return max(worst, float(np.abs(yardstick_item(zero, H, W, table32).astype(np.float64) - mel_cepstrum(zero, H, W)).max()))
+
+
+# ---- the inputs of tests/test_audio_boundaries_*.py: items whose frames end on either side of what one workgroup of logspec_project_kernel
+# takes (LP_UPB = 64 pairs, 128 frames: csrc/efts_mcep.hip:28), and frame sequences on either side of one step of frame_dist_kernel
+# (FD_CHUNK = 1024 frames: csrc/efts_mcep.hip:117)
+FRAMES_PER_WORKGROUP, DIST_CHUNK = 128, 1024
+BOUNDARY_FRAMES = (127, 128, 129, 130)
+BOUNDARY_CONFIGS = (("fp32", False, 256, 1024), ("int16", True, 256, 1024), ("fp32_hop120_win600", False, 120, 600), ("int16_hop120_win600", True, 120, 600))
+BOUNDARY_REST = {256: (17, 0, 255, 100), 120: (7, 0, 119, 60)}        # len = H (T - 1) + r, 0 <= r < H
+BOUNDARY_SEEDS = (2, 5, 0, 0)                                         # searched like SEEDS: every power cell at least 1e-5 at both hops
+
+
+def boundary_lengths(H):
+    return tuple(H * (T - 1) + r for T, r in zip(BOUNDARY_FRAMES, BOUNDARY_REST[H]))
+
+
+@functools.lru_cache(maxsize=None)
+def _boundary_pcm(item):
+    return pcm(boundary_lengths(256)[item], item, BOUNDARY_SEEDS[item])
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_batch(pcm16=False, H=256):
+    """(x [4, max], lengths): item b is one signal on the int16 grid -- at hop 120 its first H (T - 1) + r samples --, behind it NaN (fp32)
+    or -32768 (int16)"""
+    lengths = boundary_lengths(H)
+    x = np.full((4, max(lengths)), -32768, dtype=np.int16) if pcm16 else np.full((4, max(lengths)), np.nan, dtype=np.float32)
+    for b, L in enumerate(lengths):
+        v = _boundary_pcm(b)[:L]
+        x[b, :L] = v if pcm16 else v.astype(np.float32) / np.float32(ST.MAX_WAV)
+    x.setflags(write=False)
+    return x, np.asarray(lengths, dtype=np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_reference(pcm16=False, H=256, W=1024):
+    """per item: (mc [T, ORDER] float64, the smallest power cell)"""
+    x, lengths = boundary_batch(pcm16, H)
+    out = []
+    for b, L in enumerate(lengths):
+        P = power(x[b, :L], H, W)
+        out.append((mel_cepstrum_of_log_power(np.log(P)), float(P.min())))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_yardstick(pcm16=False, H=256, W=1024):
+    """max |fp32 yardstick - float64 reference| over boundary_batch (CPU)"""
+    from efficient_tts_amd.mcep import mcep_table
+    table32 = mcep_table(N, ORDER, ALPHA).astype(np.float32)
+    x, lengths = boundary_batch(pcm16, H)
+    ref = boundary_reference(pcm16, H, W)
+    return max(float(np.abs(yardstick_item(x[b, :L], H, W, table32).astype(np.float64) - ref[b][0]).max()) for b, L in enumerate(lengths))
+
+
+DIST_COUNTS = (1023, 1024, 1025, 2049, 5)     # n = min(Ta, Tb) per pair
+DIST_DIMS = (ORDER + 1, ORDER)                # with and without c~[0]
+
+
+def dist_frames(D, seed=0):
+    """(x fp32 [B, Tx, D], x_frames, y fp32 [B, Ty, D], y_frames): cepstrum-like rows (coefficient k falls off as 1 / (1 + k)), y a disturbed
+    copy whose disturbance grows along the item; the shorter side alternates; NaN in the rows at and beyond each count"""
+    rng = np.random.default_rng(seed + D)
+    B, T = len(DIST_COUNTS), max(DIST_COUNTS) + 3
+    x = np.full((B, T, D), np.nan, dtype=np.float32)
+    y = np.full((B, T + 2, D), np.nan, dtype=np.float32)
+    xf, yf = [], []
+    for b, n in enumerate(DIST_COUNTS):
+        ta, tb = (n, min(n + 2, T + 2)) if b % 2 == 0 else (min(n + 3, T), n)
+        fall = 1.0 / (1.0 + np.arange(D))
+        x[b, :ta] = (rng.standard_normal((ta, D)) * fall).astype(np.float32)
+        y[b, :tb] = (rng.standard_normal((tb, D)) * fall).astype(np.float32)
+        m = min(ta, tb)
+        y[b, :m] = (x[b, :m] + np.linspace(0.05, 0.5, m)[:, None] * y[b, :m]).astype(np.float32)
+        xf.append(ta)
+        yf.append(tb)
+    return x, np.asarray(xf, dtype=np.int32), y, np.asarray(yf, dtype=np.int32)

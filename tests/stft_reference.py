@@ -109,3 +109,34 @@ def batch(lengths=LENGTHS, seed=0, fill=None):
     for b, L in enumerate(lengths):
         x[b, :L], y[b, :L] = signal(L, seed + b)
     return x, y
+
+
+# ---- the inputs of tests/test_audio_boundaries_*.py: items whose frames end on either side of what one workgroup of stft_kernel takes
+# (2 UPB frames) and of what one step of stft_reduce_kernel sums (ST_CHUNK frames)
+FRAMES_PER_WORKGROUP = {256: 256, 512: 128, 1024: 64, 2048: 32}      # 2 * st_cfg<N>::UPB (csrc/efts_stft.hip:40)
+REDUCE_CHUNK = 1024                                                   # ST_CHUNK (csrc/efts_stft.hip:27)
+BOUNDARY_MAG = ((256, 64, 256), (512, 50, 240), (1024, 120, 600))     # the smallest hop the project uses at each size
+BOUNDARY_DIST = (512, 50, 240)
+BOUNDARY_DIST_FRAMES = (1024, 1025, 2049, 130)
+
+
+def boundary_mag_lengths(N, H):
+    """T = 2 UPB - 1, 2 UPB, 2 UPB + 1, 2 UPB + 2: the first workgroup ends on an unpaired frame, is exactly full, then the second one holds
+    an unpaired frame, then one pair"""
+    per = FRAMES_PER_WORKGROUP[N]
+    return tuple(H * (T - 1) for T in (per - 1, per, per + 1, per + 2))
+
+
+def boundary_dist_lengths():
+    return tuple(BOUNDARY_DIST[1] * (T - 1) for T in BOUNDARY_DIST_FRAMES)
+
+
+def boundary_batch(lengths, seed, fp32_x=True):
+    """x (fp32 with NaN behind every item, or int16 with -32768 there) and y (int16, -32768 behind every item) of signal()"""
+    n = max(lengths)
+    x = np.full((len(lengths), n), np.nan, dtype=np.float32) if fp32_x else np.full((len(lengths), n), -32768, dtype=np.int16)
+    y = np.full((len(lengths), n), -32768, dtype=np.int16)
+    for b, L in enumerate(lengths):
+        xf, y[b, :L] = signal(L, seed + b)
+        x[b, :L] = xf if fp32_x else np.round(xf * np.float32(MAX_WAV)).astype(np.int16)
+    return x, y

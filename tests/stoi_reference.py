@@ -174,3 +174,121 @@ def yardstick(pcm16: bool = False) -> float:
             if r["segments"]:
                 worst = max(worst, abs(q["stoi"] - r["stoi"]), abs(q["estoi"] - r["estoi"]))
     return worst
+
+
+# ---- the inputs of tests/test_audio_boundaries_*.py: items long enough to leave the first turn of stoi_select_kernel's scan (256 frames)
+# and the first chunk of stoi_reduce_kernel's sum (512 segments)
+
+def frame_energies(x) -> np.ndarray:
+    """e[f] of stoi(): the float64 energies of the windowed frames of x"""
+    x = np.asarray(x).astype(np.float64)
+    F = frame_count(x.shape[0])
+    idx = HOP * np.arange(F)[:, None] + np.arange(FRAME)[None, :]
+    xf = window() * x[idx]
+    return (xf * xf).sum(axis=1)
+
+
+def keep_flags(x) -> np.ndarray:
+    """the frames stoi() keeps: e 10^4 > e_max"""
+    e = frame_energies(x)
+    return e * 1e4 > e.max() if e.size else np.zeros(0, dtype=bool)
+
+
+def truncate_to_kept_fast(x: np.ndarray, K: int) -> int:
+    """truncate_to_kept(x, K) from the frame energies alone: a prefix of F' frames keeps the frames whose energy times 10^4 exceeds the
+    running maximum over that prefix"""
+    e = frame_energies(x)
+    for F in range(1, e.shape[0] + 1):
+        kept = int((e[:F] * 1e4 > e[:F].max()).sum())
+        if kept >= K:
+            assert kept == K
+            return FRAME + HOP * (F - 1)
+    raise AssertionError(f"x never keeps {K} frames")
+
+
+def dense(n: int, seed: int) -> np.ndarray:
+    """a stationary complex of 12 tones between 200 and 3500 Hz, amplitude 0.05 each, plus white noise of 0.01: no frame is silent by the 40 dB
+    rule; fp32 at 10 000 Hz"""
+    rng = np.random.default_rng(seed)
+    t = np.arange(n, dtype=np.float64) / FS
+    tones = sum(0.05 * np.sin(2.0 * np.pi * f * t + rng.uniform(0, 2 * np.pi)) for f in np.linspace(200.0, 3500.0, 12))
+    return (tones + 0.01 * rng.standard_normal(n)).astype(np.float32)
+
+
+def add_ramped_noise(x: np.ndarray, snr_from: float, snr_to: float, seed: int) -> np.ndarray:
+    """x + white noise whose level moves linearly in dB from `snr_from` to `snr_to` against x's mean power over the item: the segments' sums
+    then differ along the item, so a sum that takes the wrong segments is a wrong sum.  fp32"""
+    rng = np.random.default_rng(seed)
+    p = float(np.mean(np.asarray(x, dtype=np.float64) ** 2))
+    snr = np.linspace(snr_from, snr_to, x.shape[0])
+    return (x + np.sqrt(p / 10.0 ** (snr / 10.0)) * rng.standard_normal(x.shape[0])).astype(np.float32)
+
+
+def length_of_frames(F: int) -> int:
+    return FRAME + HOP * (F - 1)
+
+
+SCAN_FRAMES = (256, 257, 300, 182)            # the last one is the neighbour that ends inside the first turn
+SCAN_SEEDS = (34, 33, 35, 36)                 # searched: tests/test_audio_boundaries_cpu.py checks what they must give
+REDUCE_SEGMENTS = (512, 513, 1025, 513, 60)   # M per item; the fourth is speech_like truncated to K = 543, the last the short neighbour
+REDUCE_SEEDS = (41, 42, 43, 46, 45)
+
+
+def boundary_batch(which: str):
+    """(x fp32 [B, ld], y fp32 [B, ld], lengths, names) with NaN behind every item.
+    "scan": speech_like items of 256, 257 and 300 frames and one of 182.
+    "reduce": dense items with M = 512, 513 and 1025 segments, one speech_like item truncated to K = 543 kept frames, one speech_like
+    item of about 60 segments."""
+    key = ("boundary", which)
+    if key not in _cache:
+        items = []
+        if which == "scan":
+            for F, seed in zip(SCAN_FRAMES, SCAN_SEEDS):
+                items.append((f"F{F}", speech_like(length_of_frames(F), seed)))
+        else:
+            for i, (M, seed) in enumerate(zip(REDUCE_SEGMENTS, REDUCE_SEEDS)):
+                if i < 3:
+                    items.append((f"dense_M{M}", dense(length_of_frames(M + SEGMENT), seed)))
+                elif i == 3:
+                    full = speech_like(160000, seed)
+                    items.append((f"speech_K{M + SEGMENT}", full[:truncate_to_kept_fast(full, M + SEGMENT)]))
+                else:
+                    items.append(("speech_short", speech_like(LD, seed)))
+        lengths = np.asarray([len(v) for _, v in items], dtype=np.int32)
+        x = np.full((len(items), int(lengths.max())), np.nan, dtype=np.float32)
+        y = x.copy()
+        for b, (_, v) in enumerate(items):
+            x[b, :len(v)] = v
+            y[b, :len(v)] = add_ramped_noise(v, 15.0, -5.0, 2000 + b)
+        for v in (x, y, lengths):
+            v.setflags(write=False)
+        _cache[key] = (x, y, lengths, tuple(name for name, _ in items))
+    return _cache[key]
+
+
+def boundary_pcm16(a: np.ndarray, lengths) -> np.ndarray:
+    """the batch as int16, -32768 behind every item"""
+    out = np.full(a.shape, -32768, dtype=np.int16)
+    for b, n in enumerate(lengths):
+        out[b, :n] = to_pcm16(a[b, :n])
+    return out
+
+
+def boundary_reference(which: str, pcm16: bool = False, dtype=np.float64):
+    """[stoi() dict per item] of boundary_batch(which) (through int16 and back when `pcm16`) -- computed once per process"""
+    key = ("boundary_ref", which, pcm16, np.dtype(dtype).name)
+    if key not in _cache:
+        x, y, lengths, _ = boundary_batch(which)
+        conv = (lambda a: to_pcm16(a).astype(np.float32) * np.float32(1.0 / 32768.0)) if pcm16 else (lambda a: a)
+        _cache[key] = [stoi(conv(x[b, :n]), conv(y[b, :n]), dtype) for b, n in enumerate(lengths)]
+    return _cache[key]
+
+
+def boundary_yardstick(which: str, pcm16: bool = False) -> float:
+    """max |fp32 definition - float64 reference| over both scores of every item of boundary_batch(which) (CPU)"""
+    worst = 0.0
+    for r, q in zip(boundary_reference(which, pcm16), boundary_reference(which, pcm16, np.float32)):
+        assert (r["frames"], r["kept"], r["segments"]) == (q["frames"], q["kept"], q["segments"])
+        if r["segments"]:
+            worst = max(worst, abs(q["stoi"] - r["stoi"]), abs(q["estoi"] - r["estoi"]))
+    return worst

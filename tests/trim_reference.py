@@ -68,3 +68,60 @@ def items(dtype=np.int16, seed=2027):
     if dtype == np.int16:
         return x
     return (x.astype(np.float32) * np.float32(2.0 ** -15)).astype(np.float32)
+
+
+# ---- the inputs of tests/test_audio_boundaries_*.py: items past one workgroup of launch A (F frames), past one turn of launch B's strided
+# loops (256 frames) and past one workgroup of launch C (TR_COPY outputs)
+SCAN_TURN, COPY_BLOCK = 256, 4096             # TR_THREADS (csrc/efts_trim_energy.h:11), TR_COPY (csrc/efts_trim_energy.h:15)
+# a hop of 202 = 2 (mod 8): with it start = (first sound frame - keep_frames) * H is no multiple of 4 for an odd frame, which no hop of PAIRS
+# can give
+BOUNDARY_PAIRS = PAIRS + [(1024, 202)]
+BOUNDARY_KEEP = 0
+BOUNDARY_NAMES = ("energy_full", "energy_plus_1", "first_sound_past_turn", "last_sound_past_turn", "copy_4095", "copy_4096", "copy_4097", "copy_8293",
+                  "short")
+
+
+def energy_frames(W, H):
+    """F of tr_launch_energy (csrc/efts_trim_energy.h:106): the frames of one workgroup of launch A"""
+    return max(1, min(64, (12288 - W) // H + 1))
+
+
+def _shape(rng, n, lead, burst_end):
+    """int16 [n]: uniform noise 45 dB under the burst, the burst (amplitude 20000) over [lead, burst_end), the low level again"""
+    low = 20000.0 * 10.0 ** (-45.0 / 20.0)
+    amp = np.full(n, low)
+    amp[lead:burst_end] = 20000.0
+    return np.round(rng.uniform(-1.0, 1.0, size=n) * amp).astype(np.int16)
+
+
+def boundary_items(W, H, dtype=np.int16, seed=4242):
+    """(x [9, ld_in], lengths): the items of BOUNDARY_NAMES, full scale (32767) behind every item; ld_in = 3 (mod 8): no row but the first
+    is aligned.  fp32: the same integers times 2^-15, exact.
+    energy_full / energy_plus_1: F H and F H + 1 samples, the burst from 3 / 8 of the item to its end, and the item's largest sample (30000)
+    is its last: with keep_frames = 0 the last frame decides new_len and the last hop chunk the gain; in energy_plus_1 both belong to the
+    second workgroup of launch A.
+    first_sound_past_turn: 262 hops of the low level -- noise, not zeros --, a burst of 3 hops, 2 hops of the low level.
+    last_sound_past_turn: 3 hops of the low level, the burst up to hop 260, 6 hops of the low level and 5 samples.
+    copy_N: 6 hops and 3 samples of the low level, then the burst to the item's end, which lies N samples behind `start`."""
+    rng = np.random.default_rng(seed + W + H)
+    F = energy_frames(W, H)
+    rows = []
+    for n in (F * H, F * H + 1):
+        rows.append(_shape(rng, n, 3 * n // 8, n))
+        rows[-1][-1] = 30000
+    rows.append(_shape(rng, 267 * H, 262 * H, 265 * H))
+    rows.append(_shape(rng, 266 * H + 5, 3 * H, 260 * H))
+    for new_len in (4095, 4096, 4097, 8293):
+        full = _shape(rng, 6 * H + 3 + 9000, 6 * H + 3, 6 * H + 3 + 9000)
+        start = trim(full, W=W, H=H, keep_frames=BOUNDARY_KEEP)["start"]
+        rows.append(full[:start + new_len])
+    rows.append(_shape(rng, 1000, 400, 600))
+    lengths = [len(v) for v in rows]
+    ld_in = max(lengths) + 3
+    ld_in += (3 - ld_in) % 8
+    x = np.full((len(rows), ld_in), 32767, dtype=np.int16)
+    for b, v in enumerate(rows):
+        x[b, :len(v)] = v
+    if dtype != np.int16:
+        x = (x.astype(np.float32) * np.float32(2.0 ** -15)).astype(np.float32)
+    return x, tuple(lengths)
