@@ -119,6 +119,13 @@ class IstftHeadArgs(C.Structure):
                 ("reserved", i32), ("reserved2", i32)]
 
 
+class SnakeAAArgs(C.Structure):
+    """mirror of `struct efts_snake_aa_args` (include/efts_abi.h)"""
+    _fields_ = [("x", vp), ("ldx", i64), ("lengths", vp), ("a", vp), ("inv_b", vp), ("plane", vp), ("ld_plane", i64), ("out", vp), ("ldo", i64),
+                ("split", i32), ("B", i32), ("pitch", i32), ("T", i32), ("len_mul", i32), ("c", i32), ("reserved", i32), ("reserved2", i32)]
+
+
+SNAKE_SEG = 32                          # EFTS_SNAKE_SEG: rows per lane of efts_snake_aa (a segment recomputes 10 rows of halo)
 ISTFT_SYNTH, ISTFT_REFLECT = 0, 1       # EFTS_ISTFT_*: the two launches of efts_istft_head
 ISTFT_RUN = 1024                        # EFTS_ISTFT_RUN: samples per workgroup
 WGRAD_MAX_ITEMS = 8
@@ -270,6 +277,8 @@ _SIGS = {
     "efts_resblock2": (i32, [C.POINTER(ResBlock2Args), vp]),
     # the inverse-STFT head of an iSTFTNet generator (and the reflected row in front of every item of its operand plane)
     "efts_istft_head": (i32, [C.POINTER(IstftHeadArgs), vp]),
+    # BigVGAN's anti-aliased Snake / SnakeBeta activation (upsample, activate, low-pass and downsample in one launch)
+    "efts_snake_aa": (i32, [C.POINTER(SnakeAAArgs), vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -111,7 +111,8 @@ extern "C" {
  *          revision stays by the same rule
  *        + efts_resblock2 (one HiFi-GAN ResBlock2, two dilated convolutions fused through LDS): export added, the revision stays by the
  *          same rule
- *        + efts_istft_head (the inverse-STFT head of an iSTFTNet generator): export added, the revision stays by the same rule */
+ *        + efts_istft_head (the inverse-STFT head of an iSTFTNet generator): export added, the revision stays by the same rule
+ *        + efts_snake_aa (BigVGAN's anti-aliased Snake / SnakeBeta activation): export added, the revision stays by the same rule */
 #define EFTS_ABI_VERSION 602
 int efts_version(void);
 const char* efts_last_error(void);
@@ -1553,6 +1554,60 @@ typedef struct efts_istft_head_args {
     int32_t reserved2;      /* 0 */
 } efts_istft_head_args;
 int efts_istft_head(const efts_istft_head_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * BigVGAN's anti-aliased periodic activation (Lee et al., ICLR 2023: Activation1d around Snake / SnakeBeta) in ONE launch: upsample by 2
+ * with a 12-tap Kaiser-windowed sinc, v = u + inv_b sin(a u)^2 per channel, low-pass and downsample by 2 with the same filter, replicate
+ * padding at both ends of every item.
+ * Filter: f[k] = 0.5 w[k] sinc(0.5 (k - 5.5)) normalised to sum 1, w = the symmetric Kaiser window of 12 points with beta = 0.1102 (A - 8.7),
+ *   A = 2.285 * 5 * pi * 1.2 + 7.95 (cutoff 0.25, half-width 0.3); built in float64, rounded once to fp32, compiled into the kernel.
+ *   f[11 - k] = f[k]; f[0 .. 5] = 0.0020289664498962423, 0.00938946394406788, -0.02554346406529466, -0.05765737547536495,
+ *   0.12857260908132875, 0.4432098000653667.
+ * Per item b: L = clamp(lengths[b], 0, T) * len_mul rows at rows b * pitch .. b * pitch + L - 1 of x, per channel j < c, with
+ * X(i) = x[clamp(i, 0, L - 1)][j]:
+ *   2x-rate sample m, taken at m' = clamp(m, 0, 2L - 1), with i0 = m' >> 1:
+ *     m' even:  u = 2 * sum_{i = 0 .. 5} f[2i + 1] * X(i0 + 2 - i)
+ *     m' odd :  u = 2 * sum_{i = 0 .. 5} f[2i]     * X(i0 + 3 - i)        both sums from 0 in ascending i, one fused multiply-add per term
+ *     v(m) = fma(inv_b[j], s * s, u),  s = sinf(a[j] * u)                  (the product rounded to fp32, the accurate sinf)
+ *   y[t] = sum_{k = 0 .. 11} f[k] * v(2t + k - 5),  t < L                  from 0 in ascending k, one fused multiply-add per term
+ *   y[t] = 0 for L <= t < T * len_mul.  y[t] depends on x[t - 5 .. t + 5] of its own item alone.
+ * Outputs, either or both: `out` fp32 [.][ldo] and `plane`, the operand plane of y in format `split`, rounded as plane_act of efts_gemm
+ * rounds (split 1 bf16(y), nearest even; split 2 hi = bf16(y), lo = bf16(y - hi); split 3 y itself).  Rows b * pitch .. b * pitch +
+ * T * len_mul - 1 of every item are written, columns 0 .. c - 1 of out and every column of the plane's chunks (c .. roundup(c, 64 or 32) - 1
+ * as zeros); the rows between items, guard rows and columns past c of out are not touched.
+ * One lane owns 4 adjacent channels and EFTS_SNAKE_SEG consecutive rows of one item and walks down them with the 6 rows of x of one pair of
+ * 2x-rate samples and the 12 values of v of one output row in registers; a segment recomputes the 10 values in front of its first row.
+ * No LDS, no barrier, no atomics, nothing read back, no launch geometry from device data: capturable.  An item gives the same bits alone,
+ * anywhere in a batch and whatever lies behind it.
+ * a and inv_b are made by the host in float64 from the fp32 parameters and rounded once: a = exp(alpha) (snake_logscale) or alpha;
+ * inv_b = 1 / (a + 1e-9) (Snake) or 1 / (b + 1e-9) with b from beta the same way (SnakeBeta).
+ * EFTS_EINVAL: null args / x / lengths / a / inv_b, neither plane nor out, split outside 1 .. 3 with a plane, reserved != 0.  EFTS_ESHAPE: c < 4 or
+ * c % 4 != 0, B outside 1 .. 65535, T, len_mul or pitch < 1, T * len_mul > pitch, B * pitch > 2^31 - 1, a row stride below the row.
+ * EFTS_EALIGN: x, a, inv_b, out or plane not 16-byte aligned, ldx % 4, ldo % 4 or ld_plane % 16 != 0, lengths not 4-byte aligned.
+ * ---------------------------------------------------------------------------------- */
+#ifndef EFTS_SNAKE_SEG
+#define EFTS_SNAKE_SEG 32 /* rows per lane */
+#endif
+typedef struct efts_snake_aa_args {
+    const float* x;         /* fp32 [B * pitch][ldx] */
+    int64_t ldx;            /* elements, % 4 == 0 */
+    const int32_t* lengths; /* [B] */
+    const float* a;         /* [c] */
+    const float* inv_b;     /* [c] */
+    void* plane;            /* operand plane of the result, row 0, or NULL */
+    int64_t ld_plane;       /* bytes, % 16 == 0 */
+    float* out;             /* fp32 [B * pitch][ldo], or NULL */
+    int64_t ldo;            /* elements, % 4 == 0 */
+    int32_t split;          /* 1, 2 or 3: format of the plane */
+    int32_t B;              /* items */
+    int32_t pitch;          /* rows per item in the row space */
+    int32_t T;              /* units of `lengths` per item at the most: T * len_mul rows of every item are written */
+    int32_t len_mul;        /* rows per unit of `lengths` */
+    int32_t c;              /* channels, % 4 == 0 */
+    int32_t reserved;       /* 0 */
+    int32_t reserved2;      /* 0 */
+} efts_snake_aa_args;
+int efts_snake_aa(const efts_snake_aa_args* a, void* stream);
 
 #ifdef __cplusplus
 }
